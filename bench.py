@@ -7,14 +7,22 @@ weight-gradient reduce-GEMMs and of the forward recurrences as three fp16 MFMAs 
 bits), fp32 accumulate; the kNN filter runs on fp16 planes in every mode (exact after its rerank) — the parity-grade mode (every
 -m gpu test holds it to the exact mode's bars).  Storage: fp32 tensors in HBM, except the aggregated block's activation a3, which
 the f16x3 mode keeps in fp16 where its backward forms dz3 lazily (k = 16 above the size gate; DESIGN.md 8 row g).  The
-exact-fp32-MFMA step is measured in the same run and reported as `exact_f32` and inside `config` (for every world size).
+exact-fp32-MFMA step is measured in the same run under --full and reported as `exact_f32` and inside `config` (for every world size).
 
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
 Rank 0 prints ONE JSON line.  `value` = garments processed by all ranks / max-over-ranks wall time of exactly K
-steps (barrier + synchronize on both sides).  Extra objects:
+steps (barrier + synchronize on both sides); `ms_per_step` = that wall time / K.  A plain run does only that: set up,
+warm up, time the K steps, write the last timed step's outputs when --dump-outputs DIR is given, print the line.
+--dump-outputs DIR: the loss, every prediction tensor and the parameters after the optimizer step of the last timed step, as
+DIR/<name>.npy (fp32; at most 64 MB in all, a larger array is replaced by a fixed, seeded sample of its elements).  The
+inputs, the initial weights and the per-step seeds are fixed, so two builds can be compared output for output.
+Everything else is measured only with --full (off by default), after the timed steps: the exact-fp32 step and the other
+arithmetic modes (`exact_f32`, `fast_math`, `config.exact_f32_value / _ms`), the per-kernel pass (`kernel_ms_per_step`,
+--call-shapes and the roofline objects below), the CPU baseline and, for N > 1, the exchange on its own.  Extra objects:
   roofline      — the dominant kernel of the step, priced as SURVEY.md 8(d) prescribes: t_roof = max(ALGORITHMIC HBM bytes / 8 TB/s,
                   EXECUTED matrix-pipe FLOPs / peak of the instruction it runs) (f16x3: 3 fp16 MFMA FLOPs per algorithmic one vs
                   2.5 PF; exact: 1 vs 157.3 TF), frac = t_roof / launch duration (HIP events on the launch stream; rocprofv3's
@@ -78,6 +86,11 @@ def parse():
     ap.add_argument('--torch-adam', action='store_true', help='torch.optim.Adam instead of the fused arena optimizer')
     ap.add_argument('--reserve-cus', type=int, default=-1, help='compute units left out of every persistent launch (room for RCCL under the '
                     'edge kernels); -1 = the package default: 16 when N > 1, else 0')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also measure the other arithmetic modes, the per-kernel pass (roofline objects), the CPU '
+                         'baseline and, for N > 1, the exchange on its own (the --no-* switches above turn single parts off)')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='write what the last timed step computed (loss, predictions, parameters after the optimizer step) as DIR/<name>.npy')
     return ap.parse_args()
 
 
@@ -464,8 +477,33 @@ def roofline_tables(rec, nsteps, args, step_s, f16_rows):
     return roof, per_kernel, roof_step
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays, budget=DUMP_BUDGET_BYTES):
+    """Writes every tensor of `arrays` ({name: tensor}) as path/<name>.npy: fp64 stays fp64, everything else becomes fp32.  When
+    the arrays exceed `budget` bytes together, every array larger than an equal share of it is replaced by a sample of its
+    flattened elements: a fixed, seeded choice of indices in ascending order, the same in every run of the same shape."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        host[name] = (t.double() if t.dtype == torch.float64 else t.float()).cpu()
+    total = sum(t.numel() * t.element_size() for t in host.values())
+    share = budget // max(len(host), 1)
+    for name, t in host.items():
+        if total > budget and t.numel() * t.element_size() > share:
+            keep = share // t.element_size()
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            t = t.reshape(-1)[idx]
+        np.save(os.path.join(path, name + '.npy'), t.numpy())
+
+
 def main():
     args = parse()
+    if args.call_shapes and not args.full:
+        raise SystemExit('--call-shapes reads the per-kernel pass: add --full')
     d = parse_defaults()
     off = [k for k in ('batch', 'points', 'k', 'model', 'epoch', 'math') if getattr(args, k) != getattr(d, k)]
     if off:
@@ -502,9 +540,13 @@ def main():
     wrapped = parallel.DistributedHotPath(model, device_ids=[dev], arena=arena, reserve_cus=None if args.reserve_cus < 0 else args.reserve_cus)
     feats, gt = synthetic(args.batch, args.points, data_config, seed=1000 + rank, device=dev)
 
+    last = {} if args.dump_outputs else None          # --dump-outputs: the predictions of the latest step (references, no copies)
+
     def step(i):
         torch.manual_seed(i * 131 + rank)              # the decoder draws random LSTM states every forward
         preds = wrapped(feats, log_step=i, epoch=args.epoch)
+        if last is not None:
+            last['preds'] = preds
         loss, _, _ = model.loss(preds, gt, epoch=args.epoch)
         loss.backward()
         wrapped.finish_gradient_sync()
@@ -519,7 +561,14 @@ def main():
         if world > 1 or args.torch_adam:
             raise SystemExit('--graph: single GPU and the fused Adam only')
         from gpe_amd import graph as gpe_graph
-        sg = gpe_graph.StepGraph(lambda f, g: model.loss(wrapped(f, log_step=0, epoch=args.epoch), g, epoch=args.epoch)[0], opt, warmup=2)
+
+        def forward_loss(f, g):
+            preds = wrapped(f, log_step=0, epoch=args.epoch)
+            if last is not None:                        # the capture's tensors: every replay rewrites them
+                last['preds'] = preds
+            return model.loss(preds, g, epoch=args.epoch)[0]
+
+        sg = gpe_graph.StepGraph(forward_loss, opt, warmup=2)
 
         def step(i):
             torch.manual_seed(i * 131 + rank)
@@ -543,11 +592,17 @@ def main():
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = t.item()
     final_loss = loss.item()
+    if args.dump_outputs and rank == 0:
+        out_arrays = {'loss': loss}
+        out_arrays.update(('pred_' + k, v) for k, v in last['preds'].items()
+                          if isinstance(v, torch.Tensor) and v.dtype.is_floating_point)
+        out_arrays['params'] = arena.flat
+        dump_outputs(args.dump_outputs, out_arrays)
 
     # ---- per-kernel durations: HIP events on the launch stream, same workload, right after the timed region ----
     roof, roof_gather, breakdown, per_kernel, roof_step = None, None, None, None, None
     rec = None
-    if not args.no_kernel_timing:
+    if args.full and not args.no_kernel_timing:
         # every rank runs these extra steps (they contain the gradient all-reduce); only rank 0 records events
         nsteps = min(args.steps, 5)
         if rank == 0:
@@ -628,7 +683,7 @@ def main():
 
     # the other arithmetic modes, measured the same way on the same workload (reported beside `value`, never as `value`)
     fast = None
-    if args.math in ('f32', 'f16x3') and not args.no_fast_math_line:
+    if args.full and args.math in ('f32', 'f16x3') and not args.no_fast_math_line:
         fast = {}
         only = None if world == 1 else ('f32', 'f16x3')        # N > 1: the two parity-grade modes (both are first-class numbers)
         for mode, note in (('f32', 'exact fp32: every product on v_mfma_f32_16x16x4_f32 (gpe_math_set(0))'),
@@ -664,13 +719,13 @@ def main():
 
     # ---- the exchange step, for N > 1: what RCCL saw and what it costs -------------------------------------------------
     exchange = None
-    if world > 1:
+    if args.full and world > 1:
         exchange = wrapped.measure_exchange(iters=10)      # every rank participates; rank 0 reports
         exchange['exposed_ms_per_step'] = wrapped.exposed_ms()
         exchange['reserved_cus'] = wrapped.reserved_cus
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args, data_config, nn_cfg) if args.model == 'lstm' else None
 
     if rank == 0:
@@ -679,7 +734,7 @@ def main():
             'metric': 'garments/sec (fwd+bwd) at N=%d pts, batch %d per GPU' % (args.points, args.batch),
             'value': garments / elapsed, 'unit': 'garments/s', 'n_gpus': world, 'steps': args.steps,
             'warmup': args.warmup, 'ms_per_step': elapsed / args.steps * 1e3, 'higher_is_better': True,
-            'scaling': 'weak', 'vs_baseline': None,
+            'scaling': 'weak', 'vs_baseline': None, 'full': args.full,
             # the arithmetic type of the timed region (not a storage claim): 'f16x3' = fp16 MFMA on two-term splits, fp32 accumulate
             'dtype': {'f32': 'f32', 'f16x3': 'f16x3 (fp16 MFMA x3 per product, fp32 accumulate)', 'bf16x6': 'bf16x6',
                       'mixed': 'bf16x3/f32', 'bf16x3': 'bf16x3'}[args.math],

@@ -209,9 +209,27 @@ def run_stitch_known_answer():
                                                          loss.item(), os.path.getsize(out) / 1024))
 
 
+def write_shipped_configs(yaml_rels):
+    """tests/golden/shipped_yaml_configs.json: the `NN` and `dataset` sections of the shipped YAMLs, verbatim (data only), for
+    tests/test_host_logic.py::test_configs_equal_shipped_yamls."""
+    import json
+    doc = {}
+    for rel in yaml_rels:
+        with open(os.path.join(REF, rel)) as f:
+            y = yaml.safe_load(f)
+        doc[rel] = {'NN': y['NN'], 'dataset': y['dataset']}
+    out = os.path.join(REPO, 'tests', 'golden', 'shipped_yaml_configs.json')
+    with open(out, 'w') as f:
+        json.dump(doc, f, indent=1, sort_keys=True)
+        f.write('\n')
+    print('%-28s %d YAML(s)' % ('shipped_yaml_configs', len(doc)))
+
+
 if __name__ == '__main__':
     os.makedirs(os.path.join(REPO, 'tests', 'golden'), exist_ok=True)
     lstm_yaml, att_yaml = 'models/baseline/lstm_stitch_tags.yaml', 'models/att/att.yaml'
+    if not ONLY or 'shipped_yaml_configs' in ONLY:
+        write_shipped_configs([lstm_yaml, att_yaml])
     run_case('GarmentFullPattern3D', lstm_yaml, SMALL_NN, 2, 64, 100, 'full3d_small', True)
     run_case('GarmentSegmentPattern3D', att_yaml, SMALL_NN, 2, 64, 200, 'segment3d_small', True)
     # shipped hyper-parameters; weights are re-derivable from the seed, so only results are stored

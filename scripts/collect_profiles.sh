@@ -2,7 +2,7 @@
 # Round-end measurement artefacts (run on the GPU box through gpurun):  scripts/collect_profiles.sh <tag>
 #   1. rocprofv3 --kernel-trace --stats of the bench workload    -> <tag>_kernel_trace.md
 #   2. two PMC passes (FETCH_SIZE, WRITE_SIZE; own runs)         -> <tag>_hbm_traffic.json (records the csrc hash)
-#   3. the default bench line (with cpu_baseline), run LAST so that it quotes the traffic file just made (bench.py only
+#   3. the --full bench line (with cpu_baseline), run LAST so that it quotes the traffic file just made (bench.py only
 #      accepts a traffic file whose csrc hash equals the tree's)  -> <tag>_bench.json
 # Everything lands in gpurun_out/ (merged back); copy the three files into profiles/ and commit them.
 TAG=${1:-r01_x}
@@ -27,7 +27,7 @@ cd $ROOT
 if [ -z "$SKIP_BENCH" ]; then
   cp $OUT/${TAG}_hbm_traffic.json $ROOT/profiles/${TAG}_hbm_traffic.json      # on the box: what bench.py will quote
   cp $OUT/${TAG}_kernel_avg.json $ROOT/profiles/${TAG}_kernel_avg.json
-  timeout 900 python bench.py --call-shapes $OUT/${TAG}_call_shapes.txt > $OUT/${TAG}_bench.log 2>&1
+  timeout 900 python bench.py --full --call-shapes $OUT/${TAG}_call_shapes.txt > $OUT/${TAG}_bench.log 2>&1
   grep '^{' $OUT/${TAG}_bench.log | tail -1 > $OUT/${TAG}_bench.json
 fi
 head -c 600 $OUT/${TAG}_bench.json; echo; head -12 $OUT/${TAG}_kernel_trace.md; head -c 400 $OUT/${TAG}_hbm_traffic.json

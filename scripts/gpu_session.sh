@@ -61,7 +61,7 @@ while [ $# -gt 0 ]; do
       ARGS=""; while [ $# -gt 0 ] && [ "$1" != "--" ]; do ARGS="$ARGS $1"; shift; done
       : > $OUT/${TAG}_ab_$VAR.txt
       for rep in $(seq ${REPS:-2}); do for V in $VALS; do
-        env GPE_DEBUG=1 $VAR=$V timeout 300 python bench.py --steps 60 --warmup 5 --no-cpu-baseline --no-fast-math-line $ARGS > $OUT/${TAG}_ab.log 2>&1
+        env GPE_DEBUG=1 $VAR=$V timeout 300 python bench.py --full --steps 60 --warmup 5 --no-cpu-baseline --no-fast-math-line $ARGS > $OUT/${TAG}_ab.log 2>&1
         grep '^{' $OUT/${TAG}_ab.log | tail -1 > $OUT/${TAG}_ab.json
         if [ ! -s $OUT/${TAG}_ab.json ]; then echo "$VAR=$V FAILED"; tail -5 $OUT/${TAG}_ab.log; fi
         line $OUT/${TAG}_ab.json "$VAR=$V" | tee -a $OUT/${TAG}_ab_$VAR.txt
@@ -79,7 +79,7 @@ while [ $# -gt 0 ]; do
       cat $OUT/${TAG}_sq_wave_states.md ;;
     configs)
       TAG=$1; shift
-      run() { N=$1; shift; timeout 400 python bench.py --no-cpu-baseline "$@" > $OUT/${TAG}_$N.log 2>&1
+      run() { N=$1; shift; timeout 400 python bench.py --full --no-cpu-baseline "$@" > $OUT/${TAG}_$N.log 2>&1
               grep '^{' $OUT/${TAG}_$N.log | tail -1 > $OUT/${TAG}_${N}_bench.json; line $OUT/${TAG}_${N}_bench.json $N; }
       run cfg1 --points 1024 --batch 8 --k 5 --steps 100 --graph          # host-bound shape: the step replayed from one hipGraph
       run cfg1_eager --points 1024 --batch 8 --k 5 --steps 100
@@ -101,7 +101,7 @@ print('| %d | %.1f | %.2f | %.3f |' % (b, d['value'], d['ms_per_step'], d['ms_pe
     bench)
       TAG=$1; shift
       ARGS=""; while [ $# -gt 0 ] && [ "$1" != "--" ]; do ARGS="$ARGS $1"; shift; done
-      timeout 600 python bench.py $ARGS > $OUT/${TAG}_bench.log 2>&1
+      timeout 600 python bench.py --full $ARGS > $OUT/${TAG}_bench.log 2>&1
       grep '^{' $OUT/${TAG}_bench.log | tail -1 > $OUT/${TAG}_bench.json; line $OUT/${TAG}_bench.json $TAG ;;
     --) ;;
     *) echo "unknown step $STEP"; exit 2 ;;

@@ -19,10 +19,10 @@ cd "$ROOT"
 export HSA_ENABLE_IPC_MODE_LEGACY=0
 for N in 1 2 4 8; do
   if [ "$N" = 1 ]; then
-    python bench.py --gpus 1 --batch "$BATCH" --steps "$STEPS" --warmup "$WARMUP" --no-cpu-baseline --no-fast-math-line > "$OUT/scale_N1.log" 2>&1
+    python bench.py --full --gpus 1 --batch "$BATCH" --steps "$STEPS" --warmup "$WARMUP" --no-cpu-baseline --no-fast-math-line > "$OUT/scale_N1.log" 2>&1
   else
     python -m torch.distributed.run --nnodes=1 --nproc-per-node "$N" --master-addr 127.0.0.1 --master-port $((29500 + N)) \
-        bench.py --gpus "$N" --batch "$BATCH" --steps "$STEPS" --warmup "$WARMUP" > "$OUT/scale_N$N.log" 2>&1
+        bench.py --full --gpus "$N" --batch "$BATCH" --steps "$STEPS" --warmup "$WARMUP" > "$OUT/scale_N$N.log" 2>&1
   fi
   grep '^{' "$OUT/scale_N$N.log" | tail -1 > "$OUT/scale_N$N.json"
 done

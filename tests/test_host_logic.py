@@ -1,6 +1,7 @@
 """not-gpu: the drop-in surface — constructors, config merging, state-dict layout, error types — mirrors the reference
 (SURVEY.md §8b), checked without touching the GPU."""
 import copy
+import json
 import os
 
 import pytest
@@ -181,12 +182,13 @@ def test_train_eval_forward_to_loss():
     assert model.loss.training is True
 
 
-@pytest.mark.skipif(not os.path.exists('/root/reference/models'), reason='reference tree only exists in the build box')
-def test_configs_equal_shipped_yamls():
-    import yaml
+def test_configs_equal_shipped_yamls(golden_dir):
+    # the `NN` and `dataset` sections of the reference's shipped YAMLs, stored verbatim by oracle/refgen/make_golden.py
+    with open(os.path.join(golden_dir, 'shipped_yaml_configs.json')) as f:
+        shipped = json.load(f)
     for rel, fn in [('models/baseline/lstm_stitch_tags.yaml', configs.lstm_model_config),
                     ('models/att/att.yaml', configs.att_model_config)]:
-        y = yaml.safe_load(open('/root/reference/' + rel))
+        y = shipped[rel]
         ref_nn = y['NN']
         ref_nn.pop('pre-trained')
         assert fn() == ref_nn
@@ -209,6 +211,35 @@ def test_bench_workload_names():
     assert bench._workload_name(mk('lstm', 8192, 64, 16)).startswith('BASELINE cfg 5')
     assert bench._workload_name(mk('lstm', 1000, 3, 10)).startswith('custom shape')
     assert 'N=1000, batch 3/GPU, k=10' in bench._workload_name(mk('lstm', 1000, 3, 10))
+
+
+def test_bench_plain_run_and_output_dump(tmp_path, monkeypatch):
+    """A plain bench.py run measures only the timed steps (--full is off by default); --dump-outputs writes fp32 / fp64 .npy files
+    within the 64 MB budget, a larger array as a fixed, seeded sample of its elements."""
+    import importlib.util
+    import sys
+    import numpy as np
+    spec = importlib.util.spec_from_file_location('bench_mod_dump', os.path.join(os.path.dirname(os.path.dirname(__file__)), 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '1', '--steps', '7', '--warmup', '2'])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--full', '--dump-outputs', str(tmp_path)])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == str(tmp_path)
+    small = {'loss': torch.tensor(1.5), 'pred_x': torch.arange(12, dtype=torch.float16).view(3, 4), 'w': torch.ones(5, dtype=torch.float64)}
+    bench.dump_outputs(str(tmp_path / 'a'), small)
+    got = {n: np.load(str(tmp_path / 'a' / (n + '.npy'))) for n in small}
+    assert got['loss'].dtype == np.float32 and got['loss'].shape == () and got['loss'] == 1.5
+    assert got['pred_x'].dtype == np.float32 and got['pred_x'].shape == (3, 4) and (got['pred_x'].ravel() == np.arange(12)).all()
+    assert got['w'].dtype == np.float64
+    big = {'params': torch.arange(4000, dtype=torch.float32), 'loss': torch.tensor(2.0)}
+    for d in ('b1', 'b2'):
+        bench.dump_outputs(str(tmp_path / d), big, budget=8000)
+    p1, p2 = (np.load(str(tmp_path / d / 'params.npy')) for d in ('b1', 'b2'))
+    assert p1.shape == (1000,) and (p1 == p2).all() and (np.diff(p1) > 0).all() and p1.max() < 4000
+    assert sum(os.path.getsize(str(tmp_path / 'b1' / f)) for f in os.listdir(str(tmp_path / 'b1'))) < 8000 + 2 * 256
 
 
 def test_bench_quotes_counter_traffic_only_for_what_it_measured(monkeypatch):
