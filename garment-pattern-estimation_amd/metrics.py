@@ -17,8 +17,15 @@ There is no CPU or torch-math path in `ComposedPatternLoss`: predictions must be
 this package produce); anything else raises, like the model path itself.
 
 The segmentation term (entmax.SparsemaxLoss on the attention weights, composed_loss.py:323-332) runs through
-ops.SparsemaxLossFn (entmax is third-party and un-vendored: its published loss restated).  Quality components are
-evaluation-side bookkeeping: `with_quality_eval` is accepted and ignored, no quality keys are added to the loss dict."""
+ops.SparsemaxLossFn (entmax is third-party and un-vendored: its published loss restated).
+
+Quality components (composed_loss.py:268-277,365-424; `quality_components` of the config) run through ops.quality_metrics: the
+reference's keys, evaluated on the matched ground truth, in at most three launches.  They are evaluated when
+`with_quality_eval` is set, `quality_components` is non-empty and autograd is not recording (the reference's evaluation entry
+points — metrics.eval_utils.eval_metrics, the trainer's validation loop — run under torch.no_grad()), or in grad-enabled calls
+too when `quality_in_training` is set (the reference's per-step logging; it costs one host read per call).  A training step
+with the defaults therefore makes exactly the launches it made before, with no host read.  Under DistributedHotPath each rank
+reports the metrics of its own shard.  DESIGN.md section 5.22."""
 import torch
 import torch.nn as nn
 
@@ -114,6 +121,7 @@ class ComposedPatternLoss:
             'order_by': 'placement', 'epoch_with_order_matching': 0}
         self.config.update(in_config)
         self.with_quality_eval = True
+        self.quality_in_training = False      # evaluate quality metrics in grad-enabled calls too (one host read per call)
         self.training = False
         self.debug_prints = False
         self.l_components = self.config['loss_components']
@@ -124,6 +132,8 @@ class ComposedPatternLoss:
         self.gt_outline_stats = {'shift': data_stats['gt_shift']['outlines'],
                                  'scale': data_stats['gt_scale']['outlines']}
         self.cluster_resolution_mapping = {}
+        self._quality_stats_host = None
+        self._quality_data_stats = (data_stats, bool(data_config.get('explicit_stitch_tags', False)))
         if any(c in self.l_components for c in ('shape', 'rotation', 'translation')):
             self.regression_loss = nn.MSELoss()
         if 'loop' in self.l_components:
@@ -277,11 +287,111 @@ class ComposedPatternLoss:
             extra, extra_dict = self._stitch_losses(preds, gt)
             full_loss = full_loss + extra
             loss_dict.update(extra_dict)
+        if self._quality_active():                                             # composed_loss.py:268-277
+            with torch.no_grad():
+                quality, correct = self._main_quality_metrics(preds, gt, gt_num_edges, names)
+                loss_dict.update(quality)
+                if epoch >= self.config['epoch_with_stitches']:
+                    loss_dict.update(self._stitch_quality_metrics(preds, gt, gt_num_edges, names, correct))
         loss_update_ind = (
             epoch == self.config['epoch_with_stitches'] and any(
                 el in self.l_components for el in ['stitch', 'stitch_supervised', 'free_class'])
             or epoch == self.config['epoch_with_order_matching'] and self.config['panel_order_inariant_loss'])
         return full_loss, loss_dict, loss_update_ind
+
+    # ---- quality metrics (composed_loss.py:365-424) -----------------------------------------------------------
+    def _quality_active(self):
+        """Quality metrics are evaluated when requested and autograd is not recording (or `quality_in_training` is set).
+        Inside a stream capture they raise: their corr_ values need one host read, which a captured graph cannot make."""
+        if not (self.with_quality_eval and self.q_components):
+            return False
+        if torch.is_grad_enabled() and not self.quality_in_training:
+            return False
+        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('ComposedPatternLoss: quality metrics read their contributor counts on the host, which a '
+                               'stream capture cannot do; set with_quality_eval = False for captured steps')
+        return True
+
+    def _quality_stats(self):
+        if self._quality_stats_host is None:
+            from . import ops
+            ds, explicit = self._quality_data_stats
+            pick = lambda k: {'shift': ds['gt_shift'][k], 'scale': ds['gt_scale'][k]}      # noqa: E731
+            self._quality_stats_host = ops.quality_stats(
+                self.gt_outline_stats,
+                pick('rotations') if 'rotation' in self.q_components else None,
+                pick('translations') if 'translation' in self.q_components else None,
+                pick('stitch_tags') if 'stitch' in self.q_components and explicit else None)
+        return self._quality_stats_host
+
+    def _quality_flags(self, stitch_stage):
+        from . import ops
+        q = self.q_components
+        flags = (ops.QM_DISCRETE if 'discrete' in q else 0) | (ops.QM_SHAPE if 'shape' in q else 0) | \
+                (ops.QM_ROT if 'rotation' in q else 0) | (ops.QM_TR if 'translation' in q else 0)
+        if stitch_stage:
+            flags |= (ops.QM_STITCH if 'stitch' in q else 0) | (ops.QM_FREE if 'free_class' in q else 0)
+            if 'stitch' in q and self._quality_data_stats[1]:
+                flags |= ops.QM_TAG_STATS
+        return flags
+
+    def _quality_vector(self, preds, gt, gt_num_edges):
+        """ONE evaluation of every requested component (the main ones and, from epoch_with_stitches on, the stitch ones):
+        -> (result vector fp32 [14] on the device, contributor counts on the host or None).  Cached per call of the loss."""
+        from . import ops
+        flags = self._quality_flags(self.epoch >= self.config['epoch_with_stitches'])
+        B, P, Lp = preds['outlines'].shape[:3] if 'outlines' in preds else preds['free_edges_mask'].shape[:3]
+        q = self.q_components
+        stitch = bool(flags & ops.QM_STITCH)
+        out, counts = ops.quality_metrics(
+            flags, self._quality_stats(), B, P, Lp,
+            outlines=preds['outlines'] if flags & (ops.QM_DISCRETE | ops.QM_SHAPE) else None,
+            gt_outlines=gt['outlines'] if flags & ops.QM_SHAPE else None,
+            num_edges=gt_num_edges if flags & (ops.QM_DISCRETE | ops.QM_SHAPE) else None,
+            num_panels=gt['num_panels'] if 'discrete' in q else None,        # KeyError like the reference when missing
+            rotations=preds['rotations'] if flags & ops.QM_ROT else None,
+            gt_rotations=gt['rotations'] if flags & ops.QM_ROT else None,
+            translations=preds['translations'] if flags & ops.QM_TR else None,
+            gt_translations=gt['translations'] if flags & ops.QM_TR else None,
+            stitch_tags=preds['stitch_tags'] if stitch else None,
+            free_logits=preds['free_edges_mask'] if flags & (ops.QM_STITCH | ops.QM_FREE) else None,
+            stitches=gt['stitches'] if stitch else None, nums=gt['num_stitches'] if stitch else None,
+            gt_free_mask=gt['free_edges_mask'] if flags & ops.QM_FREE else None)
+        # the corr_ values exist only with the `discrete` component (the reference's correct-pattern mask); then their
+        # contributor counts decide None — the one host read of the evaluation path
+        host = counts.tolist() if flags & ops.QM_DISCRETE else None
+        self._quality_last = (out, host)
+        self.last_quality_vector = out            # diagnostics / tests: the raw result vector
+        return out, host
+
+    def _main_quality_metrics(self, preds, ground_truth, gt_num_edges, names):
+        """composed_loss.py:365-396.  Values are 0-d fp32 device tensors (views of one result vector), None where the
+        reference gives None; `names` is accepted, the reference's per-pattern diagnostic prints are not reproduced.
+        -> (dict, correct-pattern indicator: the host contributor counts, or None without `discrete`)."""
+        out, host = self._quality_vector(preds, ground_truth, gt_num_edges)
+        q, d = self.q_components, {}
+        corr = host is not None
+        if 'discrete' in q:
+            d.update(num_panels_accuracy=out[0], num_edges_accuracy=out[1], corr_num_edges_accuracy=out[2])
+        if 'shape' in q:
+            d.update(panel_shape_l2=out[3], corr_panel_shape_l2=out[4] if corr and host[1] else None)
+        if 'rotation' in q:
+            d.update(rotation_l2=out[5], corr_rotation_l2=out[6] if corr and host[0] else None)
+        if 'translation' in q:
+            d.update(translation_l2=out[7], corr_translation_l2=out[8] if corr and host[0] else None)
+        return d, host
+
+    def _stitch_quality_metrics(self, preds, ground_truth, gt_num_edges, names, correct_mask):
+        """composed_loss.py:398-424 (evaluated in the same launches as the main metrics; this reads its slots)."""
+        out, host = self._quality_last
+        q, d = self.q_components, {}
+        if 'stitch' in q:
+            has = host is not None and host[2] > 0
+            d.update(stitch_precision=out[9], stitch_recall=out[10],
+                     corr_stitch_precision=out[11] if has else None, corr_stitch_recall=out[12] if has else None)
+        if 'free_class' in q:
+            d.update(free_edge_acc=out[13])
+        return d
 
     def _stitch_losses(self, preds, gt):
         """composed_loss.py:336-362 through ops.StitchLossFn."""

@@ -1757,6 +1757,86 @@ def order_match(pred_feat, gt_feat):
     return perm, fail
 
 
+QM_DISCRETE, QM_SHAPE, QM_ROT, QM_TR, QM_STITCH, QM_FREE, QM_TAG_STATS = 1, 2, 4, 8, 16, 32, 64
+QUALITY_KEYS = ('num_panels_accuracy', 'num_edges_accuracy', 'corr_num_edges_accuracy', 'panel_shape_l2',
+                'corr_panel_shape_l2', 'rotation_l2', 'corr_rotation_l2', 'translation_l2', 'corr_translation_l2',
+                'stitch_precision', 'stitch_recall', 'corr_stitch_precision', 'corr_stitch_recall', 'free_edge_acc')
+QUALITY_WS_DOUBLES = 16          # include/gpe_hip.h: `part` holds B * 16 doubles
+
+
+def quality_stats(ol_stats, rot_stats=None, tr_stats=None, tag_stats=None):
+    """The 72-float host array `stats_host` of the quality entry points (include/gpe_hip.h), from the {'shift', 'scale'} stats
+    of the outlines / rotations / translations / stitch tags.  The pad vector, its isclose tolerance and the loop-closure
+    threshold are formed with torch fp32 arithmetic, as nn/metrics/metrics.py:107-109 and torch.isclose form them."""
+    import ctypes
+    v = [0.0] * 72
+    sh = torch.tensor(ol_stats['shift'], dtype=F32)
+    sc = torch.tensor(ol_stats['scale'], dtype=F32)
+    pad = -sh / sc
+    tol = 0.07 + (1e-5 * pad).abs()                 # torch.isclose(atol=0.07, rtol=1e-5) against the pad vector
+    thr = torch.tensor([3, 3]) / sc[:2]             # 3 cm per coordinate
+    v[0:4], v[4:8], v[8:12], v[12:16], v[16:18] = sh.tolist(), sc.tolist(), pad.tolist(), tol.tolist(), thr.tolist()
+    for base, st in ((24, rot_stats), (40, tr_stats), (56, tag_stats)):
+        if st is not None:
+            s_, c_ = [float(x) for x in st['shift']], [float(x) for x in st['scale']]
+            if len(s_) > 8:
+                raise ValueError('quality metrics support feature widths <= 8 (got %d)' % len(s_))
+            v[base:base + len(s_)], v[base + 8:base + 8 + len(c_)] = s_, c_
+    return (ctypes.c_float * 72)(*v)
+
+
+def quality_metrics(flags, stats, B, P, Lp, outlines=None, gt_outlines=None, num_edges=None, num_panels=None, rotations=None,
+                    gt_rotations=None, translations=None, gt_translations=None, stitch_tags=None, free_logits=None,
+                    stitches=None, nums=None, gt_free_mask=None):
+    """ComposedPatternLoss quality metrics (nn/metrics/composed_loss.py:365-424) in <= 3 launches, no host read:
+    -> (out fp32 [14] in the order of QUALITY_KEYS, counts int32 [4]: contributors of the corr_ slots, include/gpe_hip.h).
+    `flags` selects the components (QM_*), `stats` is quality_stats(...).  Predictions are the strided views of the decoders'
+    outputs; ground truth is what the loss matched (order / origin), any dtype (converted on the device)."""
+    ref = outlines if outlines is not None else free_logits
+    _dev_check(ref)
+    dev = ref.device
+    part = torch.empty(B * QUALITY_WS_DOUBLES, device=dev, dtype=torch.float64)
+    out = torch.empty(len(QUALITY_KEYS), device=dev, dtype=F32)
+    counts = torch.empty(4, device=dev, dtype=torch.int32)
+    main = flags & (QM_DISCRETE | QM_SHAPE | QM_ROT | QM_TR)
+    if main:
+        need_ol = flags & (QM_DISCRETE | QM_SHAPE)
+        ol = outlines.detach() if need_ol else None
+        sb, sp, sl = _view_strides(ol) if need_ol else (0, 0, 0)
+        gto = gt_outlines.float().contiguous() if flags & QM_SHAPE else None
+        ne = num_edges.reshape(-1).to(torch.int32).contiguous() if need_ol else None
+        npn = num_panels.reshape(-1).to(torch.int32).contiguous() if flags & QM_DISCRETE else None
+        rot = rotations.detach() if flags & QM_ROT else None
+        tr = translations.detach() if flags & QM_TR else None
+        R = rot.shape[-1] if rot is not None else 0
+        T = tr.shape[-1] if tr is not None else 0
+        for t in (ol, rot, tr):
+            if t is not None:
+                _dev_check(t)
+        L.call('gpe_quality_panels', ol, sb, sp, sl, gto, ne, npn,
+               rot, _row_stride(rot, P) if rot is not None else 0,
+               gt_rotations.float().contiguous() if rot is not None else None, R,
+               tr, _row_stride(tr, P) if tr is not None else 0,
+               gt_translations.float().contiguous() if tr is not None else None, T,
+               B, P, Lp, main, stats, part)
+    st_flags = flags & (QM_STITCH | QM_FREE | QM_TAG_STATS)
+    if st_flags & (QM_STITCH | QM_FREE):
+        lg = free_logits.detach()
+        _dev_check(lg)
+        tags = stitch_tags.detach() if flags & QM_STITCH else None
+        if tags is not None:
+            _dev_check(tags)
+        ts = _view_strides(tags) if tags is not None else (0, 0, 0)
+        L.call('gpe_quality_stitches', tags, ts[0], ts[1], ts[2], tags.shape[3] if tags is not None else 0,
+               lg, lg.stride(0), lg.stride(1), lg.stride(2),
+               stitches.long().contiguous() if tags is not None else None,
+               nums.reshape(-1).long().contiguous() if tags is not None else None,
+               stitches.shape[-1] if tags is not None else 0,
+               gt_free_mask.float().contiguous() if flags & QM_FREE else None, B, P, Lp, st_flags, stats, part)
+    L.call('gpe_quality_finalize', part, B, P, Lp, flags, out, counts)
+    return out, counts
+
+
 def standardize(x, shift, scale):
     """nn/data/transforms.py:35-50 FeatureStandartization on the device: (x - shift) / scale per column."""
     import ctypes

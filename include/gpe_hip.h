@@ -509,6 +509,37 @@ int gpe_stitch_renumber(const int64_t* stitches, const int64_t* nums, int B, int
 int gpe_panel_shift(const float* feat, int D, const int32_t* lead, const int32_t* num_edges, long npanels, int L, float* out,
                     void* stream);
 
+/* ---- quality metrics of ComposedPatternLoss (nn/metrics/composed_loss.py:365-424; nn/metrics/metrics.py:13-325;
+ * nn/data/datasets.py:917-968) --------------------------------------------------------------------------------------------
+ * Added without a version bump (gpe_abi_version() stays 7): three compute entry points, nothing else changes.
+ * flags: 1 discrete (panel / edge counts) | 2 shape (vertex L2) | 4 rotation L2 | 8 translation L2 | 16 stitch precision /
+ * recall | 32 free-edge accuracy | 64 un-standardise the stitch tags (data_config['explicit_stitch_tags']).
+ * stats_host: HOST array of 72 floats — [0:4] outline shift, [4:8] outline scale, [8:12] pad vector (standardised), [12:16]
+ * isclose tolerance per feature (atol + |rtol * pad|), [16:18] loop-closure threshold (3 cm / scale), [24:32] rotation shift,
+ * [32:40] rotation scale, [40:48] translation shift, [48:56] translation scale, [56:64] stitch-tag shift, [64:72] its scale.
+ * part: caller-owned fp64 workspace of B * 16 doubles (B * 128 bytes), written by gpe_quality_panels (flags 1-8) and
+ * gpe_quality_stitches (flags 16, 32) and read by gpe_quality_finalize, all with the same flags.  Limits: P, L <= 64,
+ * R, T, D <= 8, P * L <= 1024.  The finalize kernel sums the per-pattern partials in pattern order (bit-reproducible).
+ * panels: predicted outlines (b,p,l,c<4) at ol + b*ol_sb + p*ol_sp + l*ol_sl + c; gt_ol fp32 [B,P,L,4] dense; num_edges
+ *         int32 [B*P] and num_panels int32 [B] of the ground truth; predicted rotation row (b,p) at rot + (b*P + p)*rot_s,
+ *         gt_rot fp32 [B,P,R] dense; translations alike.
+ * stitches: tags / logits as gpe_stitch_loss_fwd; stitches int64 [B][2][S] / nums int64 [B] the ground truth; gt_mask fp32
+ *         [B,P,L] (1 = free).  Greedy pairing of the non-free edges' tags by global minimum distance, ties to the smallest
+ *         (row, column) of the upper-triangular distance matrix.
+ * finalize: out fp32 [14] = {num_panels_accuracy, num_edges_accuracy, corr_num_edges_accuracy, panel_shape_l2,
+ *         corr_panel_shape_l2, rotation_l2, corr_rotation_l2, translation_l2, corr_translation_l2, stitch_precision,
+ *         stitch_recall, corr_stitch_precision, corr_stitch_recall, free_edge_acc}; counts int32 [4] = {patterns with the
+ *         right panel count, shape panels of those, those with detected stitches, all shape panels}: the contributors of
+ *         the corr_ slots (0 = the reference's None). */
+int gpe_quality_panels(const float* ol, long ol_sb, long ol_sp, long ol_sl, const float* gt_ol, const int32_t* num_edges,
+                       const int32_t* num_panels, const float* rot, long rot_s, const float* gt_rot, int R, const float* tr,
+                       long tr_s, const float* gt_tr, int T, int B, int P, int L, int flags, const float* stats_host,
+                       double* part, void* stream);
+int gpe_quality_stitches(const float* tags, long t_sb, long t_sp, long t_sl, int D, const float* logit, long m_sb, long m_sp,
+                         long m_sl, const int64_t* stitches, const int64_t* nums, int S, const float* gt_mask, int B, int P,
+                         int L, int flags, const float* stats_host, double* part, void* stream);
+int gpe_quality_finalize(const double* part, int B, int P, int L, int flags, float* out, int32_t* counts, void* stream);
+
 
 /* ---- optimizer / input side (nn/trainer.py:162-185; nn/data/transforms.py:35-50) ----------------------------------- */
 /* one torch.optim.Adam step (amsgrad off) over a flat arena of n floats (16-B aligned p, g, m, v); `step` counts from 1;
