@@ -100,6 +100,13 @@ def set_reserved_cus(n):
     return prev
 
 
+def get_reserved_cus():
+    """The compute units the persistent launches currently leave out (set_reserved_cus)."""
+    n = lib().gpe_reserve_cus_set(0)
+    lib().gpe_reserve_cus_set(n)
+    return n
+
+
 def get_math():
     return {v: k for k, v in MATH_MODES.items()}[lib().gpe_math_get()]
 

@@ -1284,11 +1284,16 @@ __global__ __launch_bounds__(256) void gpe_redgemm_thin_kernel(RdParams p)
     }
 }
 
-// row split of the deep kernel: ~3 workgroups per CU, at least 4 row tiles each, <= RDD_MAX_GX partial images
+// row split of the deep kernel: ~3 workgroups per CU, but enough of them for at most RDD_MAX_TPW row tiles each as far as the
+// RDD_MAX_GX partial images allow (every workgroup sums its tiles in one fp32 accumulator chain, whose rounding grows with its length:
+// sized by the CU count alone, 64 usable CUs put 8 k rows into one chain just below the deep-kernel switch, 3.1e-6 of max|G| against
+// fp64), and at least 4 row tiles each
+#define RDD_MAX_TPW 64                // = the big-block kernel's tiles per workgroup at the switch (num_tiles < 64 gx)
 static int rdd_gx(int Mg, int Ng, long num_tiles, int cus)
 {
     const long blocks = (long)gpe_cdiv(Mg, RDD_B) * gpe_cdiv(Ng, RDD_B);
     long gx = gpe_cdiv(3L * cus, blocks);
+    if (num_tiles >= 0 && gx < gpe_cdiv(num_tiles, (long)RDD_MAX_TPW)) gx = gpe_cdiv(num_tiles, (long)RDD_MAX_TPW);
     if (gx > RDD_MAX_GX) gx = RDD_MAX_GX;
     if (num_tiles >= 0 && gx > num_tiles / 4) gx = num_tiles / 4;
     return gx < 1 ? 1 : (int)gx;

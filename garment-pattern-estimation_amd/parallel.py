@@ -28,7 +28,8 @@ class DistributedHotPath(nn.Module):
     def __init__(self, module, device_ids=None, bucket_bytes=8 << 20, process_group=None, arena=None, reserve_cus=None):
         """reserve_cus: compute units left out of every persistent launch of this process while the model trains (room for the
         collective's kernels under the fused edge kernels: include/gpe_hip.h gpe_reserve_cus_set).  None = 16 when the world has
-        more than one rank (two CUs per XCD: measured cost at N = 1, cfg 2: profiles/r06_z_reserved_cus.md), else 0."""
+        more than one rank (two CUs per XCD: measured cost at N = 1, cfg 2: profiles/r06_z_reserved_cus.md); with one rank None
+        leaves the process's reservation (set_reserved_cus) as it is and reports it in `reserved_cus`."""
         super().__init__()
         self.module = module
         self.device_ids = list(device_ids) if device_ids is not None else []
@@ -57,12 +58,14 @@ class DistributedHotPath(nn.Module):
                 p.register_post_accumulate_grad_hook(lambda _p, i=i: self._on_hook(_p, i))
         self._exposed = []
         self._reset()
-        if reserve_cus is None:
-            reserve_cus = 16 if self.world > 1 else 0
-        self.reserved_cus = int(reserve_cus)
-        if torch.cuda.is_available():
-            from . import _lib
-            _lib.set_reserved_cus(self.reserved_cus)
+        from . import _lib
+        if reserve_cus is None and self.world == 1:
+            # no collective to make room for: a reservation the caller set stays in force
+            self.reserved_cus = _lib.get_reserved_cus() if torch.cuda.is_available() else 0
+        else:
+            self.reserved_cus = int(16 if reserve_cus is None else reserve_cus)
+            if torch.cuda.is_available():
+                _lib.set_reserved_cus(self.reserved_cus)
 
     def forward(self, *args, **kwargs):
         return self.module(*args, **kwargs)

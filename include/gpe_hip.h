@@ -45,7 +45,9 @@ int gpe_debug_get(void);
  * per CU" and hold 100 - 160 KB of LDS each for the whole launch: with nothing reserved, a collective's kernel queued on another
  * stream (RCCL's all-reduce of a gradient bucket, launched from inside backward: garment-pattern-estimation_amd/parallel.py) only
  * gets onto the chip when one of them retires — the "overlap" degenerates into waiting at kernel boundaries.  Process-global like the
- * arithmetic mode; returns the previous reservation, -22 for a bad n. */
+ * arithmetic mode; returns the previous reservation, -22 for a bad n.  Results are not bit-identical across reservations (the
+ * order of the partial sums and the choice of kernel change with the grid), but parity with the oracle holds at every reservation
+ * (tests/test_gpu_grid_sizes.py). */
 int gpe_reserve_cus_set(int n);
 /* arithmetic of the fused per-edge GEMMs (gpe_edge_mlp_fwd / gpe_edge_mlp_bwd / gpe_edge_redgemm):
  *   0 = "f32"    exact fp32 matrix instruction (v_mfma_f32_16x16x4_f32)

@@ -734,8 +734,13 @@ def test_persistent_lstm_stack_matches_the_diagonal_launches(gpe, Bn, In, Hh, T,
             gpe.set_math(prev)
 
 
+# (reserve: usable CUs 256 - reserve on an MI355X; the 736-row panel stack at R = 192 — one row group of 46 row tiles, more than a
+# workgroup's 16 — is not eligible and takes the diagonal launches, so the 64-CU cases are a one-layer panel stack (4 row groups)
+# and the sequence-input stack)
 @pytest.mark.parametrize('Bn,In,Hh,T,L,seq,reserve', [(736, 250, 250, 14, 3, False, 0), (730, 250, 250, 6, 3, False, 16), (900, 40, 96, 5, 2, True, 0),
-                                                      (1500, 32, 64, 4, 1, False, 0), (2100, 64, 32, 7, 4, True, 0)])
+                                                      (1500, 32, 64, 4, 1, False, 0), (2100, 64, 32, 7, 4, True, 0),
+                                                      (736, 250, 250, 14, 3, False, 4), (736, 250, 250, 14, 3, False, 100),
+                                                      (736, 250, 250, 14, 1, False, 192), (900, 40, 96, 5, 2, True, 192)])
 def test_multi_tile_persistent_lstm_forward(gpe, Bn, In, Hh, T, L, seq, reserve):
     """csrc/gpe_rnn_persist_mt.hip (round 6): the forward of an LSTM stack whose 16-row tiles outnumber the chip (the 736-row panel
     decoder) as ONE persistent launch in f16x3 mode — waves own row tiles, state rows published already split into their fp16 terms,
