@@ -75,12 +75,19 @@ class EdgeConvFeatures(nn.Module):
             'EConv_feature': 112, 'EConv_aggr': 'max', 'global_pool': 'mean',
             'skip_connections': False, 'graph_pooling': False, 'pool_ratio': 0.1}
         self.config.update(config)
-        if self.config['graph_pooling']:
-            raise NotImplementedError('graph_pooling (DynamicASAPool) is outside the accelerated path; '
-                                      'no shipped config enables it')
         depth = self.config['conv_depth']
-        feat = [self.config['EConv_feature']] * depth
-        hid = [self.config['EConv_hidden']] * depth
+        pooling = self.config['graph_pooling']
+        if pooling and self.config['skip_connections']:
+            # the reference concatenates the pooled features with ALL input positions and fails inside torch.cat at the first forward
+            raise ValueError('skip_connections cannot be combined with graph_pooling: the pooled clouds keep %s of the points '
+                             'the skip connection would concatenate' % self.config['pool_ratio'])
+        if pooling:
+            # nn/net_blocks.py:113-118: widths grow towards the last layer when the clouds shrink
+            feat = [int(self.config['EConv_feature'] / d) for d in range(depth, 0, -1)]
+            hid = [int(self.config['EConv_hidden'] / d) for d in range(depth, 0, -1)]
+        else:
+            feat = [self.config['EConv_feature']] * depth
+            hid = [self.config['EConv_hidden']] * depth
         mlp_depth = self.config['EConv_hidden_depth']
         self.conv_layers = nn.ModuleList()
         self.conv_layers.append(DynamicEdgeConv(
@@ -90,6 +97,12 @@ class EdgeConvFeatures(nn.Module):
             self.conv_layers.append(DynamicEdgeConv(
                 MLP([2 * feat[c - 1]] + [hid[c]] * mlp_depth + [feat[c]]),
                 k=self.config['k_neighbors'], aggr=self.config['EConv_aggr']))
+        if pooling:
+            # nn/net_blocks.py:138-142: one pool after every conv, the last one included
+            self.gpool_layers = nn.ModuleList()
+            for c in range(depth):
+                self.gpool_layers.append(DynamicASAPool(feat[c], k=self.config['k_neighbors'],
+                                                        pool_ratio=self.config['pool_ratio']))
         if self.config['global_pool'] == 'max':
             self.global_pool = ops.segment_max
         elif self.config['global_pool'] == 'mean':
@@ -118,15 +131,133 @@ class EdgeConvFeatures(nn.Module):
         batch = torch.arange(B, device=positions.device).repeat_interleave(N) if want_batch else None
         out = pos_flat
         order = None                                         # layer l + 1 searches its graph in layer l's locality order
-        for conv in self.conv_layers:
-            out = conv(out, B, N, order=order)
-            order = conv.last_order
+        if self.config['graph_pooling']:
+            for conv, pool in zip(self.conv_layers, self.gpool_layers):
+                _check_cloud(conv.k, N)
+                out = conv(out, B, N, order=order)
+                # the pool's search may take the conv's order (same numbering); the next conv may not (a foreign numbering)
+                out, (_, N) = pool(out, (B, N), order=conv.last_order)
+                order = None
+            if want_batch:
+                batch = torch.arange(B, device=positions.device).repeat_interleave(N)
+        else:
+            for conv in self.conv_layers:
+                out = conv(out, B, N, order=order)
+                order = conv.last_order
         if self.config['skip_connections']:
             out = torch.cat([out, pos_flat], dim=-1)
         if global_pool:
             pooled = self.global_pool(out.contiguous() if out.stride(1) != 1 else out, B, N)
             return ops.linear(pooled, self.lin.weight, self.lin.bias), out, batch
         return None, out, batch
+
+
+def _check_cloud(k, N):
+    if N < k:
+        # torch_cluster would quietly hand out fewer neighbours; the fused kernels need k of them
+        raise ValueError('a pooled cloud of %d points is smaller than k_neighbors = %d: raise pool_ratio or lower k_neighbors'
+                         % (N, k))
+
+
+class _LEConvHolder(nn.Module):
+    """parameter container with PyG 2.x LEConv's names (gnn_score.lin1 / lin2 / lin3; lin2 has no bias)."""
+
+    def __init__(self, F):
+        super().__init__()
+        self.lin1 = nn.Linear(F, 1)
+        self.lin2 = nn.Linear(F, 1, bias=False)
+        self.lin3 = nn.Linear(F, 1)
+
+
+class _ASAPoolingHolder(nn.Module):
+    """parameter container with PyG 2.x ASAPooling's names (lin, att, gnn_score); the arithmetic is ops.AsapPoolFn."""
+
+    def __init__(self, F, ratio):
+        super().__init__()
+        self.in_channels = F
+        self.ratio = ratio
+        self.lin = nn.Linear(F, F)
+        self.att = nn.Linear(2 * F, 1)
+        self.gnn_score = _LEConvHolder(F)
+
+    def params(self):
+        g = self.gnn_score
+        return [self.lin.weight, self.lin.bias, self.att.weight, self.att.bias, g.lin1.weight, g.lin1.bias, g.lin2.weight,
+                g.lin3.weight, g.lin3.bias]
+
+
+class DynamicASAPool(nn.Module):
+    """nn/net_blocks.py:194-218: ASAPooling on the kNN graph of the node features, parameters under `edge_pool.*`.
+
+    Restated exactly (csrc/gpe_asap.hip, include/gpe_hip.h gpe_asap_fwd): the graph always uses k = 10 neighbours (the `k`
+    argument is ignored, as in the reference; min(10, N) for smaller clouds) and is not flipped, so a node pools from every node
+    that has it among its neighbours.  Fixed here where upstream leaves it open: equal fitness keeps the lower index; equal channel
+    maxima route the gradient to the lowest-numbered source.  The parameters are drawn with torch.nn.Linear's initialisation in
+    PyG 2.x's registration order (lin, att, gnn_score.lin1/2/3); same-seed equality with a model built by PyG itself is not
+    claimed (its draw order depends on the version).
+
+    forward(node_features [B*N, F], batch) -> (out [B*M, F], new_batch), M = ceil(fp32(pool_ratio) * N) per cloud.  batch is
+    either the reference's LongTensor (clouds of equal size; B is read from it on the host once — a synchronising read) or a pair
+    (B, N), in which case new_batch is the pair (B, M) and nothing is read back."""
+
+    def __init__(self, feature_size, k=10, pool_ratio=0.5):
+        super().__init__()
+        self.k = ops.ASAP_K
+        self.edge_pool = _ASAPoolingHolder(feature_size, pool_ratio)
+        self.keep_decisions = False      # True: `last` receives the graph, kept rows, winners and fitness of every forward (tests)
+        self.last = {}
+
+    def forward(self, node_features, batch, order=None):
+        if isinstance(batch, torch.Tensor):
+            B = int(batch[-1].item()) + 1 if batch.numel() else 0
+            N = node_features.shape[0] // max(B, 1)
+            if B * N != node_features.shape[0]:
+                raise ValueError('DynamicASAPool takes clouds of equal size (%d rows, %d clouds)' % (node_features.shape[0], B))
+        else:
+            B, N = batch
+        x = node_features if node_features.dtype == torch.float32 else node_features.float()
+        self.last = {}
+        out, M = ops.asap_pool(x, B, N, self.edge_pool.params(), self.edge_pool.ratio, order=order,
+                               trace=self.last if self.keep_decisions else None)
+        if isinstance(batch, torch.Tensor):
+            return out, torch.arange(B, device=batch.device).repeat_interleave(M)
+        return out, (B, M)
+
+
+class EdgeConvPoolingFeatures(nn.Module):
+    """nn/net_blocks.py:221-268: conv1 -> pool1 -> conv2 -> pool2 -> conv3 -> global max pool -> Linear; forward(positions
+    [B, N, 3]) -> [B, out_size].  Defaults n_features 32 / 128 / 256, k = 10; both pools keep half of the points."""
+
+    def __init__(self, out_size, config={}):
+        super().__init__()
+        self.config = {'conv_depth': 3}
+        self.config.update(n_features1=32, n_features2=128, n_features3=256, k=10)
+        self.config.update(config)
+        c = self.config
+        self.conv1 = DynamicEdgeConv(MLP([2 * 3, 64, 64, c['n_features1']]), k=c['k'], aggr='max')
+        self.pool1 = DynamicASAPool(c['n_features1'], k=c['k'])
+        self.conv2 = DynamicEdgeConv(MLP([2 * c['n_features1'], c['n_features2'], c['n_features2'], c['n_features2']]),
+                                     k=c['k'], aggr='max')
+        self.pool2 = DynamicASAPool(c['n_features2'], k=c['k'])
+        self.conv3 = DynamicEdgeConv(MLP([2 * c['n_features2'], c['n_features3'], c['n_features3'], c['n_features3']]),
+                                     k=c['k'], aggr='max')
+        self.lin = nn.Linear(c['n_features3'], out_size)
+
+    def register_packs(self, plan):
+        for conv in (self.conv1, self.conv2, self.conv3):
+            conv.register_packs(plan)
+        plan.add_linear(self.lin.weight)
+
+    def forward(self, positions):
+        B, N = positions.size(0), positions.size(1)
+        out = positions.reshape(-1, positions.size(-1)).float().contiguous()
+        for conv, pool in ((self.conv1, self.pool1), (self.conv2, self.pool2)):
+            _check_cloud(conv.k, N)
+            out = conv(out, B, N)
+            out, (_, N) = pool(out, (B, N), order=conv.last_order)
+        _check_cloud(self.conv3.k, N)
+        out = self.conv3(out, B, N)
+        return ops.linear(ops.segment_max(out, B, N), self.lin.weight, self.lin.bias)
 
 
 class _PointConvHolder(nn.Module):
@@ -461,16 +592,3 @@ class MLPDecoder(nn.Module):
         out = ops.dense_mlp(batch_enc, self.mlp, self.training)
         return out.contiguous().view(batch_size, self.out_len, -1)
 
-
-def _not_accelerated(name):
-    class _Missing(nn.Module):
-        def __init__(self, *a, **kw):
-            raise NotImplementedError(
-                '%s is selectable in the reference (nn/net_blocks.py) but used by no shipped config; '
-                'it is a "next" row of the scope table (SURVEY.md §8f) and has no kernels yet' % name)
-    _Missing.__name__ = name
-    return _Missing
-
-
-EdgeConvPoolingFeatures = _not_accelerated('EdgeConvPoolingFeatures')
-DynamicASAPool = _not_accelerated('DynamicASAPool')

@@ -86,7 +86,14 @@ class GarmentFullPattern3D(BaseModule):
                                                       **in_loss_config})
         self.config['loss'] = self.loss.config               # the loss object owns the merged dict from here on
         cfg = self.config
-        self.feature_extractor = getattr(blocks, cfg['feature_extractor'])(cfg['pattern_encoding_size'], cfg)
+        extractor = getattr(blocks, cfg['feature_extractor'])
+        if extractor is blocks.EdgeConvPoolingFeatures:
+            # the block itself is usable (net_blocks.EdgeConvPoolingFeatures); the model is not: it returns one [B, out] tensor,
+            # and the reference's forward_encode takes [0] of it (nn/nets.py:136) — the FIRST garment's encoding for the batch
+            raise NotImplementedError('GarmentFullPattern3D with EdgeConvPoolingFeatures: the reference encodes every garment of '
+                                      'a batch with the first garment\'s encoding (nn/nets.py:136 takes [0] of the block\'s '
+                                      '[B, out] tensor); use EdgeConvFeatures with graph_pooling: True instead')
+        self.feature_extractor = extractor(cfg['pattern_encoding_size'], cfg)
         cfg.update(getattr(self.feature_extractor, 'config', {}))
         # one row per sequence decoder: name, class key, output width, sequence length (`out_len` is swallowed by **kwargs in the
         # recurrent decoders and used by MLPDecoder: nn/net_blocks.py:273-298,365)
@@ -142,6 +149,9 @@ class GarmentSegmentPattern3D(GarmentFullPattern3D):
                                   quality_components=['shape', 'discrete', 'rotation', 'translation'])
         super().__init__(data_config, config, in_loss_config)
         self.save_att_weights = 'segmentation' in self.loss.config['loss_components']
+        if self.save_att_weights and self.config.get('graph_pooling'):
+            raise ValueError("the 'segmentation' loss term needs one attention weight per input point; graph_pooling: True "
+                             "leaves the pooled points only — disable one of the two settings")
         if 'local_attention' not in self.config:
             self.config['local_attention'] = False
         attention_input_size = self.feature_extractor.config['EConv_feature']

@@ -14,6 +14,7 @@ Two per-model services live here as well (both optional; without them every Func
                 straight into the arena's gradient buffer (no per-parameter tensors, no cat/copy for the all-reduce
                 buckets, one fused Adam launch).
 """
+import math
 import os
 import warnings
 import weakref
@@ -1150,6 +1151,95 @@ def edge_conv_general(x, B, N, k, training, eps, momentum, nb, aggr, tensors):
     else:
         out = SegmentMeanFn.apply(msg, B * N, k)
     return out, idx
+
+
+# -------------------------------------------------------------------------------------------------
+# graph pooling (DynamicASAPool)
+# -------------------------------------------------------------------------------------------------
+ASAP_K = 10                        # nn/net_blocks.py:204: DynamicASAPool builds its graph with k = 10 whatever it is given
+ASAP_F_MAX, ASAP_N_MAX = 512, 8192
+
+
+def asap_count(N, ratio):
+    """Nodes PyG's topk keeps per cloud: ceil(float(ratio) * N) evaluated in fp32, as PyG does on a float32 fitness (0.3 x 50 -> 16,
+    not 15); a ratio >= 1 is a count (at most N)."""
+    if not ratio > 0:
+        raise ValueError('pool ratio must be positive, got %r' % (ratio,))
+    if ratio >= 1:
+        return min(int(ratio), N)
+    return int(math.ceil(np.float32(ratio) * np.float32(N)))
+
+
+def asap_state_words(B, N, F, k):
+    """include/gpe_hip.h gpe_asap_fwd: the 4-byte words of the state the forward leaves for the backward."""
+    return 1024 + B * N * (2 * F + k + 8)
+
+
+def asap_bwd_ws_bytes(B, N, F, k):
+    """include/gpe_hip.h gpe_asap_bwd: the backward's workspace."""
+    nblk = min((B * N + 15) // 16, 1024)
+    return 8 * (nblk + 1) * (5 * F + 3) + 4 * B * N * (F + k + 4)
+
+
+class AsapPoolFn(torch.autograd.Function):
+    """DynamicASAPool (nn/net_blocks.py:194-218): PyG ASAPooling on knn(x, x, 10) per cloud -> (out [B*M, F], perm, rank, idx).
+    x: [B*N, F] rows of B clouds of N points; params: lin.weight, lin.bias, att.weight, att.bias, gnn_score.lin1.weight,
+    lin1.bias, lin2.weight, lin3.weight, lin3.bias.  perm int32 [B*M]: the kept GLOBAL rows, per cloud in descending fitness;
+    rank int32 [B*N]: output row of a kept node, -1 otherwise; idx int32 [B, N, min(10, N)]: the kNN graph.  M is computed on the
+    host from (N, ratio): nothing here reads the device, so the op can be captured (graph.StepGraph).  order: a locality order of
+    the points (the preceding EdgeConv layer's last_order), a speed hint of the graph search.  save=False (no_grad): nothing is
+    kept for a backward."""
+
+    @staticmethod
+    def forward(ctx, x, B, N, ratio, order, save, trace, *params):
+        _dev_check(x)
+        F = x.shape[1]
+        if not (1 <= F <= ASAP_F_MAX and 1 <= N <= ASAP_N_MAX) or x.shape[0] != B * N:
+            raise ValueError('ASAP pooling takes 1 <= F <= %d features and 1 <= N <= %d points per cloud (got x %s for B=%d, '
+                             'N=%d)' % (ASAP_F_MAX, ASAP_N_MAX, tuple(x.shape), B, N))
+        k = min(ASAP_K, N)
+        M = asap_count(N, ratio)
+        xc = x if x.stride(1) == 1 else x.contiguous()
+        idx = knn(xc, B, N, k, order=order)
+        rev_off, rev_edge = knn_reverse(idx)
+        dev = x.device
+        state = torch.empty(asap_state_words(B, N, F, k), device=dev, dtype=F32)
+        out = torch.empty(B * M, F, device=dev, dtype=F32)
+        perm = torch.empty(B * M, device=dev, dtype=torch.int32)
+        rank = torch.empty(B * N, device=dev, dtype=torch.int32)
+        L.call('gpe_asap_fwd', xc, xc.stride(0), B, N, F, k, rev_off, rev_edge, *params, M, out, perm, rank, state)
+        ctx.mark_non_differentiable(perm, rank, idx)
+        ctx.dims = (B, N, F, k)
+        if trace is not None:                              # copies, not views: the trace must not keep the whole state alive
+            BN = B * N
+            trace['winners'] = state[1024 + BN * F:1024 + 2 * BN * F].view(torch.int32).view(BN, F).clone()
+            trace['fitness'] = state[1024 + BN * (2 * F + k + 6):1024 + BN * (2 * F + k + 7)].clone()
+        if save:
+            ctx.save_for_backward(xc, idx, rev_off, rev_edge, rank, state, *params)
+        return out, perm, rank, idx
+
+    @staticmethod
+    def backward(ctx, gout, *_):
+        xc, idx, rev_off, rev_edge, rank, state, *params = ctx.saved_tensors
+        B, N, F, k = ctx.dims
+        dev = xc.device
+        gout = gout.contiguous()
+        dx = torch.empty(B * N, F, device=dev, dtype=F32)
+        grads = [_gbuf(p) for p in params]
+        nws = asap_bwd_ws_bytes(B, N, F, k)
+        L.call('gpe_asap_bwd', gout, xc, xc.stride(0), B, N, F, k, idx, rev_off, rev_edge, *params, rank, state, dx, F, *grads,
+               _workspace(nws, dev))
+        return (dx, None, None, None, None, None, None) + tuple(_gret(p, g) for p, g in zip(params, grads))
+
+
+def asap_pool(x, B, N, params, ratio, order=None, trace=None):
+    """-> (out [B*M, F], M): DynamicASAPool's ASAPooling on x [B*N, F] (AsapPoolFn).  trace (a dict, optional) receives the kept
+    rows 'perm', the output rows 'rank', the graph 'knn', the channel-max 'winners' and the 'fitness' of this call."""
+    save = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params))
+    out, perm, rank, idx = AsapPoolFn.apply(x, B, N, ratio, order, save, trace, *params)
+    if trace is not None:
+        trace.update(perm=perm, rank=rank, knn=idx)
+    return out, asap_count(N, ratio)
 
 
 # -------------------------------------------------------------------------------------------------

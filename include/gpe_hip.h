@@ -542,6 +542,42 @@ int gpe_quality_stitches(const float* tags, long t_sb, long t_sp, long t_sl, int
                          int L, int flags, const float* stats_host, double* part, void* stream);
 int gpe_quality_finalize(const double* part, int B, int P, int L, int flags, float* out, int32_t* counts, void* stream);
 
+/* ---- graph pooling: DynamicASAPool = PyG ASAPooling on the kNN graph of the node features (nn/net_blocks.py:194-218, used by
+ * EdgeConvFeatures with graph_pooling (:113-118, :138-142, :172-176) and EdgeConvPoolingFeatures (:221-268)) -------------------
+ * Added without a version bump (gpe_abi_version() stays 7): two compute entry points, nothing else changes.
+ * Graph: idx [B][N][k] of gpe_knn on x with k = min(10, N) (the reference fixes k = 10, :204) and its transpose rev_off / rev_edge
+ * of gpe_knn_reverse.  torch_cluster's rows are [query, neighbour] and ASAPooling sends from row 0 to row 1, so target c receives
+ * from every q with c in kNN(q); add_remaining_self_loops drops a q == c edge and appends one self-loop:
+ *   cluster(c) = {c} + {q != c : c in kNN(q)},  deg(c) = |cluster(c)|.
+ * Forward (fp32 in every arithmetic mode): x_q[c] = channel max over cluster(c) (ties: lowest source index);
+ * s_cq = leaky_relu(att([lin(x_q[c]) | x[q]]), 0.2), folded as u . x_q[c] + s0 + w_x . x[q] with u = W_lin^T w_q,
+ * s0 = w_q . b_lin + b_att (att.weight = [w_q | w_x]); alpha = softmax over cluster(c) (max-subtracted, denominator + 1e-16);
+ * x'_c = sum alpha_cq x[q]; fitness_c = sigmoid(sum_{q in cluster(c)} lin1(x'_q) - deg(c) lin2(x'_c) + lin3(x'_c)) (LEConv);
+ * per cloud the M nodes of highest fitness, in descending fitness, ties to the lower index (PyG topk); M is the caller's
+ * ceil(fp32(ratio) * fp32(N)).  out [B*M][F] = x'[perm] * fitness[perm]; perm int32 [B*M] = GLOBAL rows b*N + c; rank int32
+ * [B*N] = the output row of a kept node, -1 otherwise.  The coarsened edge list of ASAPooling is not built (the reference discards
+ * it).  Parameters in PyG 2.x's layout: w_lin [F][F], b_lin [F], w_att [1][2F], b_att [1], w1 [1][F], b1 [1], w2 [1][F] (no
+ * bias), w3 [1][F], b3 [1] (gnn_score.lin1 / lin2 / lin3).
+ * state: caller-owned, 16-B aligned, 4 * (1024 + B*N*(2F + k + 8)) bytes, written by gpe_asap_fwd and read by gpe_asap_bwd
+ * (x', channel-max winners, alpha, scores, fitness, degrees).
+ * Backward: dout [B*M][F] dense -> dx [B*N][lddx >= F] and the nine parameter gradients (same shapes as the parameters; written,
+ * not accumulated).  No atomics: per-node pulls over the kNN lists and the reverse buckets, parameter sums in fp64 per workgroup
+ * partial and combined in a fixed order (bit-reproducible).  ws: caller-owned, 16-B aligned,
+ *   8 * (nblk + 1) * (5F + 3) + 4 * B*N*(F + k + 4) bytes,   nblk = min(ceil(B*N / 16), 1024).
+ * Limits: 1 <= F <= 512, 1 <= N <= 8192, 1 <= k <= min(64, N), 1 <= M <= N, ldx >= F; anything else returns -22.
+ * Launches: forward 3 (prep: w_x . x and the folded u, s0; cluster: one wave per target; select: one workgroup per cloud, bitonic
+ * sort of 64-bit keys in LDS), backward 5 (dfitness; per-target G and attention backward; per-source pull + partials; column
+ * sums; finalize). */
+int gpe_asap_fwd(const float* x, int ldx, int B, int N, int F, int k, const int32_t* rev_off, const int32_t* rev_edge,
+                 const float* w_lin, const float* b_lin, const float* w_att, const float* b_att, const float* w1, const float* b1,
+                 const float* w2, const float* w3, const float* b3, int M, float* out, int32_t* perm, int32_t* rank, float* state,
+                 void* stream);
+int gpe_asap_bwd(const float* dout, const float* x, int ldx, int B, int N, int F, int k, const int32_t* idx, const int32_t* rev_off,
+                 const int32_t* rev_edge, const float* w_lin, const float* b_lin, const float* w_att, const float* b_att,
+                 const float* w1, const float* b1, const float* w2, const float* w3, const float* b3, const int32_t* rank,
+                 const float* state, float* dx, int lddx, float* g_wlin, float* g_blin, float* g_watt, float* g_batt, float* g_w1,
+                 float* g_b1, float* g_w2, float* g_w3, float* g_b3, void* ws, void* stream);
+
 
 /* ---- optimizer / input side (nn/trainer.py:162-185; nn/data/transforms.py:35-50) ----------------------------------- */
 /* one torch.optim.Adam step (amsgrad off) over a flat arena of n floats (16-B aligned p, g, m, v); `step` counts from 1;
