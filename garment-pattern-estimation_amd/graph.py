@@ -24,6 +24,7 @@ import torch
 
 from . import _lib as L
 from . import ops
+from . import streams
 
 
 class HostDrawn:
@@ -31,7 +32,7 @@ class HostDrawn:
 
     def __init__(self, device):
         self.device = device
-        self.entries = []            # [shape, fill_fn, device tensor, [pinned x 2], [event x 2], flip]
+        self.entries = []            # streams.Staged: .dst the device tensor, .fill what draws it
         self.cursor = 0
         self.capturing = False
 
@@ -39,15 +40,7 @@ class HostDrawn:
         """Draw every registered tensor (registration order = call order = the reference's draw order) and queue its copy."""
         self.cursor = 0
         for e in self.entries:
-            self._fill(e)
-
-    def _fill(self, e):
-        e[5] ^= 1
-        pin, ev = e[3][e[5]], e[4][e[5]]
-        ev.synchronize()                       # the copy that last read this pinned buffer (two steps ago) has run
-        e[1](pin)
-        e[2].copy_(pin, non_blocking=True)
-        ev.record()
+            e.refill()
 
     def get(self, shape, fill_fn):
         shape = tuple(shape)
@@ -57,14 +50,12 @@ class HostDrawn:
             if self.capturing:
                 raise RuntimeError('StepGraph: the captured step draws a host tensor the warm-up steps did not draw (shape %s): the '
                                    'step must issue the same sequence of launches every time' % (shape,))
-            e = [shape, fill_fn, torch.empty(shape, device=self.device),
-                 [torch.empty(shape, pin_memory=True) for _ in range(2)], [torch.cuda.Event() for _ in range(2)], 0]
-            self.entries.append(e)
-            self._fill(e)
-        e = self.entries[i]
-        if e[0] != shape:
-            raise RuntimeError('StepGraph: host-drawn tensor %d changed shape (%s -> %s)' % (i, e[0], shape))
-        return e[2]
+            self.entries.append(streams.Staged(shape, self.device, fill_fn))
+            self.entries[i].refill()
+        dst = self.entries[i].dst
+        if tuple(dst.shape) != shape:
+            raise RuntimeError('StepGraph: host-drawn tensor %d changed shape (%s -> %s)' % (i, tuple(dst.shape), shape))
+        return dst
 
 
 class StepGraph:
@@ -86,7 +77,7 @@ class StepGraph:
         self.static_in = None
         self.loss = None
         self.guards = []             # (HalfActGuard, amax word) pairs met during the capture
-        self.hyper = []              # per arena run: (device pair, [pinned pair x 2], [event x 2])
+        self.hyper = []              # per arena run: streams.Staged of Adam's two step-dependent floats
         self.runs = None
         self.replays = 0
         self.captures = 0
@@ -107,7 +98,7 @@ class StepGraph:
 
     def _like(self, obj):
         if isinstance(obj, torch.Tensor):
-            return torch.empty_like(obj, device=self.device) if obj.dtype.is_floating_point or True else obj
+            return torch.empty_like(obj, device=self.device)
         if isinstance(obj, dict):
             return {k: self._like(v) for k, v in obj.items()}
         if isinstance(obj, (list, tuple)):
@@ -197,17 +188,12 @@ class StepGraph:
         if i >= len(self.hyper) and ops.CAPTURE is not None:
             raise RuntimeError('StepGraph: more optimizer runs than pre-allocated scalar slots')
         while len(self.hyper) <= i:
-            self.hyper.append((torch.zeros(2, device=self.device), [torch.zeros(2, pin_memory=True) for _ in range(2)],
-                               [torch.cuda.Event() for _ in range(2)], [0]))
+            self.hyper.append(streams.Staged(2, self.device))
         return self.hyper[i]
 
     def write_hyper(self, i, lr, beta1, beta2, step):
-        dev, pins, evs, flip = self.hyper_slot(i)
-        flip[0] ^= 1
-        pin, ev = pins[flip[0]], evs[flip[0]]
-        ev.synchronize()
-        rc = L.lib().gpe_adam_hyper(float(lr), float(beta1), float(beta2), int(step), ctypes.c_void_p(pin.data_ptr()))
+        slot = self.hyper_slot(i)
+        rc = L.lib().gpe_adam_hyper(float(lr), float(beta1), float(beta2), int(step), ctypes.c_void_p(slot.next().data_ptr()))
         if rc != 0:
             raise RuntimeError('gpe_adam_hyper failed with code %d' % rc)
-        dev.copy_(pin, non_blocking=True)
-        ev.record()
+        slot.push()

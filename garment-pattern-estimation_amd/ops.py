@@ -14,6 +14,7 @@ Two per-model services live here as well (both optional; without them every Func
                 straight into the arena's gradient buffer (no per-parameter tensors, no cat/copy for the all-reduce
                 buckets, one fused Adam launch).
 """
+import contextlib
 import math
 import os
 import warnings
@@ -23,6 +24,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import streams
 
 F32 = torch.float32
 
@@ -57,12 +59,10 @@ def _workspace(nbytes, device):
     """caller-owned scratch of a C-ABI call (include/gpe_hip.h: `ws`).  One grow-only buffer per (device, stream): launches of one
     stream are ordered, so consecutive calls may share it, and two streams never do (the library's only rule for workspaces).
     Re-allocation goes through torch's caching allocator, which keeps the old block alive until the stream has passed it."""
-    dev = torch.device(device)
-    idx = dev.index if dev.index is not None else torch.cuda.current_device()
-    key = (idx, torch.cuda.current_stream(idx).cuda_stream)
+    key = streams.stream_key(device)
     buf = _WS.get(key)
     if buf is None or buf.numel() < nbytes:
-        buf = torch.empty(max(int(nbytes), 1 << 20), device=torch.device('cuda', idx), dtype=torch.uint8)
+        buf = torch.empty(max(int(nbytes), 1 << 20), device=torch.device('cuda', key[0]), dtype=torch.uint8)
         _WS[key] = buf
     return buf
 
@@ -100,12 +100,10 @@ _TICKETS = {}
 
 def _ticket(device):
     """the last-arriver ticket of gpe_pack_fold: one zeroed uint32 per (device, stream), left zero by every launch."""
-    dev = torch.device(device)
-    idx = dev.index if dev.index is not None else torch.cuda.current_device()
-    key = (idx, torch.cuda.current_stream(idx).cuda_stream)
+    key = streams.stream_key(device)
     t = _TICKETS.get(key)
     if t is None:
-        t = _TICKETS[key] = torch.zeros(1, device=torch.device('cuda', idx), dtype=torch.int32)
+        t = _TICKETS[key] = torch.zeros(1, device=torch.device('cuda', key[0]), dtype=torch.int32)
     return t
 
 
@@ -136,83 +134,22 @@ def pack_fold(W, bias, stats, ews, ews_n, clear_word):
 SIDE_GRADS = not (os.environ.get('GPE_DEBUG') == '1' and os.environ.get('GPE_SIDE_GRADS') == '0')
 SIDE_MIN_EDGES = 1 << 17
 SIDE_PQ = not (os.environ.get('GPE_DEBUG') == '1' and os.environ.get('GPE_SIDE_PQ') == '0')     # the forward fork of EdgeConvFn (A/B)
+# The fork / join mechanics, the lane's state and the idle-stretch jobs live in streams.py (one lane per device); this file decides
+# what goes there.  _LAST_EDGES stays process-global on purpose: it is a size proxy for "is this step GPU-bound", not stream state.
 _LAST_EDGES = [0]
-_SIDE_STREAMS = {}
-_SIDE_JOIN_QUEUED = [False]
-_SIDE_DIRTY = [False]                 # the side stream holds launches the current stream has not waited for
 
 
-def _side_stream():
-    idx = torch.cuda.current_device()
-    st = _SIDE_STREAMS.get(idx)
-    if st is None:
-        st = _SIDE_STREAMS[idx] = torch.cuda.Stream(device=idx)
-    return st
+def _side_ok(edges):
+    """May a step whose EdgeConv graph has `edges` edges fork onto the side lane now?  (the switches are read at call time)"""
+    return bool(SIDE_GRADS and edges >= SIDE_MIN_EDGES and not torch.cuda.is_current_stream_capturing())
 
 
-def join_side():
-    """The current stream waits for everything on the side stream.  Runs as an autograd callback at the end of every backward pass
-    that used the side stream, and once more in front of every optimizer step (optim.FusedAdam) — the second call is what a pass
-    that died with an exception half-way leaves to."""
-    _SIDE_JOIN_QUEUED[0] = False
-    if _SIDE_DIRTY[0]:
-        _SIDE_DIRTY[0] = False
-        torch.cuda.current_stream().wait_stream(_side_stream())
-
-
-# Work that only a LATER phase of the step needs and that has its inputs early — the transposed graphs of the gather backward need
-# the forward's graphs only — waits in _IDLE_JOBS for a stretch of the step that leaves the chip idle: the first recurrent stack of the
-# forward (the pattern decoder's persistent launch sits on the CUs of one XCD) launches it on the side stream (run_idle_jobs).
-_IDLE_JOBS = []
-
-
-def run_idle_jobs():
-    if not _IDLE_JOBS:
-        return
-    if torch.cuda.is_current_stream_capturing():
-        del _IDLE_JOBS[:]
-        return
-    main, side = torch.cuda.current_stream(), _side_stream()
-    side.wait_stream(main)
-    _SIDE_DIRTY[0] = True
-    with torch.cuda.stream(side):
-        for job in _IDLE_JOBS:
-            job['rev'] = knn_reverse(job['idx'])
-            job['idx'].record_stream(side)
-            job['event'] = side.record_event()
-    del _IDLE_JOBS[:]
-
-
-class side_grads:
+def side_grads(params, tensors):
     """with side_grads(params, tensors) as on_side: ...  — the launches inside run on the side stream when that is legal (see above);
     `tensors` = every main-stream tensor the launches read (kept away from the allocator until the side stream has passed them)."""
-
-    def __init__(self, params, tensors):
-        self.on = bool(SIDE_GRADS and _LAST_EDGES[0] >= SIDE_MIN_EDGES and params and all(_SINK.get(p.data_ptr()) is not None and _SINK[p.data_ptr()][0]() is not None
-                                                     for p in params) and not torch.cuda.is_current_stream_capturing())
-        self.tensors = tensors
-        self.ctx = None
-
-    def __enter__(self):
-        if not self.on:
-            return False
-        main, side = torch.cuda.current_stream(), _side_stream()
-        side.wait_stream(main)
-        for t in self.tensors:
-            if t is not None:
-                t.record_stream(side)
-        _SIDE_DIRTY[0] = True
-        if not _SIDE_JOIN_QUEUED[0]:
-            _SIDE_JOIN_QUEUED[0] = True
-            torch.autograd.Variable._execution_engine.queue_callback(join_side)
-        self.ctx = torch.cuda.stream(side)
-        self.ctx.__enter__()
-        return True
-
-    def __exit__(self, *exc):
-        if self.ctx is not None:
-            self.ctx.__exit__(*exc)
-        return False
+    if params and _side_ok(_LAST_EDGES[0]) and all(_SINK.get(p.data_ptr()) is not None and _SINK[p.data_ptr()][0]() is not None for p in params):
+        return streams.lane(params[0].device.index).fork(tensors, leaf=True)
+    return contextlib.nullcontext(False)
 
 
 # -------------------------------------------------------------------------------------------------
@@ -860,22 +797,17 @@ class EdgeConvFn(torch.autograd.Function):
         words = f16x3_words(2 * nb + 1, E, dev)           # (+ 1: max |s g| of the layer-output gradient, lazy dz3)
         # The [P|Q] projection (and its f16x3 bound) needs the layer input only — not the graph: on a GPU-bound step it runs on the
         # side stream beside the graph search, whose kernels leave most of the chip's issue slots empty
-        fork = bool(SIDE_GRADS and SIDE_PQ and E >= SIDE_MIN_EDGES and not torch.cuda.is_current_stream_capturing())
+        fork = SIDE_PQ and _side_ok(E)
         if fork:
-            main, side = torch.cuda.current_stream(), _side_stream()
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
+            lane = streams.lane(dev.index)
+            with lane.fork([x, words]):                     # (joined below, once the graph search is queued)
                 PQ = torch.empty(BN, 2 * H0, device=dev, dtype=F32)
                 linear_raw(_rows2d(x), wpq_p, bpq, BN, 2 * H0, C, _rows2d(PQ))
                 if words is not None:
                     sws, sws_n = edge_workspace(B, N, k, max(round_up(widths[-1], 4), 2 * H0), dev)      # (the side stream's own workspace)
                     L.call('gpe_edge_pq_amax', PQ, 2 * H0, H0, BN, _word(words, 0), sws, sws_n)
-            x.record_stream(side)
-            if words is not None:
-                words.record_stream(side)
             idx, jg, order_out = knn(x, B, N, k, want_global=True, order=order, want_order=True)
-            main.wait_stream(side)
-            PQ.record_stream(main)
+            lane.wait(made=[PQ])
         else:
             idx, jg, order_out = knn(x, B, N, k, want_global=True, order=order, want_order=True)
             PQ = torch.empty(BN, 2 * H0, device=dev, dtype=F32)
@@ -951,10 +883,13 @@ class EdgeConvFn(torch.autograd.Function):
         ctx.words = words
         ctx.rev_job = None
         if fork and training:
+            # Work that only a LATER phase of the step needs and that has its inputs early — the transposed graph of the gather backward
+            # needs this graph only — waits on the lane for a stretch of the step that leaves the chip idle: the first recurrent stack of
+            # the forward (the pattern decoder's persistent launch sits on the CUs of one XCD) launches it there (RNNStackFn.forward)
             if order is None:
-                del _IDLE_JOBS[:]                            # (a new forward pass: whatever an abandoned one left behind is dropped)
-            ctx.rev_job = {'idx': idx, 'rev': None, 'event': None}
-            _IDLE_JOBS.append(ctx.rev_job)
+                del lane.jobs[:]                             # (a new forward pass: whatever an abandoned one left behind is dropped)
+            ctx.rev_job = {'fn': knn_reverse, 'src': idx, 'out': None, 'event': None}
+            lane.jobs.append(ctx.rev_job)
         ctx.save_for_backward(x, idx, jg, PQ, *params, *acts[1:], *stats,
                               *([mx, mn, amx, amn] if aggr == 'max' else [abar]))
         ctx.mark_non_differentiable(idx, order_out)
@@ -991,16 +926,14 @@ class EdgeConvFn(torch.autograd.Function):
         # now and finds its CUs in the gaps between the edge kernels (main waits for it in front of gpe_edge_pull_dq)
         rev, rev_event = None, None
         job = getattr(ctx, 'rev_job', None)
-        if job is not None and job['rev'] is not None:
-            rev, rev_event = job['rev'], job['event']       # built during the forward's idle stretch (run_idle_jobs)
-        elif SIDE_GRADS and SIDE_PQ and E >= SIDE_MIN_EDGES and not torch.cuda.is_current_stream_capturing():
-            if job is not None and job in _IDLE_JOBS:
-                _IDLE_JOBS.remove(job)
-            main, side = torch.cuda.current_stream(), _side_stream()
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
+        lane = streams.lane(dev.index)
+        if job is not None and job['out'] is not None:
+            rev, rev_event = job['out'], job['event']             # built during the forward's idle stretch (Lane.run_jobs)
+        elif SIDE_PQ and _side_ok(E):
+            if job is not None and job in lane.jobs:
+                lane.jobs.remove(job)
+            with lane.fork([idx]):                          # (joined in front of gpe_edge_pull_dq)
                 rev = knn_reverse(idx)
-            idx.record_stream(side)
 
         # ---- last block: BatchNorm applied after the aggregation -----------------------------------------
         psb = L.query('gpe_point_sums_blocks')
@@ -1084,12 +1017,8 @@ class EdgeConvFn(torch.autograd.Function):
 
         # ---- block 0: gather backward = deterministic pull through the transposed graph -----------------
         if rev is not None:
-            if rev_event is not None:
-                torch.cuda.current_stream().wait_event(rev_event)
-            else:
-                torch.cuda.current_stream().wait_stream(_side_stream())
             rev_off, rev_edge = rev
-            rev_off.record_stream(torch.cuda.current_stream()); rev_edge.record_stream(torch.cuda.current_stream())
+            lane.wait(made=rev, event=rev_event)
         else:
             rev_off, rev_edge = knn_reverse(idx)
         L.call('gpe_edge_pull_dq', dz, dz.stride(0), rev_off, rev_edge, B, N, k, H0, dPQ[:, H0:], 2 * H0)
@@ -1264,8 +1193,8 @@ class RNNStackFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, h0, c0, T, n_layers, kind, want_state, h0_ok, *params):
-        run_idle_jobs()                                    # (the chip is about to idle: ops._IDLE_JOBS)
         _dev_check(x)
+        streams.lane(x.device.index).run_jobs()            # (the chip is about to idle: the jobs EdgeConvFn.forward left on the lane)
         ctx.set_materialize_grads(False)
         dev = x.device
         lstm = kind == 'lstm'

@@ -16,6 +16,7 @@ import math
 import torch
 
 from . import ops
+from . import streams
 from . import _lib as L
 
 
@@ -210,7 +211,8 @@ class FusedAdam:
 
     def step(self, grad_scale=1.0):
         a = self.arena
-        ops.join_side()                # weight gradients written on the side stream (ops.side_grads)
+        # weight gradients written on the side stream (ops.side_grads) — also what a backward pass that died half-way left un-joined
+        streams.lane(a.flat.device.index).join()
         lr = self.lr if self.schedule is None else self.schedule.lr(self.t)
         self.t += 1
         runs = self._runs(self._live(), advance=True)
@@ -228,11 +230,11 @@ class FusedAdam:
     def step_captured(self, ctx, grad_scale=1.0):
         """Called INSIDE the capture, after backward: queues the launches, advances nothing.  -> the runs' (lo, hi)."""
         a = self.arena
-        ops.join_side()
+        streams.lane(a.flat.device.index).join()
         self._cap_live = self._live()
         runs = self._runs(self._cap_live, advance=False)
         for r, (lo, hi, _) in enumerate(runs):
-            L.call('gpe_adam_step_dev', a.flat[lo:hi], a.grad[lo:hi], self.m[lo:hi], self.v[lo:hi], hi - lo, ctx.hyper_slot(r)[0],
+            L.call('gpe_adam_step_dev', a.flat[lo:hi], a.grad[lo:hi], self.m[lo:hi], self.v[lo:hi], hi - lo, ctx.hyper_slot(r).dst,
                    float(self.betas[0]), float(self.betas[1]), self.eps, self.weight_decay, float(grad_scale), 1)
         if len(runs) != 1 or runs[0][:2] != (0, a.numel):
             a.grad.zero_()

@@ -12,6 +12,7 @@ import torch
 import torch.distributed as dist
 import torch.nn as nn
 
+from . import streams
 from .optim import FlatArena
 
 
@@ -121,10 +122,8 @@ class DistributedHotPath(nn.Module):
             # "written" means "queued": on the stream of the launch that told the arena.  The collective's stream waits for the CURRENT
             # stream only, and gradients of this bucket may sit on the other one (ops.side_grads runs the leaf weight-gradient launches
             # on a side stream): inside a side block the side stream is behind everything the main stream had queued at the fork —
-            # which is every gradient written so far — and on the main stream the side stream is joined here.
-            from . import ops
-            if ops._SIDE_DIRTY[0] and torch.cuda.current_stream() != ops._side_stream():
-                torch.cuda.current_stream().wait_stream(ops._side_stream())
+            # which is every gradient written so far — and on the main stream the side stream is joined here (Lane.join tells the two apart).
+            streams.lane(flat.device.index).join()
         if self._avg_op:
             # RCCL averages inside the collective: no extra elementwise launch per bucket and step
             self._inflight.append(dist.all_reduce(flat, op=dist.ReduceOp.AVG, group=self.group, async_op=True))

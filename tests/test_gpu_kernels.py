@@ -2167,7 +2167,7 @@ def test_two_rank_exchange_on_shared_gpu(gpe, golden_dir, tmp_path):
         ex = ddp.exposed_ms()
         assert ex is not None and ex >= 0.0               # the un-hidden part of the exchange is measured and reported (bench.py N > 1 lines)
         assert 0 < early < len(ddp._buckets)             # some buckets left during backward, the None-grad one at the end
-        assert ops._SIDE_STREAMS                          # (the side stream was used)
+        assert gpe_amd.streams.lane(0).stream is not None   # (the side stream was used)
         for n, p in model.named_parameters():
             g = local_g[n]
             if g is None:

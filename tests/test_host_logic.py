@@ -358,3 +358,19 @@ def test_half_act_guard_host_side():
     assert c2.half_act_guard.disabled and c2.half_act_guard._pending is None and c2.half_act_guard is not conv.half_act_guard
     g3 = pickle.loads(pickle.dumps(conv.half_act_guard))
     assert g3.disabled and g3._pending is None
+
+
+def test_side_lanes_are_per_device():
+    """streams.lane: one lane per device ordinal, sharing no flag and no job list — and building one touches no device (there is
+    none here): the stream itself is created on first use."""
+    from gpe_amd import streams
+    a, b = streams.lane(0), streams.lane(1)
+    assert a is streams.lane(0) and a is not b and (a.index, b.index) == (0, 1)
+    assert a.stream is None and b.stream is None
+    a.dirty = a.queued = True
+    a.jobs.append('job')
+    try:
+        assert not b.dirty and not b.queued and b.jobs == [] and b.jobs is not a.jobs
+    finally:
+        a.dirty = a.queued = False
+        del a.jobs[:]
