@@ -244,3 +244,16 @@ class StitchOnEdge3DPairs(BaseModule):
         return_shape.pop(-1)
         out = ops.dense_mlp(pairs_batch.contiguous().view(-1, pairs_batch.shape[-1]), self.mlp, self.training)
         return out.view(return_shape)
+
+    def predict_stitches(self, edges3d, num_edges, data_stats, **kw):
+        """The model's prediction-time use (nn/data/pattern_converter.py:411-499: all_edge_pairs + stitches_from_pair_classifier):
+        every cross-panel pair of the garments' 3D edges classified and, per edge, only the strongest positive kept — on the device,
+        without materialising the pairs.  edges3d [B, P, L, element_size / 2] un-standardised edges per panel slot, num_edges [B, P];
+        data_stats: {'f_shift', 'f_scale'} of the pair rows.  -> {'stitches', 'num_stitches', 'scores'[, 'logits']} (ops.stitch_pairs;
+        keywords route=, return_logits=)."""
+        if self.pair_feature_len % 2:
+            raise ValueError('element_size must be even: a pair row is two edges (got %d)' % self.pair_feature_len)
+        if self.training:
+            raise RuntimeError('predict_stitches runs the eval-mode classifier: call .eval() first (the reference does, '
+                               'pattern_converter.py:415)')
+        return ops.stitch_pairs(edges3d, num_edges, self.mlp, data_stats['f_shift'], data_stats['f_scale'], **kw)

@@ -1547,6 +1547,154 @@ def dense_mlp(x, mlp, training):
     return DenseMLPFn.apply(x, training, blocks[0][2].eps, blocks[0][2].momentum, len(blocks), *params, *bufs)
 
 
+# -------------------------------------------------------------------------------------------------
+# stitch recovery from the edge-pair classifier (forward only)
+# -------------------------------------------------------------------------------------------------
+STITCH_PAIRS_MAX_PANELS, STITCH_PAIRS_MAX_EDGES = 32, 16
+STITCH_PAIRS_ROUTES = ('auto', 'fused', 'rows')
+_STITCH_ROWS_BUDGET = 1 << 19              # pair rows the generic route materialises per dense-MLP call
+
+
+def stitch_pairs_on_menu(mlp):
+    """can csrc/gpe_stitch_pairs.hip's fused kernel run this MLP?  (1 - 4 equally wide Linear layers in front of the output Linear,
+    width <= 256 and a multiple of 4, an even number <= 32 of input features)"""
+    blocks = [mlp[i] for i in range(len(mlp))]
+    n = len(blocks) - 1
+    if not 1 <= n <= 4 or blocks[-1][0].weight.shape[0] != 1:
+        return False
+    H, K0 = blocks[0][0].weight.shape
+    if H > 256 or H % 4 or K0 % 2 or K0 > 32:
+        return False
+    return all(tuple(b[0].weight.shape) == (H, H) for b in blocks[1:-1]) and blocks[-1][0].weight.shape[1] == H
+
+
+def _stitch_ldw(H):
+    nb = (H + 15) // 16
+    nb = 4 if nb <= 4 else 8 if nb <= 8 else 13 if nb <= 13 else 16
+    return nb * 16 if (nb * 16) % 32 == 16 else nb * 16 + 16
+
+
+def _stitch_row_off(e, Lm, E):
+    q, r = divmod(e, Lm)
+    return Lm * q * E - Lm * Lm * (q * (q + 1) // 2) + r * (E - (q + 1) * Lm)
+
+
+def _stitch_fused(edges, ne, blocks, shift, scale, table, dense):
+    """the store-free route: per-edge projections [A | Bv] of the first Linear (standardisation folded in), then one launch that
+    classifies every pair from them"""
+    B, P, Lm, Fe = edges.shape
+    dev = edges.device
+    n = len(blocks) - 1
+    H = blocks[0][0].weight.shape[0]
+    W1, b1 = blocks[0][0].weight, blocks[0][0].bias
+    inv = torch.tensor([1.0 / s for s in scale], device=dev, dtype=F32)
+    off = torch.tensor([-sh / sc for sh, sc in zip(shift, scale)], device=dev, dtype=F32)
+    ab = torch.empty(B * P * Lm, 2 * H, device=dev, dtype=F32)
+    rows = _rows2d(edges.view(-1, Fe))
+    linear_raw(rows, pack_weight(W1[:, :Fe], col_scale=inv[:Fe]), fold_bias(W1, b1, off), B * P * Lm, H, Fe, (ab, 2 * H, 0, 0))
+    linear_raw(rows, pack_weight(W1[:, Fe:], col_scale=inv[Fe:]), None, B * P * Lm, H, Fe, (ab[:, H:], 2 * H, 0, 0))
+    ldw = _stitch_ldw(H)
+    wpk = torch.zeros((n - 1) * (H + 1) * ldw + H + 4, device=dev, dtype=F32)
+    # f16x3: two-term fp16 planes of the hidden layers' folded weights, one power of two per layer (its amax word)
+    h3 = L.get_math() == 'f16x3' and H <= 224 and n > 1
+    KP = round_up(H, 32)
+    planes = torch.empty((n - 1) * KP * ldw, device=dev, dtype=F32) if h3 else None
+    words = torch.empty(n - 1, device=dev, dtype=torch.int32) if h3 else None
+    st = None
+    for l, blk in enumerate(blocks):
+        bn = blk[2]
+        if l > 0:
+            W, b = blk[0].weight, blk[0].bias
+            if l < n:
+                o = (l - 1) * (H + 1) * ldw
+                L.call('gpe_stitch_pairs_pack', W, W.stride(0), H, H, st[2], wpk[o:], ldw)
+                L.call('gpe_fold_bias', W, W.stride(0), H, H, b, st[3], wpk[o + H * ldw:])
+                if h3:
+                    L.call('gpe_absmax', wpk[o:], ldw, H, ldw, words[l - 1:])
+                    L.call('gpe_stitch_pairs_planes', wpk[o:], H, ldw, words[l - 1:], planes[(l - 1) * KP * ldw:])
+            else:
+                o = (n - 1) * (H + 1) * ldw
+                L.call('gpe_stitch_pairs_pack', W, W.stride(0), 1, H, st[2], wpk[o:], 1)
+                L.call('gpe_fold_bias', W, W.stride(0), 1, H, b, st[3], wpk[o + H:])
+        st = bn_from_running(bn.running_mean, bn.running_var, bn.weight, bn.bias, bn.eps)
+    L.call('gpe_stitch_pairs_fwd', ab, 2 * H, H, n, wpk, planes, words, st, ne, B, P, Lm, table, dense)
+
+
+def _stitch_rows(edges, ne, mlp, shift, scale, table, dense):
+    """the generic route: materialised pair rows of a chunk of i-edges -> the dense-MLP kernels (eval) -> the same epilogue"""
+    import ctypes
+    B, P, Lm, Fe = edges.shape
+    E = P * Lm
+    sh = (ctypes.c_float * (2 * Fe))(*[float(v) for v in shift])
+    sc = (ctypes.c_float * (2 * Fe))(*[float(v) for v in scale])
+    last = (P - 1) * Lm                         # the edges of the last panel slot have no later partner
+    c0 = 0
+    while c0 < last:
+        c1 = c0 + 1
+        while (c1 < last and B * (c1 + 1 - c0) <= 65535
+               and B * (_stitch_row_off(c1 + 1, Lm, E) - _stitch_row_off(c0, Lm, E)) <= _STITCH_ROWS_BUDGET):
+            c1 += 1
+        nrows = _stitch_row_off(c1, Lm, E) - _stitch_row_off(c0, Lm, E)
+        rows = torch.empty(B * nrows, 2 * Fe, device=edges.device, dtype=F32)
+        L.call('gpe_stitch_pairs_rows', edges, ne, B, P, Lm, Fe, sh, sc, c0, c1, nrows, rows)
+        y = dense_mlp(rows, mlp, False)
+        L.call('gpe_stitch_pairs_reduce', y, y.stride(0), ne, B, P, Lm, c0, c1, nrows, table, dense)
+        c0 = c1
+
+
+def stitch_pairs(edges3d, num_edges, mlp, f_shift, f_scale, route='auto', return_logits=False):
+    """Stitches of B garments from the edge-pair classifier `mlp` (net_blocks.MLP([2 Fe, H x n, 1]), eval mode): what the
+    reference does at prediction time with NNSewingPattern.all_edge_pairs + stitches_from_pair_classifier
+    (nn/data/pattern_converter.py:411-499) with the intended indexing of line 432.
+
+    edges3d [B, P, L, Fe] fp32: un-standardised 3D edges per panel slot; num_edges [B, P] int (0 = panel absent); f_shift / f_scale:
+    2 Fe numbers.  -> stitches int32 [B, 2, S] (edge ids panel * L + edge, side 0 = lower panel, ascending (i, j, r, c), zero-padded;
+    S = P * L // 2), num_stitches int32 [B], scores fp32 [B, S] (logits) and, with return_logits, the dense logits [B, P*L, P*L]
+    (NaN where there is no pair).  No host synchronisation.  route: 'fused' (csrc/gpe_stitch_pairs.hip's store-free kernel; ValueError
+    off its menu), 'rows' (materialised rows through the dense-MLP kernels), 'auto' (fused on the menu, rows otherwise)."""
+    if route not in STITCH_PAIRS_ROUTES:
+        raise ValueError('unknown route %r (choose from %s)' % (route, STITCH_PAIRS_ROUTES))
+    if edges3d.dim() != 4:
+        raise ValueError('edges3d must be [B, P, L, Fe] (got %s)' % (tuple(edges3d.shape),))
+    B, P, Lm, Fe = edges3d.shape
+    if P > STITCH_PAIRS_MAX_PANELS or Lm > STITCH_PAIRS_MAX_EDGES or P * Lm < 2 or B < 1:
+        raise ValueError('stitch_pairs handles 1 .. %d panels of 1 .. %d edges (got P = %d, L = %d)'
+                         % (STITCH_PAIRS_MAX_PANELS, STITCH_PAIRS_MAX_EDGES, P, Lm))
+    blocks = [mlp[i] for i in range(len(mlp))]
+    if blocks[0][0].weight.shape[1] != 2 * Fe or len(f_shift) != 2 * Fe or len(f_scale) != 2 * Fe or Fe > 16:
+        raise ValueError('the classifier takes %d features per pair, the statistics have %d / %d, the edges %d each (<= 16)'
+                         % (blocks[0][0].weight.shape[1], len(f_shift), len(f_scale), Fe))
+    if mlp.training:
+        raise RuntimeError('stitch_pairs is a prediction path: call .eval() on the model first (BatchNorm running statistics)')
+    if tuple(num_edges.shape) != (B, P) or num_edges.is_floating_point() or num_edges.device != edges3d.device:
+        raise ValueError('num_edges must be an integer [B, P] tensor on the device of edges3d')
+    on_menu = stitch_pairs_on_menu(mlp)
+    if route == 'fused' and not on_menu:
+        raise ValueError("route='fused' needs 1 - 4 hidden layers of one width <= 256 that is a multiple of 4; use 'auto' or 'rows'")
+    _dev_check(edges3d)
+    fused = on_menu and route != 'rows'
+    dev = edges3d.device
+    E, S = P * Lm, P * Lm // 2
+    shift, scale = [float(v) for v in f_shift], [float(v) for v in f_scale]
+    with torch.no_grad():
+        edges = edges3d.detach().contiguous()
+        ne = num_edges.to(torch.int32).contiguous()
+        table = torch.zeros(B, E, device=dev, dtype=torch.int64)
+        dense = torch.full((B, E, E), float('nan'), device=dev, dtype=F32) if return_logits else None
+        if fused:
+            _stitch_fused(edges, ne, blocks, shift, scale, table, dense)
+        else:
+            _stitch_rows(edges, ne, mlp, shift, scale, table, dense)
+        stitches = torch.empty(B, 2, S, device=dev, dtype=torch.int32)
+        nums = torch.empty(B, device=dev, dtype=torch.int32)
+        scores = torch.empty(B, S, device=dev, dtype=F32)
+        L.call('gpe_stitch_select', table, B, P, Lm, stitches, nums, scores)
+    out = {'stitches': stitches, 'num_stitches': nums, 'scores': scores}
+    if return_logits:
+        out['logits'] = dense
+    return out
+
+
 class SparsemaxLossFn(torch.autograd.Function):
     """entmax.SparsemaxLoss()(x, target) as nn/metrics/composed_loss.py:323-332 calls it: mean over rows of the sparsemax
     Fenchel-Young loss; gradient (sparsemax(x) - onehot(target)) / rows."""

@@ -578,6 +578,61 @@ int gpe_asap_bwd(const float* dout, const float* x, int ldx, int B, int N, int F
                  const float* state, float* dx, int lddx, float* g_wlin, float* g_blin, float* g_watt, float* g_batt, float* g_w1,
                  float* g_b1, float* g_w2, float* g_w3, float* g_b3, void* ws, void* stream);
 
+/* ---- stitch recovery from the edge-pair classifier (StitchOnEdge3DPairs at prediction time: nn/data/pattern_converter.py:411-499
+ * all_edge_pairs + stitches_from_pair_classifier; forward only) ---------------------------------------------------------------------
+ * Added without a version bump (gpe_abi_version() stays 7): six compute entry points, nothing else changes.
+ * Garment b has P panel slots of L edge slots; num_edges int32 [B][P] (clamped to 0 .. L; 0 = panel absent).  Pattern-level edge id
+ * e = panel * L + edge, E = P * L.  Pairs: (panel i, edge r) x (panel j, edge c), i < j, r < num_edges[i], c < num_edges[j]; order
+ * key (i, j, r, c) lexicographic, packed as i << 13 | j << 8 | r << 4 | c.  A pair is positive iff sigmoid(logit) > 0.5 in fp32.
+ * table: caller-owned uint64 [B][E], ZEROED by the caller; every positive pair does a 64-bit atomicMax of
+ *   (bit pattern of its logit) << 32 | ~key   on the entries of both of its edges (positive logits order like their bit patterns, the
+ * complement makes the earlier pair win a tie), so an entry ends as the edge's best pair whatever the arrival order.
+ * logits (may be NULL): fp32 [B][E][E], entry (e_i, e_j) of every valid pair is written, nothing else is touched.
+ * Limits: 1 <= P <= 32, 1 <= L <= 16, 1 <= B <= 65535; anything else returns -22.
+ *
+ * gpe_stitch_pairs_fwd, the fused store-free classifier.  The first Linear is split per edge, W1 [e_i | e_j] + b1 = A_i + Bv_j:
+ *   ab [B*E][ldab] fp32 holds [A | Bv] (2 H columns, 16-B aligned rows; the standardisation folded in; gpe_linear writes it).
+ *   n_layers = Linear layers in front of the output Linear (1 .. 4, all H wide: H <= 256, H % 4 == 0), each followed by ReLU and an
+ *   eval-mode BatchNorm that is folded into the next Linear.  wpk (16-B aligned) holds, with NB = the smallest of {4, 8, 13, 16}
+ *   >= ceil(H / 16) and ldw = 16 NB (+ 16 unless 16 NB % 32 == 16):
+ *     for each of the n_layers - 1 hidden H x H layers: Wt [H][ldw] = gpe_stitch_pairs_pack(w, .., col_scale = s of the BatchNorm
+ *       in front, ldo = ldw), then the folded bias (gpe_fold_bias) in a zero-filled row of ldw floats;
+ *     then the output layer: H floats (gpe_stitch_pairs_pack with N = 1, ldo = 1) and its folded bias (1 float)
+ *   = (n_layers - 1) * (H + 1) * ldw + H + 1 floats.  last_stats [4][1] = gpe_bn_from_running of the output block:
+ *   logit = s * relu(z) + t.  A workgroup classifies 8 x 8 edges (64 pairs) on v_mfma_f32_16x16x4_f32;
+ *   dynamic LDS 4 * (64 * ((H/4 | 1) * 4) + 32 * ldw) bytes.
+ *   f16x3 (gpe_math_set(4), H <= 224, B * E * E / 2 >= gpe_f16x3_min_rows(), planes and w_amax given; otherwise the exact kernel):
+ *   three v_mfma_f32_16x16x32_f16 per product on two-term fp16 splits, fp32 accumulate; the weights are normalised per layer,
+ *   w_amax uint32 [n_layers - 1] = amax words of the hidden layers' Wt (gpe_absmax over [H][ldw]) and planes = per hidden layer
+ *   KP * ldw floats written by gpe_stitch_pairs_planes (KP = H rounded up to 32), 16-B aligned; the activations are normalised per
+ *   wave (32 pair rows) and layer by the maximum found in the accumulators.  A workgroup classifies 8 x 16 edges; dynamic LDS
+ *   4 * (128 * (KP + 8) + 32 * ldw) bytes.  Both may be NULL.  Other modes run the exact kernel.
+ * gpe_stitch_pairs_pack: out[k][n] = w[n][k] * col_scale[k] (col_scale may be NULL) for k < K, n < N, zero for N <= n < ldo.
+ * gpe_stitch_pairs_planes: wt [K][ldw] (a gpe_stitch_pairs_pack output, ldw % 16 == 0) scaled by the power of two of its amax word
+ *   and split in two fp16 terms, in the B-fragment order of v_mfma_f32_16x16x32_f16: per 32-k slab [hi | lo][4][ldw][8 halves].
+ *
+ * The generic route (any MLP): i-edge e = (panel q, edge r) owns the E - (q + 1) L rows of the edge slots of the later panels,
+ * starting at row off(e) = L q E - L^2 q (q + 1) / 2 + r (E - (q + 1) L); a call handles the i-edges [c0, c1) of every garment,
+ * rows_chunk >= off(c1) - off(c0) rows per garment, B * (c1 - c0) <= 65535.
+ * gpe_stitch_pairs_rows writes rows [B][rows_chunk][2 Fe] = ([e_i | e_j] - shift) / scale (HOST arrays of 2 Fe floats, Fe <= 16;
+ *   edges3d fp32 [B][E][Fe] dense), zero rows for edge slots that are not present;
+ * gpe_stitch_pairs_reduce reads the classifier's output y (row pitch ldy) in the same order and applies the epilogue above.
+ *
+ * gpe_stitch_select: a pair survives iff the entries of both of its edges name it.  stitches int32 [B][2][S], S = E / 2: the edge
+ * ids of the survivors (side 0 = lower panel) in ascending order key, zero-padded; num_stitches int32 [B]; scores fp32 [B][S] the
+ * logits.  One workgroup per garment, no atomics on global memory: bit-reproducible. */
+int gpe_stitch_pairs_pack(const float* w, int ldw, int N, int K, const float* col_scale, float* out, int ldo, void* stream);
+int gpe_stitch_pairs_planes(const float* wt, int K, int ldw, const uint32_t* amax, void* out, void* stream);
+int gpe_stitch_pairs_fwd(const float* ab, int ldab, int H, int n_layers, const float* wpk, const void* planes,
+                         const uint32_t* w_amax, const float* last_stats, const int32_t* num_edges, int B, int P, int L,
+                         uint64_t* table, float* logits, void* stream);
+int gpe_stitch_pairs_rows(const float* edges3d, const int32_t* num_edges, int B, int P, int L, int Fe, const float* shift_host,
+                          const float* scale_host, int c0, int c1, long rows_chunk, float* rows, void* stream);
+int gpe_stitch_pairs_reduce(const float* y, long ldy, const int32_t* num_edges, int B, int P, int L, int c0, int c1,
+                            long rows_chunk, uint64_t* table, float* logits, void* stream);
+int gpe_stitch_select(const uint64_t* table, int B, int P, int L, int32_t* stitches, int32_t* num_stitches, float* scores,
+                      void* stream);
+
 
 /* ---- optimizer / input side (nn/trainer.py:162-185; nn/data/transforms.py:35-50) ----------------------------------- */
 /* one torch.optim.Adam step (amsgrad off) over a flat arena of n floats (16-B aligned p, g, m, v); `step` counts from 1;
