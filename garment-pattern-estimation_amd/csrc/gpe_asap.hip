@@ -5,7 +5,7 @@
 // Query branch folded: att_q(lin(x_q)) = u . x_q + s0 with u = W_lin^T w_q, s0 = w_q . b_lin + b_att (no F x F GEMM).
 // All arithmetic is fp32 (weight-gradient sums in fp64), whatever the arithmetic mode of the edge kernels; no atomics anywhere,
 // and every launch grid is a function of (B, N, F) only, so results are bit-identical run to run and across devices.
-#include "gpe_common.h"
+#include "gpe_device.h"
 #include <math.h>
 
 namespace {
@@ -255,7 +255,7 @@ __global__ __launch_bounds__(1024) void asap_select_kernel(int N, int F, int k, 
             if (q != c) pre += S.A[base + q];
         }
         pre = pre - (float)S.deg[base + c] * S.Bv[base + c] + S.L3[base + c];
-        const float fit = 1.f / (1.f + expf(-pre));
+        const float fit = gpe_sigmoid(pre);
         S.fit[base + c] = fit;
         S.L3[base + c] = pre;                // the L3 slot keeps the pre-activation from here on (for the backward)
         rank[base + c] = -1;
@@ -326,7 +326,7 @@ __global__ __launch_bounds__(ASAP_THREADS) void asap_dpre_kernel(const float* __
     a = wave_sum(a);
     // sigmoid' = sigmoid(pre) sigmoid(-pre): no cancellation in 1 - fit where the fitness saturates
     const float pre = S.L3[gc];
-    if (lane == 0) W.dpre[gc] = a * (S.fit[gc] * (1.f / (1.f + expf(pre))));
+    if (lane == 0) W.dpre[gc] = a * (S.fit[gc] * gpe_sigmoid(-pre));
 }
 
 // one wave per target c: G_c = dL/dx'_c, then the attention backward over cluster(c) -> dz per edge, ds_c

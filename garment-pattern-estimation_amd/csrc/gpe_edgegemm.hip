@@ -25,21 +25,18 @@
 // x = hi + lo + O(2^-18 |x|) with hi = bf16(x), lo = bf16(x - hi);  a*b ~= ah*bh + ah*bl + al*bh on the bf16 matrix pipe
 // (v_mfma_f32_16x16x32_bf16, fp32 accumulate): three MFMAs at 16x the fp32-MFMA rate each, AND a bf16 stream leaves the
 // SIMD's other wave free to issue (see the header).  LDS/VGPR footprint is unchanged: 2 x 2 bytes per element.
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef short s16x4_t __attribute__((ext_vector_type(4)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ void eg_split4(const float4 v, uint2& hi, uint2& lo)
 {
-    const f32x2_t a = {v.x, v.y}, b = {v.z, v.w};
-    const unsigned h0 = __builtin_bit_cast(unsigned, __builtin_convertvector(a, bf16x2_t));   // v_cvt_pk_bf16_f32 (RNE)
-    const unsigned h1 = __builtin_bit_cast(unsigned, __builtin_convertvector(b, bf16x2_t));
-    const f32x2_t ra = {v.x - __uint_as_float(h0 << 16), v.y - __uint_as_float(h0 & 0xffff0000u)};
-    const f32x2_t rb = {v.z - __uint_as_float(h1 << 16), v.w - __uint_as_float(h1 & 0xffff0000u)};
+    const gpe_f32x2 a = {v.x, v.y}, b = {v.z, v.w};
+    const unsigned h0 = __builtin_bit_cast(unsigned, __builtin_convertvector(a, gpe_bf16x2));   // v_cvt_pk_bf16_f32 (RNE)
+    const unsigned h1 = __builtin_bit_cast(unsigned, __builtin_convertvector(b, gpe_bf16x2));
+    const gpe_f32x2 ra = {v.x - __uint_as_float(h0 << 16), v.y - __uint_as_float(h0 & 0xffff0000u)};
+    const gpe_f32x2 rb = {v.z - __uint_as_float(h1 << 16), v.w - __uint_as_float(h1 & 0xffff0000u)};
     hi = make_uint2(h0, h1);
-    lo = make_uint2(__builtin_bit_cast(unsigned, __builtin_convertvector(ra, bf16x2_t)),
-                    __builtin_bit_cast(unsigned, __builtin_convertvector(rb, bf16x2_t)));
+    lo = make_uint2(__builtin_bit_cast(unsigned, __builtin_convertvector(ra, gpe_bf16x2)),
+                    __builtin_bit_cast(unsigned, __builtin_convertvector(rb, gpe_bf16x2)));
 }
 
 // One N-tile of the packed weight as bf16x3 B fragments: KCH/2 slabs of 32 k (+ a 16-k tail when KCH is odd).  Slab s of
@@ -80,7 +77,7 @@ __device__ __forceinline__ int eg_kpos(int c)
 
 __device__ __forceinline__ f32x4 eg_mfma32(const uint4 a, const uint4 b, const f32x4 c)
 {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(gpe_bf16x8, a), __builtin_bit_cast(gpe_bf16x8, b), c, 0, 0, 0);
 }
 __device__ __forceinline__ f32x4 eg_mfma16(const uint2 a, const uint2 b, const f32x4 c)
 {

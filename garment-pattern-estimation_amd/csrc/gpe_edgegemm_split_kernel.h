@@ -33,7 +33,6 @@
 #include <stdlib.h>
 #include <string.h>
 
-#define X6_PB 16          // rows a wave stages / finishes per tile
 // scheduling fences around a slot's memory slice: always for the fp32-tile policy.  The two-plane policy runs faster WITHOUT
 // them (its slots hold 6 - 12 short MFMAs: letting the scheduler weave the slice into them, under max-ilp, measured 13.78 ->
 // 13.46 ms per step in one session, scripts/ab_bench.sh); the knob stays for A/B builds.
@@ -41,7 +40,6 @@
 #define X6_PLANES_FENCE 0
 #endif
 #define X6_FENCE(planes) (!(planes) || X6_PLANES_FENCE)
-#define X6_NPW 4          // max points per wave per tile (gather / aggregation paths)
 // default left-over scheme per kernel kind (see the LEFT template parameter), from the A/B of profiles/r04_c_left_schemes.md
 // (us per launch at cfg 2, schemes 0 / 1 / 2): F2 480 / 462 / 448, F3 480 / 516 / 495, B3 518 / 529 / 521, B2 528 / 526 / 517
 #ifndef X6_LEFT_F2
@@ -50,46 +48,6 @@
 #define X6_LEFT_B3 0
 #define X6_LEFT_B2 2
 #endif
-#define GPE_ENOTSUP_SHAPE 12345
-
-// A wave has 256 architectural VGPRs + 256 accumulation VGPRs; MFMA takes its B operand from either file.  The resident
-// weights (208 registers) are pinned in AGPRs by hand: left to itself the allocator keeps them architectural and, in the
-// gather variants, spills them to scratch memory — reloaded every chunk behind an s_waitcnt vmcnt(0).
-__device__ __forceinline__ float x6_pin_agpr(float x)
-{
-    float a;
-    asm volatile("v_accvgpr_write_b32 %0, %1" : "=a"(a) : "v"(x));
-    return a;
-}
-__device__ __forceinline__ float4 x6_UNUSED_pin4(const float4 v)
-{
-    return make_float4(x6_pin_agpr(v.x), x6_pin_agpr(v.y), x6_pin_agpr(v.z), x6_pin_agpr(v.w));
-}
-
-// P row of (pseudo-)point x: x itself, or x / f when a k > 16 point runs as f pseudo-points (RgParams::pmagic, gpe_edgegemm_sr.hip)
-template <bool PSEUDO>
-__device__ __forceinline__ long x6_prow(int x, unsigned pmagic) { return PSEUDO ? (long)__umulhi((unsigned)x, pmagic) : (long)x; }
-
-// Wave-uniform choice among the (<= X6_NPW) P rows of a wave's points.  Arguments BY VALUE and selects on values: written
-// as `if (idx == q) dst = arr_q` the compiler turns the phi of loads into a load through a phi of pointers into the lambda
-// closure, which pins the closure AND every captured local (v[], act[], ...) in scratch memory — each access then drags
-// an s_waitcnt vmcnt(0) through the load pipeline.
-__device__ __forceinline__ float4 x6_sel4(const float4 a0, const float4 a1, const float4 a2, const float4 a3, int idx)
-{
-    float4 r = a0;
-    r.x = (idx == 1) ? a1.x : r.x; r.y = (idx == 1) ? a1.y : r.y; r.z = (idx == 1) ? a1.z : r.z; r.w = (idx == 1) ? a1.w : r.w;
-    r.x = (idx == 2) ? a2.x : r.x; r.y = (idx == 2) ? a2.y : r.y; r.z = (idx == 2) ? a2.z : r.z; r.w = (idx == 2) ? a2.w : r.w;
-    r.x = (idx == 3) ? a3.x : r.x; r.y = (idx == 3) ? a3.y : r.y; r.z = (idx == 3) ? a3.z : r.z; r.w = (idx == 3) ? a3.w : r.w;
-    return r;
-}
-
-typedef __bf16 x6_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 x6_bf16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 x6_f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 x6_f16x2 __attribute__((ext_vector_type(2)));
-typedef float x6_f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned x6_u32x4 __attribute__((ext_vector_type(4)));
-
 // ---- split policies --------------------------------------------------------------------------------------------------------
 // P planes per operand; NPROD plane products per fp32 product, listed small terms first: product t multiplies plane pa(t) of
 // the A fragment with plane pw(t) of the resident weight.
@@ -98,11 +56,7 @@ struct SplitBf16x3 {
     static constexpr bool SCALED = false;
     __device__ static constexpr int pa(int t) { return t == 0 ? 2 : t == 1 ? 0 : t == 2 ? 1 : t == 3 ? 1 : 0; }   // l h m m h h
     __device__ static constexpr int pw(int t) { return t == 0 ? 0 : t == 1 ? 2 : t == 2 ? 1 : t == 3 ? 0 : t == 4 ? 1 : 0; }   // H L M H M H
-    __device__ static __forceinline__ unsigned cvt2(float a, float b)              // {bf16(a) | bf16(b) << 16}, RNE
-    {
-        const x6_f32x2 v = {a, b};
-        return __builtin_bit_cast(unsigned, __builtin_convertvector(v, x6_bf16x2));
-    }
+    __device__ static __forceinline__ unsigned cvt2(float a, float b) { return gpe_cvt2_bf16(a, b); }
     __device__ static __forceinline__ void split2(float a, float b, unsigned (&o)[3])
     {
         o[0] = cvt2(a, b);
@@ -111,9 +65,9 @@ struct SplitBf16x3 {
         const float sa = ra - __uint_as_float(o[1] << 16), sb = rb - __uint_as_float(o[1] & 0xffff0000u);
         o[2] = cvt2(sa, sb);
     }
-    __device__ static __forceinline__ f32x4 mfma(const x6_u32x4 a, const x6_u32x4 b, const f32x4 c)
+    __device__ static __forceinline__ f32x4 mfma(const gpe_u32x4 a, const gpe_u32x4 b, const f32x4 c)
     {
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(x6_bf16x8, a), __builtin_bit_cast(x6_bf16x8, b), c, 0, 0, 0);
+        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(gpe_bf16x8, a), __builtin_bit_cast(gpe_bf16x8, b), c, 0, 0, 0);
     }
 };
 
@@ -122,23 +76,16 @@ struct SplitF16x2 {
     static constexpr bool SCALED = true;
     __device__ static constexpr int pa(int t) { return t == 0 ? 1 : 0; }    // l h h
     __device__ static constexpr int pw(int t) { return t == 1 ? 1 : 0; }    // H L H
-    __device__ static __forceinline__ void split2(float a, float b, unsigned (&o)[2])
+    __device__ static __forceinline__ void split2(float a, float b, unsigned (&o)[2]) { gpe_split2_f16(a, b, o[0], o[1]); }
+    __device__ static __forceinline__ f32x4 mfma(const gpe_u32x4 a, const gpe_u32x4 b, const f32x4 c)
     {
-        const x6_f32x2 v = {a, b};
-        const x6_f16x2 h = __builtin_convertvector(v, x6_f16x2);                   // v_cvt_pk_f16_f32, RNE
-        const x6_f32x2 r = v - __builtin_convertvector(h, x6_f32x2);               // exact in fp32
-        o[0] = __builtin_bit_cast(unsigned, h);
-        o[1] = __builtin_bit_cast(unsigned, __builtin_convertvector(r, x6_f16x2));
-    }
-    __device__ static __forceinline__ f32x4 mfma(const x6_u32x4 a, const x6_u32x4 b, const f32x4 c)
-    {
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(x6_f16x8, a), __builtin_bit_cast(x6_f16x8, b), c, 0, 0, 0);
+        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(gpe_f16x8, a), __builtin_bit_cast(gpe_f16x8, b), c, 0, 0, 0);
     }
     __device__ static __forceinline__ void scale_of(unsigned amax, float& s, float& inv) { gpe_h3_scale_of(amax, s, inv); }
 };
 
 // P-plane split of 8 consecutive k-values of a lane's MFMA operand: f[0..7] -> planes (8 16-bit values each, k order kept)
-template <class SP> struct X6Frag { x6_u32x4 pl[SP::P]; };
+template <class SP> struct X6Frag { gpe_u32x4 pl[SP::P]; };
 
 template <class SP>
 __device__ __forceinline__ X6Frag<SP> x6_split8(const float4 lo, const float4 hi)
@@ -150,12 +97,12 @@ __device__ __forceinline__ X6Frag<SP> x6_split8(const float4 lo, const float4 hi
     SP::split2(hi.z, hi.w, q3);
     X6Frag<SP> f;
 #pragma unroll
-    for (int t = 0; t < SP::P; ++t) f.pl[t] = (x6_u32x4){q0[t], q1[t], q2[t], q3[t]};
+    for (int t = 0; t < SP::P; ++t) f.pl[t] = (gpe_u32x4){q0[t], q1[t], q2[t], q3[t]};
     return f;
 }
 __device__ __forceinline__ float4 x6_scale4(const float4 v, float s) { return make_float4(v.x * s, v.y * s, v.z * s, v.w * s); }
 // keep a resident B fragment in accumulation registers (MFMA reads B from either file)
-__device__ __forceinline__ void x6_pin(x6_u32x4& v) { asm volatile("" : "+a"(v)); }
+__device__ __forceinline__ void x6_pin(gpe_u32x4& v) { asm volatile("" : "+a"(v)); }
 
 // C-tile pitch in floats
 template <class SP> __host__ __device__ constexpr int x6_ldc(int NT, int KCH) { return 16 * NT + 4; }
@@ -219,15 +166,15 @@ __global__ __launch_bounds__(256, 1) void gpe_edgegemm_split_kernel(RgParams p, 
     // enough for the loads to have landed, and BEFORE the epilogue's conditional stores: see gpe_edgegemm_sr.hip); the last
     // slots finish EPR rows of the previous tile each
     constexpr int EPR = (NSLOT >= 28) ? 1 : 2;
-    constexpr int EP_START = NSLOT - X6_PB / EPR;
-    constexpr int CM_SLOTS = 4, CMR = X6_PB / CM_SLOTS;
+    constexpr int EP_START = NSLOT - RG_PB / EPR;
+    constexpr int CM_SLOTS = 4, CMR = RG_PB / CM_SLOTS;
     constexpr int CM_START = EP_START - CM_SLOTS;
     static_assert(CM_START >= 2, "K too short for the slot schedule");
     // The 13 x 13 backward variants of the two-plane policy stage their 16 rows in TWO batches of 8 through the same registers
     // (batch 0: issued in slot 0, committed in slots CM_START, CM_START + 1; batch 1: issued in slot CM_START + 2, committed in
     // the tile's last two slots): 32 staging registers instead of 64, which is what keeps them free of scratch spills.
     constexpr int NH = (SP::SCALED && NT == 13 && KCH == 13 && EMODE != E_EDGE_FWD) ? 2 : 1;
-    constexpr int RBH = X6_PB / NH;
+    constexpr int RBH = RG_PB / NH;
     // ... and load the stored activation of epilogue row u in slot u (the row is finished in slot EP_START + u, 12 slots later)
     // instead of all 16 in slot 0: at most 12 - 13 of them are live at a time.
     // (gathered activations come from the cloud's L2-resident table: 8 slots of lead instead of 12, 9 rows live)
@@ -247,7 +194,7 @@ __global__ __launch_bounds__(256, 1) void gpe_edgegemm_split_kernel(RgParams p, 
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int j = lane & 15, g = lane >> 4;
     const int g_tail = (g >= 2) ? (g & 1) : g;           // ROT: chunk read by a lane of the 16-wide tail slab
-    const int rows_w = p.R >> 2;                         // rows of a tile this wave stages / finishes (<= X6_PB)
+    const int rows_w = p.R >> 2;                         // rows of a tile this wave stages / finishes (<= RG_PB)
     const int rb = wave * rows_w;
     const int rk16 = (65536 + p.k - 1) / p.k;            // u / k == (u * rk16) >> 16 for u < 64
     const int PT = p.R / p.k, npw = PT >> 2;             // points per tile / per wave: first point of this wave's
@@ -268,8 +215,8 @@ __global__ __launch_bounds__(256, 1) void gpe_edgegemm_split_kernel(RgParams p, 
     // ---- weights: resident 16-bit B fragments, SP::P planes -----------------------------------------------------------------
     // lane (j, g) of slab sl holds k = 32 sl + 8 g + {0..7} of column 16*tile + j: two float4 of the packed weight
     // (chunk 2 sl + (g >> 1), k-quads 2 (g & 1) and 2 (g & 1) + 1)
-    x6_u32x4 wP[SP::P][AQ][KS];
-    x6_u32x4 lP[SP::P][BQ > 0 ? BQ : 1][LSL];
+    gpe_u32x4 wP[SP::P][AQ][KS];
+    gpe_u32x4 lP[SP::P][BQ > 0 ? BQ : 1][LSL];
     {
         auto load_frag = [&](int col, int sl) -> X6Frag<SP> {
             const int cc = (col < p.Npad) ? col : p.Npad - 1;
@@ -364,7 +311,7 @@ __global__ __launch_bounds__(256, 1) void gpe_edgegemm_split_kernel(RgParams p, 
     }
     float4 pvs0, pvs1, pvs2, pvs3;                       // P rows of the points being staged (gather)
     pvs0 = pvs1 = pvs2 = pvs3 = make_float4(0.f, 0.f, 0.f, 0.f);
-    float4 act[(EMODE != E_EDGE_FWD) ? X6_PB : 1];       // stored activations of the tile being finished (backward)
+    float4 act[(EMODE != E_EDGE_FWD) ? RG_PB : 1];       // stored activations of the tile being finished (backward)
     float4 pve0, pve1, pve2, pve3;                       // P rows of the points being finished (E_BWD_GATHER)
     pve0 = pve1 = pve2 = pve3 = make_float4(0.f, 0.f, 0.f, 0.f);
     int s_rv = 0;                                        // valid rows of the tile being staged
@@ -425,14 +372,14 @@ __global__ __launch_bounds__(256, 1) void gpe_edgegemm_split_kernel(RgParams p, 
         jgv_cur = jgv_e;
         if (!ACT_LATE) {
 #pragma unroll
-            for (int u = 0; u < X6_PB; ++u) issue_act_load(u);
+            for (int u = 0; u < RG_PB; ++u) issue_act_load(u);
         }
         if (GATHER_ACT) {
             const int pt0 = tile * PT + wave * npw + vz, ptl = tile * PT + ((last * rkl) >> 16);
-            pve0 = ld4(p.pq + x6_prow<PSEUDO>((pt0 + 0 < ptl) ? pt0 + 0 : ptl, p.pmagic) * p.ldpq + cn);
-            pve1 = ld4(p.pq + x6_prow<PSEUDO>((pt0 + 1 < ptl) ? pt0 + 1 : ptl, p.pmagic) * p.ldpq + cn);
-            pve2 = ld4(p.pq + x6_prow<PSEUDO>((pt0 + 2 < ptl) ? pt0 + 2 : ptl, p.pmagic) * p.ldpq + cn);
-            pve3 = ld4(p.pq + x6_prow<PSEUDO>((pt0 + 3 < ptl) ? pt0 + 3 : ptl, p.pmagic) * p.ldpq + cn);
+            pve0 = ld4(p.pq + rg_prow<PSEUDO>((pt0 + 0 < ptl) ? pt0 + 0 : ptl, p.pmagic) * p.ldpq + cn);
+            pve1 = ld4(p.pq + rg_prow<PSEUDO>((pt0 + 1 < ptl) ? pt0 + 1 : ptl, p.pmagic) * p.ldpq + cn);
+            pve2 = ld4(p.pq + rg_prow<PSEUDO>((pt0 + 2 < ptl) ? pt0 + 2 : ptl, p.pmagic) * p.ldpq + cn);
+            pve3 = ld4(p.pq + rg_prow<PSEUDO>((pt0 + 3 < ptl) ? pt0 + 3 : ptl, p.pmagic) * p.ldpq + cn);
         }
     };
     auto issue_stage_loads = [&](int tile, int h) {
@@ -473,10 +420,10 @@ __global__ __launch_bounds__(256, 1) void gpe_edgegemm_split_kernel(RgParams p, 
         }
         if (AMODE == A_GATHER) {
             const int pt0 = tile * PT + wave * npw + vz, ptl = tile * PT + ((last * rkl) >> 16);
-            pvs0 = ld4(p.pq + x6_prow<PSEUDO>((pt0 + 0 < ptl) ? pt0 + 0 : ptl, p.pmagic) * p.ldpq + ck);
-            pvs1 = ld4(p.pq + x6_prow<PSEUDO>((pt0 + 1 < ptl) ? pt0 + 1 : ptl, p.pmagic) * p.ldpq + ck);
-            pvs2 = ld4(p.pq + x6_prow<PSEUDO>((pt0 + 2 < ptl) ? pt0 + 2 : ptl, p.pmagic) * p.ldpq + ck);
-            pvs3 = ld4(p.pq + x6_prow<PSEUDO>((pt0 + 3 < ptl) ? pt0 + 3 : ptl, p.pmagic) * p.ldpq + ck);
+            pvs0 = ld4(p.pq + rg_prow<PSEUDO>((pt0 + 0 < ptl) ? pt0 + 0 : ptl, p.pmagic) * p.ldpq + ck);
+            pvs1 = ld4(p.pq + rg_prow<PSEUDO>((pt0 + 1 < ptl) ? pt0 + 1 : ptl, p.pmagic) * p.ldpq + ck);
+            pvs2 = ld4(p.pq + rg_prow<PSEUDO>((pt0 + 2 < ptl) ? pt0 + 2 : ptl, p.pmagic) * p.ldpq + ck);
+            pvs3 = ld4(p.pq + rg_prow<PSEUDO>((pt0 + 3 < ptl) ? pt0 + 3 : ptl, p.pmagic) * p.ldpq + ck);
         }
     };
     // ---- LDS commit of staged row u (compile-time u) ------------------------------------------------------------------
@@ -485,14 +432,14 @@ __global__ __launch_bounds__(256, 1) void gpe_edgegemm_split_kernel(RgParams p, 
         const int r = rbl + u;
         float4 o = v[u % RBH];
         if (AMODE == A_GATHER) {
-            const float4 pv = K16 ? pvs0 : x6_sel4(pvs0, pvs1, pvs2, pvs3, (u * rkl) >> 16);
+            const float4 pv = K16 ? pvs0 : rg_sel4(pvs0, pvs1, pvs2, pvs3, (u * rkl) >> 16);
             o.x = fmaxf(o.x + pv.x, 0.f); o.y = fmaxf(o.y + pv.y, 0.f);
             o.z = fmaxf(o.z + pv.z, 0.f); o.w = fmaxf(o.w + pv.w, 0.f);
         }
         if constexpr (LAZY) {
             // dz3 of slot u of the wave's point (gpe_dz3_kernel's arithmetic): the message that won the aggregation carries s * g
-            const x6_f32x2 a01 = __builtin_convertvector(__builtin_bit_cast(x6_f16x2, __float_as_uint(o.x)), x6_f32x2);
-            const x6_f32x2 a23 = __builtin_convertvector(__builtin_bit_cast(x6_f16x2, __float_as_uint(o.y)), x6_f32x2);
+            const gpe_f32x2 a01 = __builtin_convertvector(__builtin_bit_cast(gpe_f16x2, __float_as_uint(o.x)), gpe_f32x2);
+            const gpe_f32x2 a23 = __builtin_convertvector(__builtin_bit_cast(gpe_f16x2, __float_as_uint(o.y)), gpe_f32x2);
             const float av[4] = {a01[0], a01[1], a23[0], a23[1]};
             if (u == 0) {                                    // (u is a compile-time constant at every call site) once per tile
                 const float gq[4] = {lz_gq.x, lz_gq.y, lz_gq.z, lz_gq.w};
@@ -543,16 +490,16 @@ __global__ __launch_bounds__(256, 1) void gpe_edgegemm_split_kernel(RgParams p, 
                 // gather variant: the activation rows stream out past L2 so that they do not evict the cloud's Q table
                 // (counter fetch of this kernel 199 -> <145 MB against 109 MB compulsory, same run time: profiles/r02_b)
                 if (AMODE == A_GATHER) {
-                    const x6_u32x4 oq = {__float_as_uint(vv[0]), __float_as_uint(vv[1]), __float_as_uint(vv[2]), __float_as_uint(vv[3])};
+                    const gpe_u32x4 oq = {__float_as_uint(vv[0]), __float_as_uint(vv[1]), __float_as_uint(vv[2]), __float_as_uint(vv[3])};
                     __builtin_amdgcn_raw_buffer_store_b128(oq, orsrc, c * 4, r * p.ldo * 4, 16);
                 } else if constexpr (OUTH) {
                     // fp16 rows (RNE), 8 bytes per quad: the backward only forms dz3 from this tensor (mask + a tiny-coefficient term)
                     // (clamped to the largest finite fp16: an activation beyond 65504 must not become inf in the stored copy — the
                     // backward would turn it into NaN gradients; mx / mn, the statistics and the amax word keep the fp32 value)
-                    const x6_f32x2 v01 = {fminf(vv[0], 65504.f), fminf(vv[1], 65504.f)}, v23 = {fminf(vv[2], 65504.f), fminf(vv[3], 65504.f)};
+                    const gpe_f32x2 v01 = {fminf(vv[0], 65504.f), fminf(vv[1], 65504.f)}, v23 = {fminf(vv[2], 65504.f), fminf(vv[3], 65504.f)};
                     *reinterpret_cast<uint2*>(reinterpret_cast<_Float16*>(p.out) + (e_row0 + r) * p.ldo + c) =
-                        make_uint2(__builtin_bit_cast(unsigned, __builtin_convertvector(v01, x6_f16x2)),
-                                   __builtin_bit_cast(unsigned, __builtin_convertvector(v23, x6_f16x2)));
+                        make_uint2(__builtin_bit_cast(unsigned, __builtin_convertvector(v01, gpe_f16x2)),
+                                   __builtin_bit_cast(unsigned, __builtin_convertvector(v23, gpe_f16x2)));
                 } else st4(p.out + (e_row0 + r) * p.ldo + c, make_float4(vv[0], vv[1], vv[2], vv[3]));
 #pragma unroll
                 for (int t = 0; t < 4; ++t) {
@@ -566,7 +513,7 @@ __global__ __launch_bounds__(256, 1) void gpe_edgegemm_split_kernel(RgParams p, 
             } else {
                 float4 av = act[u];
                 if (GATHER_ACT) {
-                    const float4 pv = K16 ? pve0 : x6_sel4(pve0, pve1, pve2, pve3, (u * rkl) >> 16);
+                    const float4 pv = K16 ? pve0 : rg_sel4(pve0, pve1, pve2, pve3, (u * rkl) >> 16);
                     av.x = fmaxf(av.x + pv.x, 0.f); av.y = fmaxf(av.y + pv.y, 0.f);
                     av.z = fmaxf(av.z + pv.z, 0.f); av.w = fmaxf(av.w + pv.w, 0.f);
                 }
@@ -581,7 +528,7 @@ __global__ __launch_bounds__(256, 1) void gpe_edgegemm_split_kernel(RgParams p, 
                 dp.x += o.x; dp.y += o.y; dp.z += o.z; dp.w += o.w;
             }
         }
-        if (K16 ? (u == X6_PB - 1) : (++es == p.k)) {        // a point is complete (K16: compile-time)
+        if (K16 ? (u == RG_PB - 1) : (++es == p.k)) {        // a point is complete (K16: compile-time)
             if (n_on) {
                 const long gpt = e_pt0 + (K16 ? 0 : ept);
                 if constexpr (TRACK && SP::SCALED) amax_run = fmaxf(fmaxf(amax_run, fmaxf(vmx[0], vmx[1])), fmaxf(vmx[2], vmx[3]));
@@ -670,7 +617,7 @@ __global__ __launch_bounds__(256, 1) void gpe_edgegemm_split_kernel(RgParams p, 
                 const int ge = (KTAIL && slr == KS - 1) ? g_tail : g;
                 const char* src = reinterpret_cast<const char*>(As) + (16 * mt + j) * PPITCH + 16 * (4 * slr + ge);
 #pragma unroll
-                for (int t = 0; t < SP::P; ++t) nf.pl[t] = *reinterpret_cast<const x6_u32x4*>(src + t * PLANE);
+                for (int t = 0; t < SP::P; ++t) nf.pl[t] = *reinterpret_cast<const gpe_u32x4*>(src + t * PLANE);
                 return;
             }
             const bool dead = KTAIL && sl == KS - 1 && g >= 2;
@@ -678,8 +625,8 @@ __global__ __launch_bounds__(256, 1) void gpe_edgegemm_split_kernel(RgParams p, 
                 const char* src = reinterpret_cast<const char*>(As) + (16 * mt + j) * PPITCH + 16 * (4 * sl + (dead ? (g & 1) : g));
 #pragma unroll
                 for (int t = 0; t < SP::P; ++t) {
-                    nf.pl[t] = *reinterpret_cast<const x6_u32x4*>(src + t * PLANE);
-                    if (dead) nf.pl[t] = (x6_u32x4){0u, 0u, 0u, 0u};
+                    nf.pl[t] = *reinterpret_cast<const gpe_u32x4*>(src + t * PLANE);
+                    if (dead) nf.pl[t] = (gpe_u32x4){0u, 0u, 0u, 0u};
                 }
             } else {
                 const float* src = &As[(16 * mt + j) * LDA + 32 * sl + 8 * (dead ? (g & 1) : g)];
@@ -707,13 +654,13 @@ __global__ __launch_bounds__(256, 1) void gpe_edgegemm_split_kernel(RgParams p, 
                     if (GATHER_ACT) jgv_e = load_jgv(tile);              // this tile is finished in the next iteration
                     if (AMODE == A_GATHER) jgv_s = load_jgv(next2 < p.num_tiles ? next2 : tile);
                 }
-                if (ACT_LATE && EMODE != E_EDGE_FWD && q >= ACT_SHIFT && q < X6_PB + ACT_SHIFT) issue_act_load(q - ACT_SHIFT);
+                if (ACT_LATE && EMODE != E_EDGE_FWD && q >= ACT_SHIFT && q < RG_PB + ACT_SHIFT) issue_act_load(q - ACT_SHIFT);
                 if (NH == 1 && q >= CM_START && q < EP_START) {
                     if (do_stage) {
 #pragma unroll
                         for (int c4 = 0; c4 < CMR; ++c4) {
                             const int u = (q - CM_START) * CMR + c4;
-                            if (u < X6_PB) commit_row(An, u);
+                            if (u < RG_PB) commit_row(An, u);
                         }
                     }
                 }
@@ -733,7 +680,7 @@ __global__ __launch_bounds__(256, 1) void gpe_edgegemm_split_kernel(RgParams p, 
 #pragma unroll
                         for (int e2 = 0; e2 < EPR; ++e2) {
                             const int u = (q - EP_START) * EPR + e2;
-                            if (u < X6_PB) epi_row(u, zq[e2]);
+                            if (u < RG_PB) epi_row(u, zq[e2]);
                         }
                     }
                 }
@@ -741,7 +688,7 @@ __global__ __launch_bounds__(256, 1) void gpe_edgegemm_split_kernel(RgParams p, 
 #pragma unroll
                     for (int e2 = 0; e2 < EPR; ++e2) {
                         const int u = (q + 1 - EP_START) * EPR + e2;
-                        const int rr = rbl + ((u < X6_PB) ? u : X6_PB - 1);
+                        const int rr = rbl + ((u < RG_PB) ? u : RG_PB - 1);
                         zq[e2] = ld4(&Cs[((rr < RG_BM) ? rr : RG_BM - 1) * LDC + cn]);
                     }
                 }
@@ -784,7 +731,7 @@ __global__ __launch_bounds__(256, 1) void gpe_edgegemm_split_kernel(RgParams p, 
                 for (int mt = 0; mt < 4; ++mt) {
                     X6Frag<SP> lf;
 #pragma unroll
-                    for (int t = 0; t < SP::P; ++t) lf.pl[t] = *reinterpret_cast<const x6_u32x4*>(base + 16 * mt * PPITCH + t * PLANE);
+                    for (int t = 0; t < SP::P; ++t) lf.pl[t] = *reinterpret_cast<const gpe_u32x4*>(base + 16 * mt * PPITCH + t * PLANE);
 #pragma unroll
                     for (int t = 0; t < SP::NPROD; ++t)
 #pragma unroll
@@ -839,10 +786,10 @@ __global__ __launch_bounds__(256, 1) void gpe_edgegemm_split_kernel(RgParams p, 
         issue_epi_loads(prev);
         if (ACT_LATE) {
 #pragma unroll
-            for (int u = 0; u < X6_PB; ++u) issue_act_load(u);
+            for (int u = 0; u < RG_PB; ++u) issue_act_load(u);
         }
 #pragma unroll
-        for (int u = 0; u < X6_PB; ++u) {
+        for (int u = 0; u < RG_PB; ++u) {
             const int rr = rbl + u;
             epi_row(u, ld4(&Cs[((rr < RG_BM) ? rr : RG_BM - 1) * LDC + cn]));
         }
@@ -986,8 +933,8 @@ static int x6_prepare(const RgParams& p_in, int amode, int emode, int stats_nblk
     // k > 16: rows that need nothing per point are tiled 4 rows per "point"; the per-point variants run a point as f pseudo-points
     // of <= 16 rows whose results are folded afterwards (gpe_edge_pseudo_setup / _fold, gpe_edgegemm_sr.hip)
     if (!gpe_edge_pseudo_setup(p, per_point, emode, fold)) return 0;
-    const int npw = X6_PB / p.k;                         // points per wave per tile
-    if (per_point && npw > X6_NPW) return 0;
+    const int npw = RG_PB / p.k;                         // points per wave per tile
+    if (per_point && npw > RG_NPW) return 0;
     p.R = 4 * npw * p.k;
     p.num_tiles = gpe_cdiv(p.M, p.R);
     p.pin_tpc = 0;

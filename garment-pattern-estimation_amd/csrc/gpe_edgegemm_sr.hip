@@ -80,12 +80,12 @@ int gpe_edge_pseudo_setup(RgParams& p, bool per_point, int emode, GpeFold& fd)
 {
     fd = GpeFold{};
     fd.f = 1;
-    if (p.k <= SR_PB) return 1;
+    if (p.k <= RG_PB) return 1;
     if (!per_point) { p.k = 4; return 1; }
     const long npts = p.M / p.k;
     int best = 0;
-    for (int kq = SR_PB; kq >= SR_PB / SR_NPW; --kq)
-        if (p.k % kq == 0 && (SR_PB / kq) * kq > (best ? (SR_PB / best) * best : 0)) best = kq;
+    for (int kq = RG_PB; kq >= RG_PB / RG_NPW; --kq)
+        if (p.k % kq == 0 && (RG_PB / kq) * kq > (best ? (RG_PB / best) * best : 0)) best = kq;
     if (!best || npts * (p.k / best) >= (1L << 31) || (p.oldagg & 3) || (p.lddp & 3)) return 0;
     fd.f = p.k / best; fd.kq = best; fd.npts = npts;
     const long nps = npts * fd.f;                                     // pseudo-points
@@ -108,10 +108,10 @@ int gpe_edge_pseudo_setup(RgParams& p, bool per_point, int emode, GpeFold& fd)
 // bytes of the pseudo-point part of an edge workspace for k neighbours, widths <= Cmax (0 for k <= 16)
 size_t gpe_edge_pseudo_bytes(long npts, int k, int Cmax)
 {
-    if (k <= SR_PB) return 0;
+    if (k <= RG_PB) return 0;
     int best = 0;
-    for (int kq = SR_PB; kq >= SR_PB / SR_NPW; --kq)
-        if (k % kq == 0 && (SR_PB / kq) * kq > (best ? (SR_PB / best) * best : 0)) best = kq;
+    for (int kq = RG_PB; kq >= RG_PB / RG_NPW; --kq)
+        if (k % kq == 0 && (RG_PB / kq) * kq > (best ? (RG_PB / best) * best : 0)) best = kq;
     if (!best) return 0;
     const size_t nps = (size_t)npts * (k / best), ld = (size_t)((Cmax + 3) & ~3);
     // forward with aggregation: mx, mn (floats) + amx, amn (bytes); gathered backward: dP (floats) — the larger of the two
@@ -154,8 +154,8 @@ int gpe_edgegemm_sr_try(const RgParams& p_in, int amode, int emode, int stats_nb
     // variants split a point into f pseudo-points of kq rows and fold the per-pseudo-point results afterwards
     GpeFold fold;
     if (!gpe_edge_pseudo_setup(p, per_point, emode, fold)) return 0;
-    const int npw = SR_PB / p.k;                         // points per wave per tile
-    if (per_point && npw > SR_NPW) return 0;
+    const int npw = RG_PB / p.k;                         // points per wave per tile
+    if (per_point && npw > RG_NPW) return 0;
     p.R = 4 * npw * p.k;
     p.num_tiles = gpe_cdiv(p.M, p.R);
     p.pin_tpc = 0;

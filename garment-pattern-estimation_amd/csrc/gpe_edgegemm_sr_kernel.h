@@ -8,43 +8,6 @@
 #include "gpe_rowgemm.h"
 #include <math.h>
 
-#define SR_PB 16          // rows a wave stages / finishes per tile
-#define SR_NPW 4          // max points per wave per tile (gather / aggregation paths)
-#define GPE_ENOTSUP_SHAPE 12345
-
-// A wave has 256 architectural VGPRs + 256 accumulation VGPRs; MFMA takes its B operand from either file.  The resident
-// weights (208 registers) are pinned in AGPRs by hand: left to itself the allocator keeps them architectural and, in the
-// gather variants, spills them to scratch memory — reloaded every chunk behind an s_waitcnt vmcnt(0).
-__device__ __forceinline__ float sr_pin_agpr(float x)
-{
-    float a;
-    asm volatile("v_accvgpr_write_b32 %0, %1" : "=a"(a) : "v"(x));
-    return a;
-}
-__device__ __forceinline__ float4 sr_pin_agpr4(const float4 v)
-{
-    return make_float4(sr_pin_agpr(v.x), sr_pin_agpr(v.y), sr_pin_agpr(v.z), sr_pin_agpr(v.w));
-}
-
-// Wave-uniform choice among the (<= SR_NPW) P rows of a wave's points.  Arguments BY VALUE and selects on values: written
-// as `if (idx == q) dst = arr_q` the compiler turns the phi of loads into a load through a phi of pointers into the lambda
-// closure, which pins the closure AND every captured local (v[], act[], ...) in scratch memory — each access then drags
-// an s_waitcnt vmcnt(0) through the load pipeline.
-__device__ __forceinline__ float4 sr_sel4(const float4 a0, const float4 a1, const float4 a2, const float4 a3, int idx)
-{
-    float4 r = a0;
-    r.x = (idx == 1) ? a1.x : r.x; r.y = (idx == 1) ? a1.y : r.y; r.z = (idx == 1) ? a1.z : r.z; r.w = (idx == 1) ? a1.w : r.w;
-    r.x = (idx == 2) ? a2.x : r.x; r.y = (idx == 2) ? a2.y : r.y; r.z = (idx == 2) ? a2.z : r.z; r.w = (idx == 2) ? a2.w : r.w;
-    r.x = (idx == 3) ? a3.x : r.x; r.y = (idx == 3) ? a3.y : r.y; r.z = (idx == 3) ? a3.z : r.z; r.w = (idx == 3) ? a3.w : r.w;
-    return r;
-}
-
-// row of the [P|Q] table that belongs to (pseudo-)point x: x itself, or x / f when a point is split into f pseudo-points
-__device__ __forceinline__ long sr_prow(int x, unsigned magic)
-{
-    return magic ? (long)__umulhi((unsigned)x, magic) : (long)x;
-}
-
 // K16: k == 16 (the benchmark configuration): every wave owns exactly ONE point per tile, so the slot index of a row is
 // its compile-time position u, a point completes exactly at u == 15, and row validity is one per-tile predicate — the
 // per-row bookkeeping (and the register copies its branches cost) disappears from the epilogue.
@@ -77,9 +40,9 @@ __global__ __launch_bounds__(256, 1) void gpe_edgegemm_sr_kernel(RgParams p, int
     // and retires in order), ~1-2 us of HBM write latency per tile.
     constexpr int CM_START = 2;
     constexpr int CM_CH = (KCH >= 13) ? 4 : 3;
-    constexpr int CMC = (SR_PB + CM_CH - 1) / CM_CH;
+    constexpr int CMC = (RG_PB + CM_CH - 1) / CM_CH;
     constexpr int EPC = (KCH >= 13) ? 2 : 3;
-    constexpr int EP_CH = (SR_PB + EPC - 1) / EPC;
+    constexpr int EP_CH = (RG_PB + EPC - 1) / EPC;
     constexpr int EP_START = KCH - EP_CH;
     static_assert(EP_START >= 2, "K too short for the chunk schedule");
     constexpr bool GATHER_ACT = (EMODE == E_BWD_GATHER);
@@ -92,7 +55,7 @@ __global__ __launch_bounds__(256, 1) void gpe_edgegemm_sr_kernel(RgParams p, int
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int j = lane & 15, g = lane >> 4;
-    const int rows_w = p.R >> 2;                         // rows of a tile this wave stages / finishes (<= SR_PB)
+    const int rows_w = p.R >> 2;                         // rows of a tile this wave stages / finishes (<= RG_PB)
     const int rb = wave * rows_w;
     const int rk16 = (65536 + p.k - 1) / p.k;            // u / k == (u * rk16) >> 16 for u < 64
     const int PT = p.R / p.k, npw = PT >> 2;             // points per tile / per wave: first point of this wave's
@@ -128,7 +91,7 @@ __global__ __launch_bounds__(256, 1) void gpe_edgegemm_sr_kernel(RgParams p, int
             }
 #pragma unroll
             for (int kc = 0; kc < KCH; ++kc)
-                dst[kc] = sr_pin_agpr4((col < p.Npad) ? t[kc] : make_float4(0.f, 0.f, 0.f, 0.f));
+                dst[kc] = rg_pin_agpr4((col < p.Npad) ? t[kc] : make_float4(0.f, 0.f, 0.f, 0.f));
         };
 #pragma unroll
         for (int i = 0; i < AQ; ++i) load_tile(16 * (AQ * wave + i) + j, wA[i]);
@@ -165,10 +128,10 @@ __global__ __launch_bounds__(256, 1) void gpe_edgegemm_sr_kernel(RgParams p, int
     float *e_mx = p.mx, *e_mn = p.mn, *e_dp = p.dP;      // the wave's point of the tile
     uint8_t *e_amx = p.oamx, *e_amn = p.oamn;
 
-    float4 v[SR_PB];                                     // rows staged for the next tile
+    float4 v[RG_PB];                                     // rows staged for the next tile
     float4 pvs0, pvs1, pvs2, pvs3;                       // P rows of the points being staged (gather)
     pvs0 = pvs1 = pvs2 = pvs3 = make_float4(0.f, 0.f, 0.f, 0.f);
-    float4 act[(EMODE != E_EDGE_FWD) ? SR_PB : 1];       // stored activations of the tile being finished (backward)
+    float4 act[(EMODE != E_EDGE_FWD) ? RG_PB : 1];       // stored activations of the tile being finished (backward)
     float4 pve0, pve1, pve2, pve3;                       // P rows of the points being finished (E_BWD_GATHER)
     pve0 = pve1 = pve2 = pve3 = make_float4(0.f, 0.f, 0.f, 0.f);
     int s_rv = 0;                                        // valid rows of the tile being staged
@@ -224,7 +187,7 @@ __global__ __launch_bounds__(256, 1) void gpe_edgegemm_sr_kernel(RgParams p, int
         // branch needs a copy at the join, and that copy waits for the load right there — no pipelining left
         const int last = e_rv - 1;
 #pragma unroll
-        for (int u = 0; u < SR_PB; ++u) {
+        for (int u = 0; u < RG_PB; ++u) {
             int r = rbl + ((u < rwl) ? u : rwl - 1);
             r = (r < last) ? r : last;                                  // clamp: unconditional loads
             if (EMODE == E_BWD_INPLACE) act[u] = ld4(p.out + (e_row0 + r) * p.ldo + cn);
@@ -235,10 +198,10 @@ __global__ __launch_bounds__(256, 1) void gpe_edgegemm_sr_kernel(RgParams p, int
         }
         if (GATHER_ACT) {
             const int pt0 = tile * PT + wave * npw + vz, ptl = tile * PT + ((last * rkl) >> 16);
-            pve0 = ld4(p.pq + sr_prow((pt0 + 0 < ptl) ? pt0 + 0 : ptl, p.pmagic) * p.ldpq + cn);
-            pve1 = ld4(p.pq + sr_prow((pt0 + 1 < ptl) ? pt0 + 1 : ptl, p.pmagic) * p.ldpq + cn);
-            pve2 = ld4(p.pq + sr_prow((pt0 + 2 < ptl) ? pt0 + 2 : ptl, p.pmagic) * p.ldpq + cn);
-            pve3 = ld4(p.pq + sr_prow((pt0 + 3 < ptl) ? pt0 + 3 : ptl, p.pmagic) * p.ldpq + cn);
+            pve0 = ld4(p.pq + rg_prow((pt0 + 0 < ptl) ? pt0 + 0 : ptl, p.pmagic) * p.ldpq + cn);
+            pve1 = ld4(p.pq + rg_prow((pt0 + 1 < ptl) ? pt0 + 1 : ptl, p.pmagic) * p.ldpq + cn);
+            pve2 = ld4(p.pq + rg_prow((pt0 + 2 < ptl) ? pt0 + 2 : ptl, p.pmagic) * p.ldpq + cn);
+            pve3 = ld4(p.pq + rg_prow((pt0 + 3 < ptl) ? pt0 + 3 : ptl, p.pmagic) * p.ldpq + cn);
         }
     };
     auto issue_stage_loads = [&](int tile) {
@@ -246,7 +209,7 @@ __global__ __launch_bounds__(256, 1) void gpe_edgegemm_sr_kernel(RgParams p, int
         s_rv = (int)((p.M - row0 < p.R) ? (p.M - row0) : p.R);
         const int last = s_rv - 1;
 #pragma unroll
-        for (int u = 0; u < SR_PB; ++u) {
+        for (int u = 0; u < RG_PB; ++u) {
             int r = rbl + ((u < rwl) ? u : rwl - 1);
             r = (r < last) ? r : last;
             if (AMODE == A_GATHER) {
@@ -259,10 +222,10 @@ __global__ __launch_bounds__(256, 1) void gpe_edgegemm_sr_kernel(RgParams p, int
         }
         if (AMODE == A_GATHER) {
             const int pt0 = tile * PT + wave * npw + vz, ptl = tile * PT + ((last * rkl) >> 16);
-            pvs0 = ld4(p.pq + sr_prow((pt0 + 0 < ptl) ? pt0 + 0 : ptl, p.pmagic) * p.ldpq + ck);
-            pvs1 = ld4(p.pq + sr_prow((pt0 + 1 < ptl) ? pt0 + 1 : ptl, p.pmagic) * p.ldpq + ck);
-            pvs2 = ld4(p.pq + sr_prow((pt0 + 2 < ptl) ? pt0 + 2 : ptl, p.pmagic) * p.ldpq + ck);
-            pvs3 = ld4(p.pq + sr_prow((pt0 + 3 < ptl) ? pt0 + 3 : ptl, p.pmagic) * p.ldpq + ck);
+            pvs0 = ld4(p.pq + rg_prow((pt0 + 0 < ptl) ? pt0 + 0 : ptl, p.pmagic) * p.ldpq + ck);
+            pvs1 = ld4(p.pq + rg_prow((pt0 + 1 < ptl) ? pt0 + 1 : ptl, p.pmagic) * p.ldpq + ck);
+            pvs2 = ld4(p.pq + rg_prow((pt0 + 2 < ptl) ? pt0 + 2 : ptl, p.pmagic) * p.ldpq + ck);
+            pvs3 = ld4(p.pq + rg_prow((pt0 + 3 < ptl) ? pt0 + 3 : ptl, p.pmagic) * p.ldpq + ck);
         }
     };
     // ---- LDS commit of staged row u (compile-time u) ------------------------------------------------------------------
@@ -272,7 +235,7 @@ __global__ __launch_bounds__(256, 1) void gpe_edgegemm_sr_kernel(RgParams p, int
         float4 o = v[u];
         if (AMODE == A_GATHER) {
             const float4 pv = K16 ? pvs0 : (KC == 4) ? ((u >> 2) == 0 ? pvs0 : (u >> 2) == 1 ? pvs1 : (u >> 2) == 2 ? pvs2 : pvs3)
-                                                     : sr_sel4(pvs0, pvs1, pvs2, pvs3, (u * rkl) >> 16);
+                                                     : rg_sel4(pvs0, pvs1, pvs2, pvs3, (u * rkl) >> 16);
             o.x = fmaxf(o.x + pv.x, 0.f); o.y = fmaxf(o.y + pv.y, 0.f);
             o.z = fmaxf(o.z + pv.z, 0.f); o.w = fmaxf(o.w + pv.w, 0.f);
         }
@@ -314,7 +277,7 @@ __global__ __launch_bounds__(256, 1) void gpe_edgegemm_sr_kernel(RgParams p, int
                 float4 av = act[u];
                 if (GATHER_ACT) {
                     const float4 pv = K16 ? pve0 : (KC == 4) ? ((u >> 2) == 0 ? pve0 : (u >> 2) == 1 ? pve1 : (u >> 2) == 2 ? pve2 : pve3)
-                                                             : sr_sel4(pve0, pve1, pve2, pve3, (u * rkl) >> 16);
+                                                             : rg_sel4(pve0, pve1, pve2, pve3, (u * rkl) >> 16);
                     av.x = fmaxf(av.x + pv.x, 0.f); av.y = fmaxf(av.y + pv.y, 0.f);
                     av.z = fmaxf(av.z + pv.z, 0.f); av.w = fmaxf(av.w + pv.w, 0.f);
                 }
@@ -388,7 +351,7 @@ __global__ __launch_bounds__(256, 1) void gpe_edgegemm_sr_kernel(RgParams p, int
     if (tile < p.num_tiles && !(p.dbg & 1)) {
         issue_stage_loads(tile);
 #pragma unroll
-        for (int u = 0; u < SR_PB; ++u) commit_row(Abuf0, u);
+        for (int u = 0; u < RG_PB; ++u) commit_row(Abuf0, u);
     }
     if (AMODE == A_GATHER && tile < p.num_tiles) jgv_s = load_jgv(next < p.num_tiles ? next : tile);
     __syncthreads();
@@ -452,7 +415,7 @@ __global__ __launch_bounds__(256, 1) void gpe_edgegemm_sr_kernel(RgParams p, int
 #pragma unroll
                     for (int q = 0; q < CMC; ++q) {
                         const int u = (kc - CM_START) * CMC + q;
-                        if (u < SR_PB) commit_row(An, u);
+                        if (u < RG_PB) commit_row(An, u);
                     }
                 }
             }
@@ -461,7 +424,7 @@ __global__ __launch_bounds__(256, 1) void gpe_edgegemm_sr_kernel(RgParams p, int
 #pragma unroll
                     for (int q = 0; q < EPC; ++q) {
                         const int u = (kc - EP_START) * EPC + q;
-                        if (u < SR_PB) epi_row(u, zq[q]);
+                        if (u < RG_PB) epi_row(u, zq[q]);
                     }
                 }
             }
@@ -469,7 +432,7 @@ __global__ __launch_bounds__(256, 1) void gpe_edgegemm_sr_kernel(RgParams p, int
 #pragma unroll
                 for (int q = 0; q < EPC; ++q) {
                     const int u = (kc + 1 - EP_START) * EPC + q;
-                    const int rr = rbl + ((u < SR_PB) ? u : SR_PB - 1);
+                    const int rr = rbl + ((u < RG_PB) ? u : RG_PB - 1);
                     zq[q] = ld4(&Cs[((rr < RG_BM) ? rr : RG_BM - 1) * LDC + cn]);
                 }
             }
@@ -520,7 +483,7 @@ __global__ __launch_bounds__(256, 1) void gpe_edgegemm_sr_kernel(RgParams p, int
     if (prev >= 0 && !(p.dbg & 2)) {
         issue_epi_loads(prev, true);
 #pragma unroll
-        for (int u = 0; u < SR_PB; ++u) {
+        for (int u = 0; u < RG_PB; ++u) {
             const int rr = rbl + u;
             epi_row(u, ld4(&Cs[((rr < RG_BM) ? rr : RG_BM - 1) * LDC + cn]));
         }

@@ -31,7 +31,6 @@
 #ifndef W8_SLOT_FENCE
 #define W8_SLOT_FENCE 1
 #endif
-typedef unsigned w8_u32x2 __attribute__((ext_vector_type(2)));
 // keeps a loaded quad (and therefore its load) in front of this point: see the finisher's epilogue
 #ifndef W8_B2_SC1
 #define W8_B2_SC1 1
@@ -147,7 +146,7 @@ __global__ __launch_bounds__(512) void gpe_edgegemm_w8_kernel(RgParams p, int st
 
     // ---- weights: resident fp16 B fragments, two planes -------------------------------------------------------------------
     // lane (j, g) of slab sl holds k = 32 sl + 8 g + {0..7} of column 16 * tile + j (see gpe_edgegemm_split_kernel.h)
-    x6_u32x4 wP[2][KS], sP[2][SL2], tP[2];
+    gpe_u32x4 wP[2][KS], sP[2][SL2], tP[2];
     {
         auto load_frag = [&](int col, int sl) -> X6Frag<SP> {
             const int cc = (col < p.Npad) ? col : p.Npad - 1;
@@ -343,8 +342,8 @@ __global__ __launch_bounds__(512) void gpe_edgegemm_w8_kernel(RgParams p, int st
             }
             if constexpr (LAZY) {
                 // dz3 of slot u of the wave's point (gpe_dz3_kernel's arithmetic): the message that won the aggregation carries s * g
-                const x6_f32x2 a01 = __builtin_convertvector(__builtin_bit_cast(x6_f16x2, __float_as_uint(o.x)), x6_f32x2);
-                const x6_f32x2 a23 = __builtin_convertvector(__builtin_bit_cast(x6_f16x2, __float_as_uint(o.y)), x6_f32x2);
+                const gpe_f32x2 a01 = __builtin_convertvector(__builtin_bit_cast(gpe_f16x2, __float_as_uint(o.x)), gpe_f32x2);
+                const gpe_f32x2 a23 = __builtin_convertvector(__builtin_bit_cast(gpe_f16x2, __float_as_uint(o.y)), gpe_f32x2);
                 const float av[4] = {a01[0], a01[1], a23[0], a23[1]};
                 if (u == 0) {                            // (u is a compile-time constant at every call site) once per tile
                     const float gq[4] = {lz_gq.x, lz_gq.y, lz_gq.z, lz_gq.w};
@@ -445,15 +444,15 @@ __global__ __launch_bounds__(512) void gpe_edgegemm_w8_kernel(RgParams p, int st
                 if constexpr (!TRACK) amax_t = fmaxf(fmaxf(amax_t, fmaxf(vv[0], vv[1])), fmaxf(vv[2], vv[3]));
                 if constexpr (OUTH) {
                     // fp16 rows (RNE), clamped to the largest finite fp16 (gpe_edgegemm_split_kernel.h)
-                    const x6_f32x2 v01 = {fminf(vv[0], 65504.f), fminf(vv[1], 65504.f)}, v23 = {fminf(vv[2], 65504.f), fminf(vv[3], 65504.f)};
-                    const w8_u32x2 hq = {__builtin_bit_cast(unsigned, __builtin_convertvector(v01, x6_f16x2)),
-                                         __builtin_bit_cast(unsigned, __builtin_convertvector(v23, x6_f16x2))};
+                    const gpe_f32x2 v01 = {fminf(vv[0], 65504.f), fminf(vv[1], 65504.f)}, v23 = {fminf(vv[2], 65504.f), fminf(vv[3], 65504.f)};
+                    const gpe_u32x2 hq = {__builtin_bit_cast(unsigned, __builtin_convertvector(v01, gpe_f16x2)),
+                                         __builtin_bit_cast(unsigned, __builtin_convertvector(v23, gpe_f16x2))};
                     if constexpr ((W8_BUFSTORE & 2) != 0)
                         __builtin_amdgcn_raw_buffer_store_b64(hq, orsrc, cn * 2, r * p.ldo * 2, 0);
                     else
                         *reinterpret_cast<uint2*>(reinterpret_cast<_Float16*>(p.out) + (e_row0 + r) * p.ldo + cn) = make_uint2(hq[0], hq[1]);
                 } else {
-                    const x6_u32x4 oq = {__float_as_uint(vv[0]), __float_as_uint(vv[1]), __float_as_uint(vv[2]), __float_as_uint(vv[3])};
+                    const gpe_u32x4 oq = {__float_as_uint(vv[0]), __float_as_uint(vv[1]), __float_as_uint(vv[2]), __float_as_uint(vv[3])};
                     // gather variant: the activation rows stream out past L2 (sc1) so that they do not evict the cloud's Q table
                     if constexpr ((W8_BUFSTORE & (AMODE == A_GATHER ? 1 : 2)) != 0)
                         __builtin_amdgcn_raw_buffer_store_b128(oq, orsrc, cn * 4, r * p.ldo * 4, AMODE == A_GATHER ? 16 : 0);
@@ -481,7 +480,7 @@ __global__ __launch_bounds__(512) void gpe_edgegemm_w8_kernel(RgParams p, int st
                 o.y = (av.y > 0.f) ? __builtin_fmaf(z.y, cs4.y, __builtin_fmaf(k24.y, av.y, c14.y)) : 0.f;
                 o.z = (av.z > 0.f) ? __builtin_fmaf(z.z, cs4.z, __builtin_fmaf(k24.z, av.z, c14.z)) : 0.f;
                 o.w = (av.w > 0.f) ? __builtin_fmaf(z.w, cs4.w, __builtin_fmaf(k24.w, av.w, c14.w)) : 0.f;
-                const x6_u32x4 oq = {__float_as_uint(o.x), __float_as_uint(o.y), __float_as_uint(o.z), __float_as_uint(o.w)};
+                const gpe_u32x4 oq = {__float_as_uint(o.x), __float_as_uint(o.y), __float_as_uint(o.z), __float_as_uint(o.w)};
                 // (gathered backward: sc1 like the gather forward — its dz rows are read by another kernel much later, and kept in L2 they
                 // evict the cloud's Q table this kernel's epilogue keeps re-reading: round 3 measured 1122 -> 974 MB fetched per launch
                 // for that change but lost 6 % to the `asm volatile` store it needed then)
@@ -563,8 +562,8 @@ __global__ __launch_bounds__(512) void gpe_edgegemm_w8_kernel(RgParams p, int st
                 const int slr = (rot + i >= KS) ? rot + i - KS : rot + i;
                 const int ge = (KTAIL && slr == KS - 1) ? g_tail : g;
                 const char* src = reinterpret_cast<const char*>(As) + (16 * mt + j) * PPITCH + 16 * (4 * slr + ge);
-                nf.pl[0] = *reinterpret_cast<const x6_u32x4*>(src);
-                nf.pl[1] = *reinterpret_cast<const x6_u32x4*>(src + PLANE);
+                nf.pl[0] = *reinterpret_cast<const gpe_u32x4*>(src);
+                nf.pl[1] = *reinterpret_cast<const gpe_u32x4*>(src + PLANE);
             };
             float4 zq = zero4;
             read_frag(0, 0);

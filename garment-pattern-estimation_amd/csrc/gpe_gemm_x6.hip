@@ -48,21 +48,21 @@ __device__ __forceinline__ int gx_slot(int row, int kg) { return kg ^ ((row >> 2
 // lie the three other row tiles
 __device__ __forceinline__ void gx_compute(const char* Ab, const char* Bb, int wm, int wn, int j, int g, f32x4 (&acc)[4][4])
 {
-    x6_u32x4 a[4][3];
+    gpe_u32x4 a[4][3];
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
         const int ra = 64 * wm + 16 * t + j;
         const char* pa = Ab + ra * 64 + 16 * gx_slot(ra, g);
 #pragma unroll
-        for (int pl = 0; pl < 3; ++pl) a[t][pl] = *reinterpret_cast<const x6_u32x4*>(pa + pl * GX_PLANE);
+        for (int pl = 0; pl < 3; ++pl) a[t][pl] = *reinterpret_cast<const gpe_u32x4*>(pa + pl * GX_PLANE);
     }
 #pragma unroll
     for (int nt = 0; nt < 4; ++nt) {
-        x6_u32x4 b[3];
+        gpe_u32x4 b[3];
         const int rb = 64 * wn + 16 * nt + j;
         const char* pb = Bb + rb * 64 + 16 * gx_slot(rb, g);
 #pragma unroll
-        for (int pl = 0; pl < 3; ++pl) b[pl] = *reinterpret_cast<const x6_u32x4*>(pb + pl * GX_PLANE);
+        for (int pl = 0; pl < 3; ++pl) b[pl] = *reinterpret_cast<const gpe_u32x4*>(pb + pl * GX_PLANE);
 #pragma unroll
         for (int t = 0; t < GXS::NPROD; ++t)
 #pragma unroll

@@ -19,7 +19,7 @@
 //             among the other survivors), then list entries and survivors are scattered to their new slots through a
 //             512-byte per-wave LDS strip.  No per-lane sorted arrays, no scratch memory.
 // Ordering rule: ascending (dist, candidate index); an equal-distance candidate never displaces an earlier one.
-#include "gpe_common.h"
+#include "gpe_device.h"
 #include <math.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -795,8 +795,6 @@ __global__ __launch_bounds__(256, KNN_MF_WGS) void gpe_knn_mfma_kernel(const flo
 // channels per step on two LDS buffers: one barrier per step instead of two per 32 channels; and 60 KB of LDS = two workgroups
 // per CU = two clouds in flight per XCD, whose plane tables (2 x 1.3 MB at the shipped size) stay in the 4 MiB L2 — the
 // fp32 filter streamed four (729 MB fetched for a 39 MB table set, profiles/r03_i_hbm_traffic.json).
-typedef _Float16 knn_f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned knn_u32x4 __attribute__((ext_vector_type(4)));
 #define KNN_H3_CCH 64                     // channels per staged step: two 32-k MFMA blocks
 #define KNN_H3_PITCH 160                  // bytes per plane row in LDS: 8 data chunks of 16 B + 2 pad (chunk count = 2 mod 4:
                                           // the ds_read_b128 that walks down a column is conflict-free, gpe_edgegemm_split_kernel.h)
@@ -929,19 +927,19 @@ __global__ __launch_bounds__(256, 2) void gpe_knn_h3_kernel(const _Float16* __re
     }
     // ---- the wave's 16 queries: resident B fragments (lane (j, g): query j, halves 32 blk + 8 g .. + 7 of both planes) ----
     const int NB = CP >> 5;
-    knn_u32x4 qh[NBMAX], ql[NBMAX];
+    gpe_u32x4 qh[NBMAX], ql[NBMAX];
     {
         const _Float16* qrow = cloud + (size_t)myq * 2 * CP;
 #pragma unroll
         for (int blk = 0; blk < NBMAX; ++blk) {
             const int bb = (blk < NB) ? blk : 0;
-            qh[blk] = *reinterpret_cast<const knn_u32x4*>(qrow + 32 * bb + 8 * g);
-            ql[blk] = *reinterpret_cast<const knn_u32x4*>(qrow + CP + 32 * bb + 8 * g);
+            qh[blk] = *reinterpret_cast<const gpe_u32x4*>(qrow + 32 * bb + 8 * g);
+            ql[blk] = *reinterpret_cast<const gpe_u32x4*>(qrow + CP + 32 * bb + 8 * g);
         }
     }
     // ---- staging: a step = 64 candidates x 64 channels of both planes = 1024 sixteen-byte pieces, four per thread ----------
     const int nchunk = (CP + KNN_H3_CCH - 1) / KNN_H3_CCH;
-    knn_u32x4 pre[4];
+    gpe_u32x4 pre[4];
     float pre_n = 0.f, pre_s = 0.f;
     int pre_first = 0, pre_tp = 0;
     // visit order of the candidate tiles of this piece: rotated so that the scan STARTS one tile before the queries' own tile (rot:
@@ -965,7 +963,7 @@ __global__ __launch_bounds__(256, 2) void gpe_knn_h3_kernel(const _Float16* __re
             const int plane = e >> 9, row = (e >> 3) & 63, c16 = e & 7;
             const int pr = (pf_c0 + row < N) ? pf_c0 + row : N - 1;
             const int cc = (c16 < nv) ? c16 : 0;                            // pieces past CP are never read back: any valid address
-            pre[i] = *reinterpret_cast<const knn_u32x4*>(cloud + (size_t)pr * 2 * CP + plane * CP + ch0 + 8 * cc);
+            pre[i] = *reinterpret_cast<const gpe_u32x4*>(cloud + (size_t)pr * 2 * CP + plane * CP + ch0 + 8 * cc);
         }
         pre_first = pf_ci == 0;
         pre_tp = pf_tp;
@@ -981,7 +979,7 @@ __global__ __launch_bounds__(256, 2) void gpe_knn_h3_kernel(const _Float16* __re
         for (int i = 0; i < 4; ++i) {
             const int e = tid + 256 * i;
             const int plane = e >> 9, row = (e >> 3) & 63, c16 = e & 7;
-            *reinterpret_cast<knn_u32x4*>(cB + buf * BUF_B + plane * PLANE_B + row * KNN_H3_PITCH + 16 * c16) = pre[i];
+            *reinterpret_cast<gpe_u32x4*>(cB + buf * BUF_B + plane * PLANE_B + row * KNN_H3_PITCH + 16 * c16) = pre[i];
         }
         if (pre_first && tid < KNN_TC) { npS[pre_tp * KNN_TC + tid] = pre_n; isS[pre_tp * KNN_TC + tid] = pre_s; }
     };
@@ -1016,16 +1014,16 @@ __global__ __launch_bounds__(256, 2) void gpe_knn_h3_kernel(const _Float16* __re
 #pragma unroll
             for (int b2 = 0; b2 < 2; ++b2) {
                 if (2 * ci + b2 < NBMAX && b2 < nblk) {
-                    const knn_u32x4 bh = qh[(2 * ci + b2 < NBMAX) ? 2 * ci + b2 : 0], bl = ql[(2 * ci + b2 < NBMAX) ? 2 * ci + b2 : 0];
+                    const gpe_u32x4 bh = qh[(2 * ci + b2 < NBMAX) ? 2 * ci + b2 : 0], bl = ql[(2 * ci + b2 < NBMAX) ? 2 * ci + b2 : 0];
 #pragma unroll
                     for (int mt = 0; mt < 4; ++mt) {
                         const char* src = tile + 16 * mt * KNN_H3_PITCH + 64 * b2;
-                        const knn_u32x4 ah = *reinterpret_cast<const knn_u32x4*>(src);
-                        const knn_u32x4 al = *reinterpret_cast<const knn_u32x4*>(src + PLANE_B);
+                        const gpe_u32x4 ah = *reinterpret_cast<const gpe_u32x4*>(src);
+                        const gpe_u32x4 al = *reinterpret_cast<const gpe_u32x4*>(src + PLANE_B);
                         // small terms first
-                        acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(knn_f16x8, al), __builtin_bit_cast(knn_f16x8, bh), acc[mt], 0, 0, 0);
-                        acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(knn_f16x8, ah), __builtin_bit_cast(knn_f16x8, bl), acc[mt], 0, 0, 0);
-                        acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(knn_f16x8, ah), __builtin_bit_cast(knn_f16x8, bh), acc[mt], 0, 0, 0);
+                        acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(gpe_f16x8, al), __builtin_bit_cast(gpe_f16x8, bh), acc[mt], 0, 0, 0);
+                        acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(gpe_f16x8, ah), __builtin_bit_cast(gpe_f16x8, bl), acc[mt], 0, 0, 0);
+                        acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(gpe_f16x8, ah), __builtin_bit_cast(gpe_f16x8, bh), acc[mt], 0, 0, 0);
                     }
                 }
             }

@@ -1,13 +1,11 @@
 // The layer-2 (wide-feature) graph search's filter as a threshold scan — the kernel behind gpe_knn (gpe_knn.hip) for 16 <= C <= 160,
 // k <= 32 (replaces torch_cluster.knn as reached from /root/reference/nn/net_blocks.py:127-135,174 through PyG's DynamicEdgeConv).
 // Its own translation unit: gpe_knn.hip is compiled under the max-ILP scheduling strategy its ordered-list kernels were tuned with.
-#include "gpe_common.h"
+#include "gpe_device.h"
 #include <math.h>
 #include <stdint.h>
 
 #define KNN_TC 64
-typedef _Float16 knn_f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned knn_u32x4 __attribute__((ext_vector_type(4)));
 
 // =====================================================================================================================
 // Round 6: the fp16-pipe filter as a THRESHOLD scan (gpe_knn_ft_kernel; C <= 160, k <= 32).  What gpe_knn_h3_kernel spends its time
@@ -87,14 +85,14 @@ __global__ __launch_bounds__(64 * NW) void gpe_knn_ft_kernel(const _Float16* __r
     const float m2e = 2.02f * ce * (nq + __int_as_float(cmax[b]));
     // ---- the wave's 16 queries: resident B fragments (lane (j, g): query j, halves 32 blk + 8 g .. + 7 of both planes) ----
     const int NB = CP >> 5;
-    knn_u32x4 qh[KNN_FT_NBMAX], ql[KNN_FT_NBMAX];
+    gpe_u32x4 qh[KNN_FT_NBMAX], ql[KNN_FT_NBMAX];
     {
         const _Float16* qrow = cloud + (size_t)myq * 2 * CP;
 #pragma unroll
         for (int blk = 0; blk < KNN_FT_NBMAX; ++blk) {
             const int bb = (blk < NB) ? blk : 0;
-            qh[blk] = *reinterpret_cast<const knn_u32x4*>(qrow + 32 * bb + 8 * g);
-            ql[blk] = *reinterpret_cast<const knn_u32x4*>(qrow + CP + 32 * bb + 8 * g);
+            qh[blk] = *reinterpret_cast<const gpe_u32x4*>(qrow + 32 * bb + 8 * g);
+            ql[blk] = *reinterpret_cast<const gpe_u32x4*>(qrow + CP + 32 * bb + 8 * g);
         }
     }
     // ---- staging: a step = one candidate tile, whole rows (4 CP bytes = CP / 4 sixteen-byte pieces per row) -----------------
@@ -108,7 +106,7 @@ __global__ __launch_bounds__(64 * NW) void gpe_knn_ft_kernel(const _Float16* __r
         prow[i] = r;
         poff[i] = (e < total) ? 16 * (e - r * ppr) : 0;
     }
-    knn_u32x4 pre[PRE];
+    gpe_u32x4 pre[PRE];
     float pre_n = 0.f, pre_s = 0.f;
     const int ntile = (N + KNN_TC - 1) / KNN_TC;
     // visit order: rotated so that the scan starts one tile before the queries' own tiles when the rows are in a locality order
@@ -123,7 +121,7 @@ __global__ __launch_bounds__(64 * NW) void gpe_knn_ft_kernel(const _Float16* __r
         for (int i = 0; i < PRE; ++i) {
             if (prow[i] >= 0) {
                 const int pr = (c0 + prow[i] < N) ? c0 + prow[i] : N - 1;
-                pre[i] = *reinterpret_cast<const knn_u32x4*>(reinterpret_cast<const char*>(cloud) + (size_t)pr * 4 * CP + poff[i]);
+                pre[i] = *reinterpret_cast<const gpe_u32x4*>(reinterpret_cast<const char*>(cloud) + (size_t)pr * 4 * CP + poff[i]);
             }
         }
         if (tid < KNN_TC) {
@@ -135,7 +133,7 @@ __global__ __launch_bounds__(64 * NW) void gpe_knn_ft_kernel(const _Float16* __r
     auto commit = [&](int buf, int tp) {
 #pragma unroll
         for (int i = 0; i < PRE; ++i)
-            if (prow[i] >= 0) *reinterpret_cast<knn_u32x4*>(cB + buf * bufB + prow[i] * pitch + poff[i]) = pre[i];
+            if (prow[i] >= 0) *reinterpret_cast<gpe_u32x4*>(cB + buf * bufB + prow[i] * pitch + poff[i]) = pre[i];
         if (tid < KNN_TC) { npS[tp * KNN_TC + tid] = pre_n; isS[tp * KNN_TC + tid] = pre_s; }
     };
     prefetch(tile_c0(0));
@@ -231,16 +229,16 @@ __global__ __launch_bounds__(64 * NW) void gpe_knn_ft_kernel(const _Float16* __r
 #pragma unroll
         for (int blk = 0; blk < KNN_FT_NBMAX; ++blk) {
             if (blk < NB && !(probe & 4)) {               // uniform
-                const knn_u32x4 bh = qh[blk], bl = ql[blk];
+                const gpe_u32x4 bh = qh[blk], bl = ql[blk];
 #pragma unroll
                 for (int mt = 0; mt < 4; ++mt) {
                     const char* src = tile + 16 * mt * pitch + 64 * blk;
-                    const knn_u32x4 ah = *reinterpret_cast<const knn_u32x4*>(src);
-                    const knn_u32x4 al = *reinterpret_cast<const knn_u32x4*>(src + 2 * CP);
+                    const gpe_u32x4 ah = *reinterpret_cast<const gpe_u32x4*>(src);
+                    const gpe_u32x4 al = *reinterpret_cast<const gpe_u32x4*>(src + 2 * CP);
                     // small terms first
-                    acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(knn_f16x8, al), __builtin_bit_cast(knn_f16x8, bh), acc[mt], 0, 0, 0);
-                    acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(knn_f16x8, ah), __builtin_bit_cast(knn_f16x8, bl), acc[mt], 0, 0, 0);
-                    acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(knn_f16x8, ah), __builtin_bit_cast(knn_f16x8, bh), acc[mt], 0, 0, 0);
+                    acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(gpe_f16x8, al), __builtin_bit_cast(gpe_f16x8, bh), acc[mt], 0, 0, 0);
+                    acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(gpe_f16x8, ah), __builtin_bit_cast(gpe_f16x8, bl), acc[mt], 0, 0, 0);
+                    acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(gpe_f16x8, ah), __builtin_bit_cast(gpe_f16x8, bh), acc[mt], 0, 0, 0);
                 }
             }
         }

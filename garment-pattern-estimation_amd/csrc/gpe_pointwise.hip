@@ -2,7 +2,7 @@
 // gather with fp64 BN statistics, BN finalisation (forward + backward coefficient algebra), max-aggregation
 // finish, kNN graph transposition + deterministic pull-style scatter, segment mean pool, LSTM cell pointwise.
 // Reference lines each one replaces are listed in include/gpe_hip.h.
-#include "gpe_common.h"
+#include "gpe_device.h"
 #include <math.h>
 
 extern "C" int gpe_abi_version(void) { return 7; }
@@ -118,8 +118,6 @@ __device__ __forceinline__ float gpe_pack_elem(const GpePackJob& jb, int n, int 
     return 0.f;
 }
 
-typedef _Float16 pk_f16x8 __attribute__((ext_vector_type(8)));
-
 // blocks a job occupies in a gpe_pack_multi launch (ops.PackPlan builds first_block from it).  Row-major sources (kinds 0, 2, 8:
 // the reduction index k is the fast index of the weight) go through 64 x 64 tiles: rows are read in whole 256-byte pieces and turned
 // in LDS — read column by column (round 2 - 5) every load instruction touched 64 cache lines for 64 floats.  Kind 9: 4096 elements
@@ -191,14 +189,14 @@ __device__ __forceinline__ void gpe_pack_tile(const GpePackJob& jb, long tb)
     for (int i = 0; i < 4; ++i) {
         const int q = tid + 256 * i, plane = q >> 9, r = q & 511, kg = r >> 6, c = r & 63;
         if (n0 + c < jb.Npad && k0 + 8 * kg < KP) {
-            pk_f16x8 o;
+            gpe_f16x8 o;
 #pragma unroll
             for (int t = 0; t < 8; ++t) {
                 const float xs = tile[c][8 * kg + t] * sc;
                 const _Float16 h = (_Float16)xs;
                 o[t] = plane ? (_Float16)(xs - (float)h) : h;
             }
-            *reinterpret_cast<pk_f16x8*>(reinterpret_cast<char*>(jb.out) + ((long)(plane * KG + (k0 >> 3) + kg) * jb.Npad + n0 + c) * 16) = o;
+            *reinterpret_cast<gpe_f16x8*>(reinterpret_cast<char*>(jb.out) + ((long)(plane * KG + (k0 >> 3) + kg) * jb.Npad + n0 + c) * 16) = o;
         }
     }
 }
@@ -260,14 +258,14 @@ __global__ __launch_bounds__(256) void gpe_pack_multi_kernel(const GpePackJob* _
         gpe_h3_scale_of(*reinterpret_cast<const unsigned*>(jb.w2), sc, inv);
         GpePackJob je = jb;
         je.kind = (jb.kind == 8) ? 2 : 1;
-        pk_f16x8 o;
+        gpe_f16x8 o;
 #pragma unroll
         for (int t = 0; t < 8; ++t) {
             const float xs = gpe_pack_elem(je, n, (int)(8 * kg) + t) * sc;
             const _Float16 h = (_Float16)xs;
             o[t] = plane ? (_Float16)(xs - (float)h) : h;
         }
-        *reinterpret_cast<pk_f16x8*>(reinterpret_cast<char*>(jb.out) + (size_t)u * 16) = o;
+        *reinterpret_cast<gpe_f16x8*>(reinterpret_cast<char*>(jb.out) + (size_t)u * 16) = o;
         return;
     }
     if (jb.kind >= 5) {                                              // vector jobs, element-wise
@@ -1196,8 +1194,6 @@ extern "C" int gpe_segment_mean_bwd(const float* gy, int ldgy, int B, int N, int
 // ---------------------------------------------------------------------------------------------------------
 // LSTM cell pointwise (gate order i, f, g, o as in torch.nn.LSTM)
 // ---------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float gpe_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
-
 __global__ void gpe_lstm_cell_fwd_kernel(float* __restrict__ gates, const float* __restrict__ c_prev, long ldc_prev,
                                          float* __restrict__ c, float* __restrict__ h, long h_stride, int Bn, int H)
 {
@@ -1206,14 +1202,11 @@ __global__ void gpe_lstm_cell_fwd_kernel(float* __restrict__ gates, const float*
     const long b = e / H;
     const int u = (int)(e - b * H);
     float* gr = gates + b * 4 * H;
-    const float ig = gpe_sigmoid(gr[u]);
-    const float fg = gpe_sigmoid(gr[H + u]);
-    const float gg = tanhf(gr[2 * H + u]);
-    const float og = gpe_sigmoid(gr[3 * H + u]);
-    const float cn = fg * c_prev[b * ldc_prev + u] + ig * gg;
+    float ig, fg, gg, og, cn;
+    gpe_lstm_cell_fwd(gr[u], gr[H + u], gr[2 * H + u], gr[3 * H + u], c_prev[b * ldc_prev + u], ig, fg, gg, og, cn);
     gr[u] = ig; gr[H + u] = fg; gr[2 * H + u] = gg; gr[3 * H + u] = og;
     c[b * H + u] = cn;
-    h[b * h_stride + u] = og * tanhf(cn);
+    h[b * h_stride + u] = gpe_lstm_cell_h(og, cn);
 }
 
 extern "C" int gpe_lstm_cell_fwd(float* gates, const float* c_prev, long ldc_prev, float* c, float* h,
@@ -1239,19 +1232,15 @@ __global__ void gpe_lstm_cell_bwd_kernel(const float* __restrict__ dh_out, long 
     const long b = e / H;
     const int u = (int)(e - b * H);
     const float* gr = gates + b * 4 * H;
-    const float ig = gr[u], fg = gr[H + u], gg = gr[2 * H + u], og = gr[3 * H + u];
     float dh = dh_out ? dh_out[b * dho_stride + u] : 0.f;
     if (dh_rec)
         for (int z = 0; z < n_rec; ++z) dh += dh_rec[(long)z * Bn * H + b * H + u];   // split-K partials
-    const float tc = tanhf(c[b * H + u]);
-    float dc = dh * og * (1.f - tc * tc);
-    if (dc_next) dc += dc_next[b * H + u];
+    float di, df, dgg, dgo, cout;
+    gpe_lstm_cell_bwd(gr[u], gr[H + u], gr[2 * H + u], gr[3 * H + u], c[b * H + u], c_prev[b * ldc_prev + u], dh,
+                      dc_next ? dc_next + b * H + u : nullptr, di, df, dgg, dgo, cout);
     float* dg = dgates + b * dg_stride;
-    dg[u] = dc * gg * ig * (1.f - ig);
-    dg[H + u] = dc * c_prev[b * ldc_prev + u] * fg * (1.f - fg);
-    dg[2 * H + u] = dc * ig * (1.f - gg * gg);
-    dg[3 * H + u] = dh * tc * og * (1.f - og);
-    dc_prev[b * H + u] = dc * fg;
+    dg[u] = di; dg[H + u] = df; dg[2 * H + u] = dgg; dg[3 * H + u] = dgo;
+    dc_prev[b * H + u] = cout;
 }
 
 extern "C" int gpe_lstm_cell_bwd(const float* dh_out, long dho_stride, const float* dh_rec, int n_rec,

@@ -8,7 +8,7 @@
 // caller-owned fp64 workspace (panel kernel, stitch kernel), and a single-thread finalise kernel combines them IN PATTERN ORDER,
 // with the reference's own number types per slot (fp32 sums where the reference sums fp32 tensors, fp64 where it sums Python
 // floats), so the result vector is bit-reproducible run to run.  At most three launches per call, no host reads.
-#include "gpe_common.h"
+#include "gpe_device.h"
 #include <math.h>
 
 // every product / sum below is rounded on its own, in the reference's order (no contraction into FMAs)
@@ -176,10 +176,6 @@ struct QmStitchParams {
     int B, P, L, flags;
 };
 
-// torch.round(torch.sigmoid(x)) == 0 on the device: sigmoid as 1 / (1 + exp(-x)) in fp32 (expf, IEEE division) and round half
-// to even, so exactly 0.5 is a non-free edge.  NaN rounds to NaN, which is "free" (the reference casts it to True).
-__device__ __forceinline__ float qm_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
-
 __device__ __forceinline__ float qm_dist(const float* T, int i, int j, int D)
 {
     float s = 0.f;
@@ -222,7 +218,9 @@ __global__ __launch_bounds__(QM_TPB) void gpe_quality_stitch_kernel(QmStitchPara
         if (e < PL) {
             const int pp = e / q.L, l = e - pp * q.L;
             const float x = q.logit[b * q.m_sb + pp * q.m_sp + l * q.m_sl];
-            const float sg = qm_sigmoid(x);
+            // torch.round(torch.sigmoid(x)) == 0 on the device: gpe_sigmoid (fp32 expf, IEEE division) and round half to even, so exactly
+            // 0.5 is a non-free edge.  NaN rounds to NaN, which is "free" (the reference casts it to True).
+            const float sg = gpe_sigmoid(x);
             nonfree = sg <= 0.5f;
             if (q.flags & QM_FREE) {
                 const float cls = sg != sg ? sg : (sg > 0.5f ? 1.f : 0.f);
@@ -252,7 +250,7 @@ __global__ __launch_bounds__(QM_TPB) void gpe_quality_stitch_kernel(QmStitchPara
         int pp = 0, l = 0;
         if (e < PL && e != drop) {
             pp = e / q.L; l = e - pp * q.L;
-            nonfree = qm_sigmoid(q.logit[b * q.m_sb + pp * q.m_sp + l * q.m_sl]) <= 0.5f;
+            nonfree = gpe_sigmoid(q.logit[b * q.m_sb + pp * q.m_sp + l * q.m_sl]) <= 0.5f;
         }
         const unsigned long long bal = __ballot(nonfree);
         if (nonfree) {

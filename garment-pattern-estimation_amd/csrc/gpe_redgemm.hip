@@ -15,7 +15,7 @@
 //     7/6 x 7/6 instead of 4/3/3/3 rows of 13 (86 % vs 81 % balance, half the operand reads);
 //   * one partial per workgroup at the end; a second kernel sums the partials in a fixed order (fp64), so results
 //     are run-to-run deterministic.
-#include "gpe_common.h"
+#include "gpe_device.h"
 #include <stdlib.h>
 
 long gpe_gemm_x6_red_ws(int Mg, int Ng);                                                 // gpe_gemm_x6.hip
@@ -578,43 +578,24 @@ __global__ __launch_bounds__(512, 2) void gpe_redgemm_pc_kernel(RdParams p)
 // A producer lane owns columns 4l..4l+3 of rows 8*w4..8*w4+7, so its four ds_write_b128 per plane land on consecutive
 // 16-byte slots across lanes (conflict-free), and a consumer's 16 lanes (i = 0..15, same g) hit 8 distinct 16-byte bank
 // groups per 8 lanes because S % 8 == 2.
-typedef __bf16 rd_bf16x2_t __attribute__((ext_vector_type(2)));
-typedef __bf16 rd_bf16x8_t __attribute__((ext_vector_type(8)));
-typedef float rd_f32x2_t __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ void rd_split_pair(float x0, float x1, unsigned& hw, unsigned& lw)
-{
-    const rd_f32x2_t x = {x0, x1};
-    hw = __builtin_bit_cast(unsigned, __builtin_convertvector(x, rd_bf16x2_t));          // v_cvt_pk_bf16_f32 (RNE)
-    const rd_f32x2_t r = {x0 - __uint_as_float(hw << 16), x1 - __uint_as_float(hw & 0xffff0000u)};
-    lw = __builtin_bit_cast(unsigned, __builtin_convertvector(r, rd_bf16x2_t));
-}
 __device__ __forceinline__ f32x4 rd_mfma32(const uint4 a, const uint4 b, const f32x4 c)
 {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(rd_bf16x8_t, a), __builtin_bit_cast(rd_bf16x8_t, b),
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(gpe_bf16x8, a), __builtin_bit_cast(gpe_bf16x8, b),
                                                    c, 0, 0, 0);
 }
 // f16x3 (gpe_math_set(4)): the same kernel with two-term fp16 splits of operands normalised per tensor by a power of two
 // (gpe_edgegemm_split_kernel.h has the arithmetic; the scales come from the notes / bounds of gpe_edgegemm_h3.hip)
-typedef _Float16 rd_f16x2_t __attribute__((ext_vector_type(2)));
-typedef _Float16 rd_f16x8_t __attribute__((ext_vector_type(8)));
 template <bool F16>
 __device__ __forceinline__ void rd_split_pair_p(float x0, float x1, unsigned& hw, unsigned& lw)
 {
-    if constexpr (F16) {
-        const rd_f32x2_t x = {x0, x1};
-        const rd_f16x2_t h = __builtin_convertvector(x, rd_f16x2_t);
-        const rd_f32x2_t r = x - __builtin_convertvector(h, rd_f32x2_t);
-        hw = __builtin_bit_cast(unsigned, h);
-        lw = __builtin_bit_cast(unsigned, __builtin_convertvector(r, rd_f16x2_t));
-    } else
-        rd_split_pair(x0, x1, hw, lw);
+    if constexpr (F16) gpe_split2_f16(x0, x1, hw, lw);
+    else gpe_split2_bf16(x0, x1, hw, lw);
 }
 template <bool F16>
 __device__ __forceinline__ f32x4 rd_mfma32_p(const uint4 a, const uint4 b, const f32x4 c)
 {
     if constexpr (F16)
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(rd_f16x8_t, a), __builtin_bit_cast(rd_f16x8_t, b), c, 0, 0, 0);
+        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(gpe_f16x8, a), __builtin_bit_cast(gpe_f16x8, b), c, 0, 0, 0);
     else
         return rd_mfma32(a, b, c);
 }
@@ -848,10 +829,8 @@ __global__ __launch_bounds__(512, 2) void gpe_redgemm_b3_kernel(RdParams p)
                 const int slot0 = (w4 & 1) * RQ;
 #pragma unroll
                 for (int q = 0; q < RQ; ++q) {
-                    typedef _Float16 rd_h2 __attribute__((ext_vector_type(2)));
-                    typedef float rd_f2 __attribute__((ext_vector_type(2)));
-                    const rd_f2 a01 = __builtin_convertvector(__builtin_bit_cast(rd_h2, __float_as_uint(ur[q].x)), rd_f2);
-                    const rd_f2 a23 = __builtin_convertvector(__builtin_bit_cast(rd_h2, __float_as_uint(ur[q].y)), rd_f2);
+                    const gpe_f32x2 a01 = __builtin_convertvector(__builtin_bit_cast(gpe_f16x2, __float_as_uint(ur[q].x)), gpe_f32x2);
+                    const gpe_f32x2 a23 = __builtin_convertvector(__builtin_bit_cast(gpe_f16x2, __float_as_uint(ur[q].y)), gpe_f32x2);
                     const float av[4] = {a01[0], a01[1], a23[0], a23[1]};
                     float dz[4];
 #pragma unroll

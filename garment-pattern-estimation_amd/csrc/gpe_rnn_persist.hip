@@ -16,38 +16,24 @@
 // runs ahead; the input-side product of the layers above is issued before the recurrent one, while the recurrent operand is
 // still being published.
 //
-// Inter-workgroup visibility (MI355X_MICROARCH.md "Workgroup dispatch, XCD placement & inter-workgroup visibility", recipe R1
-// of cdna_hip_programming.md Guideline 16): published words are written with sc1 (write-through) stores, every storing wave
-// drains vmcnt before the workgroup's ONE relaxed agent-scope counter increment; consumers poll the counter with relaxed
-// agent-scope loads and read the payload with sc1 buffer loads (L1 bypass; the producer stored sc1, so no acquire fence).
-// Nothing depends on workgroup -> XCD placement or dispatch order.  All workgroups must be co-resident: the host sizes the grid
-// to at most one workgroup per CU (the LDS image allows no second one); every spin is bounded and traps.  Counters are zeroed
-// by a memset node in front of every launch.
+// Inter-workgroup visibility: recipe R1 (gpe_device.h: hand-off), workgroup form — ONE counter increment per workgroup and cell;
+// consumers read the payload with sc1 buffer loads.  Co-residency: the host sizes the grid to at most one workgroup per CU (the
+// LDS image allows no second one).  Counters are zeroed by a memset node in front of every launch.
 //
 // The backward kernel mirrors it: workgroup (l, rg, nb) owns dh columns of 16 units; its slices of W_hh_l^T and W_ih_{l+1}^T
 // (K = 4H rows x 16 columns) stay in LDS; the exchanged operand is the pre-activation gradient row dG (4H wide, torch gate
 // order, written straight into the caller's dgx rows, which the weight-gradient GEMMs read afterwards).
 // Arithmetic: exact fp32 MFMA, or f16x3 (gpe_math_set(4)): weights from the caller's fp16 plane packs; the forward state rows
-// enter scaled by 2^12 (|h| < 1, start states < 16: same contract as gpe_rnn_wave.hip); the backward dG fragments are
+// enter scaled by GPE_STATE_SA (gpe_device.h: |h| < 1, start states < 16); the backward dG fragments are
 // normalised PER WAVE by the largest magnitude the wave just loaded (each wave owns its partial accumulator, so the scale is
 // undone before the partials meet) — no amax words, no atomics.
-#include "gpe_common.h"
-#include <math.h>
+#include "gpe_device.h"
 
 extern "C" int gpe_debug_get(void);
 
 #define PS_MAXL 4
 #define PS_LDC 68                 // forward C tile pitch (64 gate columns + 4)
 #define PS_LDB 20                 // backward C tile pitch (16 units + 4)
-#define PS_SPIN_LIMIT (1u << 23)  // polls (>= 0.1 us each) before a stuck workgroup traps instead of hanging the queue
-#define PS_SA 4096.f
-#define PS_INV_SA (1.f / 4096.f)
-
-typedef unsigned ps_u32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 ps_f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 ps_f16x2 __attribute__((ext_vector_type(2)));
-typedef float ps_f32x2 __attribute__((ext_vector_type(2)));
-
 struct PsFwdParams {
     int L, T, Bn, H, NB, RG, NRT;
     const float* xproj0; long xp0_sb, xp0_st;
@@ -83,41 +69,8 @@ struct PsBwdParams {
         if (p.trace && tid == 0) p.trace[((long)blockIdx.x * T + t) * 8 + (i)] = wall_clock64();            \
     } while (0)
 
-__device__ __forceinline__ float ps_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
-
-// every wave polls for itself: one word, relaxed, agent scope (an sc1 load: served by L2 / the fabric, never by this CU's L1)
-__device__ __forceinline__ void ps_wait(const unsigned* flag, unsigned need)
-{
-    unsigned spins = 0;
-    for (;;) {
-        const unsigned v = __builtin_amdgcn_readfirstlane(__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-        if (v >= need) break;
-        __builtin_amdgcn_s_sleep(1);
-        if (++spins > PS_SPIN_LIMIT) __builtin_trap();
-    }
-    asm volatile("" ::: "memory");           // payload loads stay below the poll
-}
-
-// publish: every storing wave has drained its sc1 stores; ONE lane counts the workgroup in
-__device__ __forceinline__ void ps_arrive(unsigned* flag, unsigned long long* stamp = nullptr)
-{
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (stamp && threadIdx.x == 0) *stamp = wall_clock64();
-    __syncthreads();
-    if (threadIdx.x == 0) __hip_atomic_fetch_add(flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ __forceinline__ void ps_split2(float a, float b, float s, unsigned& h, unsigned& l)
-{
-    const ps_f32x2 v = {a * s, b * s};
-    const ps_f16x2 hh = __builtin_convertvector(v, ps_f16x2);
-    const ps_f32x2 r = v - __builtin_convertvector(hh, ps_f32x2);
-    h = __builtin_bit_cast(unsigned, hh);
-    l = __builtin_bit_cast(unsigned, __builtin_convertvector(r, ps_f16x2));
-}
-
 // zero the elements of a loaded quad whose k index is past the operand's K extent (what follows a row in memory is another row)
-__device__ __forceinline__ ps_u32x4 ps_mask4(ps_u32x4 v, int k0, int K)
+__device__ __forceinline__ gpe_u32x4 ps_mask4(gpe_u32x4 v, int k0, int K)
 {
     v[0] = (k0 < K) ? v[0] : 0u; v[1] = (k0 + 1 < K) ? v[1] : 0u;
     v[2] = (k0 + 2 < K) ? v[2] : 0u; v[3] = (k0 + 3 < K) ? v[3] : 0u;
@@ -132,7 +85,7 @@ __device__ __forceinline__ ps_u32x4 ps_mask4(ps_u32x4 v, int k0, int K)
 //   H3 slice layout  [plane][KP / 8][16 NT columns][8 halves]   step = 32 k, two quads per lane
 //   fp32 slice layout [KP / 4][16 NT columns][4 floats]          step = 16 k, one quad per lane
 template <bool H3, int MAXS>
-struct PsA { ps_u32x4 v[H3 ? 2 * MAXS : MAXS]; };
+struct PsA { gpe_u32x4 v[H3 ? 2 * MAXS : MAXS]; };
 
 template <bool H3, int MAXS>
 __device__ __forceinline__ void ps_load(PsA<H3, MAXS>& A, __amdgpu_buffer_rsrc_t rs, int arow, long pitch, int K, int s_lo, int nsteps)
@@ -175,20 +128,20 @@ __device__ __forceinline__ float ps_mma(const PsA<H3, MAXS>& A, int KP, const ch
         for (int i = 0; i < MAXS; ++i) {
             const int s = s_lo + i;
             if (s < s_hi) {
-                ps_u32x4 ah, al;
-                const ps_u32x4 a0 = A.v[2 * i], a1 = A.v[2 * i + 1];
-                { unsigned h, l; ps_split2(__uint_as_float(a0[0]), __uint_as_float(a0[1]), sA, h, l); ah[0] = h; al[0] = l; }
-                { unsigned h, l; ps_split2(__uint_as_float(a0[2]), __uint_as_float(a0[3]), sA, h, l); ah[1] = h; al[1] = l; }
-                { unsigned h, l; ps_split2(__uint_as_float(a1[0]), __uint_as_float(a1[1]), sA, h, l); ah[2] = h; al[2] = l; }
-                { unsigned h, l; ps_split2(__uint_as_float(a1[2]), __uint_as_float(a1[3]), sA, h, l); ah[3] = h; al[3] = l; }
+                gpe_u32x4 ah, al;
+                const gpe_u32x4 a0 = A.v[2 * i], a1 = A.v[2 * i + 1];
+                { unsigned h, l; gpe_split2_f16(__uint_as_float(a0[0]), __uint_as_float(a0[1]), sA, h, l); ah[0] = h; al[0] = l; }
+                { unsigned h, l; gpe_split2_f16(__uint_as_float(a0[2]), __uint_as_float(a0[3]), sA, h, l); ah[1] = h; al[1] = l; }
+                { unsigned h, l; gpe_split2_f16(__uint_as_float(a1[0]), __uint_as_float(a1[1]), sA, h, l); ah[2] = h; al[2] = l; }
+                { unsigned h, l; gpe_split2_f16(__uint_as_float(a1[2]), __uint_as_float(a1[3]), sA, h, l); ah[3] = h; al[3] = l; }
                 const char* wb = W + ((4 * s + g) * 16 * NT + j) * 16;
 #pragma unroll
                 for (int n = 0; n < NT; ++n) {
-                    const ps_u32x4 bh = *reinterpret_cast<const ps_u32x4*>(wb + 256 * n);
-                    const ps_u32x4 bl = *reinterpret_cast<const ps_u32x4*>(wb + 256 * n + plane_b);
-                    acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(ps_f16x8, al), __builtin_bit_cast(ps_f16x8, bh), acc[n], 0, 0, 0);
-                    acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(ps_f16x8, ah), __builtin_bit_cast(ps_f16x8, bl), acc[n], 0, 0, 0);
-                    acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(ps_f16x8, ah), __builtin_bit_cast(ps_f16x8, bh), acc[n], 0, 0, 0);
+                    const gpe_u32x4 bh = *reinterpret_cast<const gpe_u32x4*>(wb + 256 * n);
+                    const gpe_u32x4 bl = *reinterpret_cast<const gpe_u32x4*>(wb + 256 * n + plane_b);
+                    acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(gpe_f16x8, al), __builtin_bit_cast(gpe_f16x8, bh), acc[n], 0, 0, 0);
+                    acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(gpe_f16x8, ah), __builtin_bit_cast(gpe_f16x8, bl), acc[n], 0, 0, 0);
+                    acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(gpe_f16x8, ah), __builtin_bit_cast(gpe_f16x8, bh), acc[n], 0, 0, 0);
                 }
             }
         }
@@ -214,20 +167,6 @@ __device__ __forceinline__ float ps_mma(const PsA<H3, MAXS>& A, int KP, const ch
     return inv;
 }
 
-// copy this workgroup's columns [c0, c0 + CW) of every 16-byte-piece group of a packed weight into LDS:
-// piece (group, c) of the pack sits at (group * Npad + c0 + c) * 16 bytes
-template <int CW>
-__device__ __forceinline__ void ps_fill(char* dst, const void* src, int ngroups, int Npad, int c0)
-{
-    const ps_u32x4* s = reinterpret_cast<const ps_u32x4*>(src);
-    ps_u32x4* d = reinterpret_cast<ps_u32x4*>(dst);
-    const int total = ngroups * CW;
-    for (int e = threadIdx.x; e < total; e += 256) {
-        const int grp = e / CW, c = e - grp * CW;
-        d[e] = s[(long)grp * Npad + c0 + c];
-    }
-}
-
 // =====================================================================================================================
 // forward
 // =====================================================================================================================
@@ -248,13 +187,13 @@ __global__ __launch_bounds__(256) void gpe_rnn_persist_fwd_kernel(PsFwdParams p)
     char* W1 = ps_smem + wbytes;
     float* Cs = reinterpret_cast<float*>(ps_smem + (p.L > 1 ? 2 : 1) * wbytes);       // [4 waves][16][PS_LDC]
 
-    ps_fill<64>(W0, p.w0[l], KP >> 2, 64 * p.NB, 64 * nb);
-    if (l > 0) ps_fill<64>(W1, p.w1[l], KP >> 2, 64 * p.NB, 64 * nb);
+    gpe_fill<64, 256>(W0, p.w0[l], KP >> 2, 64 * p.NB, 64 * nb);
+    if (l > 0) gpe_fill<64, 256>(W1, p.w1[l], KP >> 2, 64 * p.NB, 64 * nb);
     float inv0 = 1.f, inv1 = 1.f;
     if constexpr (H3) {
         float sw;
-        gpe_h3_scale_of(p.s0[l][0], sw, inv0); inv0 *= PS_INV_SA;
-        if (l > 0) { gpe_h3_scale_of(p.s1[l][0], sw, inv1); inv1 *= PS_INV_SA; }
+        gpe_h3_scale_of(p.s0[l][0], sw, inv0); inv0 *= GPE_STATE_INV_SA;
+        if (l > 0) { gpe_h3_scale_of(p.s1[l][0], sw, inv1); inv1 *= GPE_STATE_INV_SA; }
     }
     __syncthreads();
 
@@ -293,18 +232,18 @@ __global__ __launch_bounds__(256) void gpe_rnn_persist_fwd_kernel(PsFwdParams p)
             for (int n = 0; n < 4; ++n) { accH[n] = (f32x4){0.f, 0.f, 0.f, 0.f}; accX[n] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
             // both flags first, then the loads of both segments back to back (one latency instead of two), then the products
             PsA<H3, MAXS> A1, A0;
-            if (l > 0) ps_wait(p.flags + ((long)(l - 1) * T + t) * p.NRT + rt, need);   // h_{l-1,t}: the layer below runs ahead
+            if (l > 0) gpe_flag_wait(p.flags + ((long)(l - 1) * T + t) * p.NRT + rt, need);   // h_{l-1,t}: the layer below runs ahead
             PS_STAMP(1);
-            if (t > 0) ps_wait(p.flags + ((long)l * T + t - 1) * p.NRT + rt, need);     // h_{l,t-1}
+            if (t > 0) gpe_flag_wait(p.flags + ((long)l * T + t - 1) * p.NRT + rt, need);     // h_{l,t-1}
             PS_STAMP(3);
             if (l > 0)                               // h_{l-1,t} (slot t+1) x W_ih_l
                 ps_load<H3, MAXS>(A1, __builtin_amdgcn_make_buffer_rsrc(p.hs + (l - 1) * p.hs_sl + (long)(t + 1) * p.hs_st, 0, nrec, 0x00020000),
                                   arow, p.hs_sb, H, s_lo, nsteps);
             ps_load<H3, MAXS>(A0, __builtin_amdgcn_make_buffer_rsrc(p.hs + l * p.hs_sl + (long)t * p.hs_st, 0, nrec, 0x00020000),
                               arow, p.hs_sb, H, s_lo, nsteps);                           // h_{l,t-1} (slot t) x W_hh_l
-            if (l > 0) ps_mma<H3, 4, MAXS, false>(A1, KP, W1, s_lo, s_hi, PS_SA, accX);
+            if (l > 0) ps_mma<H3, 4, MAXS, false>(A1, KP, W1, s_lo, s_hi, GPE_STATE_SA, accX);
             PS_STAMP(2);
-            ps_mma<H3, 4, MAXS, false>(A0, KP, W0, s_lo, s_hi, PS_SA, accH);
+            ps_mma<H3, 4, MAXS, false>(A0, KP, W0, s_lo, s_hi, GPE_STATE_SA, accH);
 #pragma unroll
             for (int n = 0; n < 4; ++n)
 #pragma unroll
@@ -318,19 +257,16 @@ __global__ __launch_bounds__(256) void gpe_rnn_persist_fwd_kernel(PsFwdParams p)
                 z[q] = (Cs[er * PS_LDC + 16 * q + eu] + Cs[(16 + er) * PS_LDC + 16 * q + eu]) +
                        (Cs[(32 + er) * PS_LDC + 16 * q + eu] + Cs[(48 + er) * PS_LDC + 16 * q + eu]);
             if (rok && uok) {
-                const float ig = ps_sigmoid(z[0] + e0);
-                const float fg = ps_sigmoid(z[1] + e1);
-                const float gg = tanhf(z[2] + e2);
-                const float og = ps_sigmoid(z[3] + e3);
-                const float cn = fg * cprev + ig * gg;
+                float ig, fg, gg, og, cn;
+                gpe_lstm_cell_fwd(z[0], e0, z[1], e1, z[2], e2, z[3], e3, cprev, ig, fg, gg, og, cn);
                 float* go = p.saved + l * p.sv_sl + (long)t * p.sv_st + (long)row * 4 * H;
                 go[unit] = ig; go[H + unit] = fg; go[2 * H + unit] = gg; go[3 * H + unit] = og;
                 p.cs[l * p.cs_sl + (long)(t + 1) * p.cs_st + (long)row * H + unit] = cn;
-                __hip_atomic_store(p.hs + l * p.hs_sl + (long)row * p.hs_sb + (long)(t + 1) * p.hs_st + unit, og * tanhf(cn),
+                __hip_atomic_store(p.hs + l * p.hs_sl + (long)row * p.hs_sb + (long)(t + 1) * p.hs_st + unit, gpe_lstm_cell_h(og, cn),
                                    __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
             PS_STAMP(5);
-            ps_arrive(p.flags + ((long)l * T + t) * p.NRT + rt,        // (its barrier also frees Cs for the next tile)
+            gpe_flag_arrive_wg(p.flags + ((long)l * T + t) * p.NRT + rt,        // (its barrier also frees Cs for the next tile)
                       p.trace ? p.trace + ((long)blockIdx.x * T + t) * 8 + 6 : nullptr);
             PS_STAMP(7);
         }
@@ -358,8 +294,8 @@ __global__ __launch_bounds__(256) void gpe_rnn_persist_bwd_kernel(PsBwdParams p)
     float* Cs = reinterpret_cast<float*>(ps_smem + (L > 1 ? 2 : 1) * wbytes);         // [4 waves][16][PS_LDB]
     const bool up = l < L - 1;                       // a layer above feeds dG_{l+1,t} x W_ih_{l+1}
 
-    ps_fill<16>(W0, p.w0[l], KP >> 2, 16 * p.NB, 16 * nb);
-    if (up) ps_fill<16>(W1, p.w1[l], KP >> 2, 16 * p.NB, 16 * nb);
+    gpe_fill<16, 256>(W0, p.w0[l], KP >> 2, 16 * p.NB, 16 * nb);
+    if (up) gpe_fill<16, 256>(W1, p.w1[l], KP >> 2, 16 * p.NB, 16 * nb);
     float invw0 = 1.f, invw1 = 1.f;
     if constexpr (H3) {
         float sw;
@@ -404,9 +340,9 @@ __global__ __launch_bounds__(256) void gpe_rnn_persist_bwd_kernel(PsBwdParams p)
             // both flags first, then the loads of both segments back to back (one latency instead of two), then the products
             PsA<H3, MAXS> A1, A0;
             const bool rec = t < T - 1;
-            if (up) ps_wait(p.flags + ((long)(l + 1) * T + t) * p.NRT + rt, need);       // dG_{l+1,t}: the layer above runs ahead
+            if (up) gpe_flag_wait(p.flags + ((long)(l + 1) * T + t) * p.NRT + rt, need);       // dG_{l+1,t}: the layer above runs ahead
             PS_STAMP(1);
-            if (rec) ps_wait(p.flags + ((long)l * T + t + 1) * p.NRT + rt, need);        // dG_{l,t+1}
+            if (rec) gpe_flag_wait(p.flags + ((long)l * T + t + 1) * p.NRT + rt, need);        // dG_{l,t+1}
             PS_STAMP(3);
             if (up)                                  // dG_{l+1,t} x W_ih_{l+1}
                 ps_load<H3, MAXS>(A1, __builtin_amdgcn_make_buffer_rsrc(p.dgx + (l + 1) * p.dg_sl + (long)t * p.dg_st, 0, nrec, 0x00020000),
@@ -431,17 +367,17 @@ __global__ __launch_bounds__(256) void gpe_rnn_persist_bwd_kernel(PsBwdParams p)
             __syncthreads();
             dh += (Cs[er * PS_LDB + eu] + Cs[(16 + er) * PS_LDB + eu]) + (Cs[(32 + er) * PS_LDB + eu] + Cs[(48 + er) * PS_LDB + eu]);
             if (rok && uok) {
-                const float tc = tanhf(ct);
-                const float dc = dh * og * (1.f - tc * tc) + cin;
+                float di, df, dg, dgo, cout;
+                gpe_lstm_cell_bwd(ig, fg, gg, og, ct, cp, dh, &cin, di, df, dg, dgo, cout);
                 float* gx = p.dgx + l * p.dg_sl + (long)row * p.dg_sb + (long)t * p.dg_st;
-                __hip_atomic_store(gx + unit, dc * gg * ig * (1.f - ig), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(gx + H + unit, dc * cp * fg * (1.f - fg), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(gx + 2 * H + unit, dc * ig * (1.f - gg * gg), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(gx + 3 * H + unit, dh * tc * og * (1.f - og), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                p.carry[((long)(t & 1) * L + l) * BH + (long)row * H + unit] = dc * fg;
+                __hip_atomic_store(gx + unit, di, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(gx + H + unit, df, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(gx + 2 * H + unit, dg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(gx + 3 * H + unit, dgo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                p.carry[((long)(t & 1) * L + l) * BH + (long)row * H + unit] = cout;
             }
             PS_STAMP(5);
-            ps_arrive(p.flags + ((long)l * T + t) * p.NRT + rt, p.trace ? p.trace + ((long)blockIdx.x * T + t) * 8 + 6 : nullptr);
+            gpe_flag_arrive_wg(p.flags + ((long)l * T + t) * p.NRT + rt, p.trace ? p.trace + ((long)blockIdx.x * T + t) * 8 + 6 : nullptr);
             PS_STAMP(7);
         }
     }

@@ -17,26 +17,17 @@
 //   * the next item's flags are polled ONCE and, when they stand, its loads are issued before the current item's products:
 //     the hand-off latency of one tile hides under the arithmetic of another (an item whose flags are not up yet is waited for
 //     after the current one — never before it: a wave that owns a single tile would wait for itself).
-// Inter-workgroup visibility: recipe R1 as in gpe_rnn_persist.hip — sc1 (write-through) stores of the payload, the storing wave
-// drains vmcnt, one relaxed agent-scope counter increment per (workgroup, tile, step); consumers poll relaxed and read sc1.
+// Inter-workgroup visibility: recipe R1 (gpe_device.h: hand-off), wave form — the storing wave drains, one counter increment per
+// (workgroup, tile, step).
 // Counter (l, slot, rt) counts the unit blocks that published h_{l, slot - 1} of tile rt; slot 0 = the start state.
-#include "gpe_common.h"
-#include <math.h>
+#include "gpe_device.h"
 
 extern "C" int gpe_debug_get(void);
 
 #define PM_MAXL 4
 #define PM_MAXS 8                 // k-steps of 32: K (= units) <= 256
-#define PM_SPIN_LIMIT (1u << 23)
 #define PM_FS 32                  // words per arrival counter: one 128-byte line each (counters that share a line serialise their
                                   // agent-scope increments and polls: measured 7 us per item with packed counters)
-#define PM_SA 4096.f
-#define PM_INV_SA (1.f / 4096.f)
-
-typedef unsigned pm_u32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 pm_f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 pm_f16x2 __attribute__((ext_vector_type(2)));
-typedef float pm_f32x2 __attribute__((ext_vector_type(2)));
 
 struct PmFwdParams {
     int L, T, Bn, H, NB, RG, NRT, KP;
@@ -66,31 +57,6 @@ struct PmFwdParams {
         if (p.trace && lane == 0) p.trace[(((long)blockIdx.x * PM_NW + wave) * (T * PM_MAXQ) + it) * 8 + (i)] = wall_clock64(); \
     } while (0)
 
-__device__ __forceinline__ float pm_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
-
-__device__ __forceinline__ unsigned pm_poll(const unsigned* flag)
-{
-    return __builtin_amdgcn_readfirstlane(__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-}
-
-__device__ __forceinline__ void pm_spin(const unsigned* flag, unsigned need)
-{
-    unsigned spins = 0;
-    while (pm_poll(flag) < need) {
-        __builtin_amdgcn_s_sleep(1);
-        if (++spins > PM_SPIN_LIMIT) __builtin_trap();
-    }
-}
-
-__device__ __forceinline__ void pm_split2(float a, float b, float s, unsigned& h, unsigned& l)
-{
-    const pm_f32x2 v = {a * s, b * s};
-    const pm_f16x2 hh = __builtin_convertvector(v, pm_f16x2);
-    const pm_f32x2 r = v - __builtin_convertvector(hh, pm_f32x2);
-    h = __builtin_bit_cast(unsigned, hh);
-    l = __builtin_bit_cast(unsigned, __builtin_convertvector(r, pm_f16x2));
-}
-
 // four consecutive floats v[0 .. nvalid) to dst (dst + 4 may run past the row: only valid elements are written); al = the
 // alignment every such quad of the tensor has: 16 / 8 / 4 bytes
 __device__ __forceinline__ void pm_store4(float* dst, const float (&v)[4], int nvalid, int al)
@@ -116,12 +82,12 @@ __device__ __forceinline__ void pm_store4(float* dst, const float (&v)[4], int n
 __device__ __forceinline__ void pm_publish_split(__amdgpu_buffer_rsrc_t rs, int rt, int j, int NS, int nb, int g, const float (&h4)[4])
 {
     unsigned hi01, hi23, lo01, lo23;
-    pm_split2(h4[0], h4[1], PM_SA, hi01, lo01);
-    pm_split2(h4[2], h4[3], PM_SA, hi23, lo23);
+    gpe_split2_f16(h4[0], h4[1], GPE_STATE_SA, hi01, lo01);
+    gpe_split2_f16(h4[2], h4[3], GPE_STATE_SA, hi23, lo23);
     const bool odd = g & 1;
     const unsigned s0 = odd ? hi01 : lo01, s1 = odd ? hi23 : lo23;
     const unsigned r0 = (unsigned)__shfl_xor((int)s0, 16), r1 = (unsigned)__shfl_xor((int)s1, 16);
-    pm_u32x4 piece;
+    gpe_u32x4 piece;
     piece[0] = odd ? r0 : hi01; piece[1] = odd ? r1 : hi23;
     piece[2] = odd ? lo01 : r0; piece[3] = odd ? lo23 : r1;
     const int kgroup = 2 * nb + (g >> 1);
@@ -131,28 +97,28 @@ __device__ __forceinline__ void pm_publish_split(__amdgpu_buffer_rsrc_t rs, int 
 
 // 16-byte payload load, sc1: served by L2 / the fabric, never by this CU's L1 (the producer stored sc1: no acquire fence needed).
 // Plain loads were measured too (every hsplit address is written once per launch, so a cached copy cannot be stale): no faster.
-__device__ __forceinline__ pm_u32x4 pm_ld(__amdgpu_buffer_rsrc_t rs, int off) { return __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 16); }
+__device__ __forceinline__ gpe_u32x4 pm_ld(__amdgpu_buffer_rsrc_t rs, int off) { return __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 16); }
 
 struct PmFwdItem {
-    pm_u32x4 hh[PM_MAXS], hl[PM_MAXS];       // h_{l,t-1}: leading / residual plane, k-step s
-    pm_u32x4 xh[PM_MAXS], xl[PM_MAXS];       // h_{l-1,t} (layers > 0)
+    gpe_u32x4 hh[PM_MAXS], hl[PM_MAXS];       // h_{l,t-1}: leading / residual plane, k-step s
+    gpe_u32x4 xh[PM_MAXS], xl[PM_MAXS];       // h_{l-1,t} (layers > 0)
     float e[4][4];                           // layer 0: the x-projection addend (gate, unit quad)
 };
 
 // products of k-steps [s_lo, s_hi) of one K segment: A = weight fragments from the LDS slice ([plane][KP / 8][64 columns][8 halves]),
 // B = the loaded planes.  The eight fragments of a k-step are read one k-step ahead of their twelve MFMAs (hipcc left alone reads
 // two fragments, waits, multiplies: the LDS latency of every pair was exposed), and consecutive MFMAs go to different accumulators.
-__device__ __forceinline__ void pm_mma(const pm_u32x4 (&bh)[PM_MAXS], const pm_u32x4 (&bl)[PM_MAXS], const char* W, int KP, int s_lo,
+__device__ __forceinline__ void pm_mma(const gpe_u32x4 (&bh)[PM_MAXS], const gpe_u32x4 (&bl)[PM_MAXS], const char* W, int KP, int s_lo,
                                        int s_hi, int j, int g, f32x4 (&acc)[4])
 {
     const int plane_b = KP * 128;                                   // (KP / 8) groups x 64 columns x 16 bytes
     const char* w0 = W + (g * 64 + j) * 16;
-    pm_u32x4 wh[2][4], wl[2][4];
+    gpe_u32x4 wh[2][4], wl[2][4];
     auto fetch = [&](int s, int buf) {
 #pragma unroll
         for (int n = 0; n < 4; ++n) {
-            wh[buf][n] = *reinterpret_cast<const pm_u32x4*>(w0 + s * 4096 + 256 * n);
-            wl[buf][n] = *reinterpret_cast<const pm_u32x4*>(w0 + s * 4096 + 256 * n + plane_b);
+            wh[buf][n] = *reinterpret_cast<const gpe_u32x4*>(w0 + s * 4096 + 256 * n);
+            wl[buf][n] = *reinterpret_cast<const gpe_u32x4*>(w0 + s * 4096 + 256 * n + plane_b);
         }
     };
     if (s_lo < s_hi) fetch(s_lo, 0);
@@ -163,26 +129,14 @@ __device__ __forceinline__ void pm_mma(const pm_u32x4 (&bh)[PM_MAXS], const pm_u
             if (s + 1 < s_hi) fetch(s + 1, buf ^ 1);
 #pragma unroll
             for (int n = 0; n < 4; ++n)
-                acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(pm_f16x8, wl[buf][n]), __builtin_bit_cast(pm_f16x8, bh[s]), acc[n], 0, 0, 0);
+                acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(gpe_f16x8, wl[buf][n]), __builtin_bit_cast(gpe_f16x8, bh[s]), acc[n], 0, 0, 0);
 #pragma unroll
             for (int n = 0; n < 4; ++n)
-                acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(pm_f16x8, wh[buf][n]), __builtin_bit_cast(pm_f16x8, bl[s]), acc[n], 0, 0, 0);
+                acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(gpe_f16x8, wh[buf][n]), __builtin_bit_cast(gpe_f16x8, bl[s]), acc[n], 0, 0, 0);
 #pragma unroll
             for (int n = 0; n < 4; ++n)
-                acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(pm_f16x8, wh[buf][n]), __builtin_bit_cast(pm_f16x8, bh[s]), acc[n], 0, 0, 0);
+                acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(gpe_f16x8, wh[buf][n]), __builtin_bit_cast(gpe_f16x8, bh[s]), acc[n], 0, 0, 0);
         }
-    }
-}
-
-// copy this workgroup's 64 columns of every 16-byte-piece group of a plane pack into LDS
-__device__ __forceinline__ void pm_fill(char* dst, const void* src, int ngroups, int Npad, int c0)
-{
-    const pm_u32x4* s = reinterpret_cast<const pm_u32x4*>(src);
-    pm_u32x4* d = reinterpret_cast<pm_u32x4*>(dst);
-    const int total = ngroups * 64;
-    for (int e = threadIdx.x; e < total; e += 64 * PM_NW) {
-        const int grp = e >> 6, c = e & 63;
-        d[e] = s[(long)grp * Npad + c0 + c];
     }
 }
 
@@ -207,7 +161,7 @@ __device__ __forceinline__ void pm_fwd_body(const PmFwdParams& p, const int l, c
         float sw0, sw1, inv1;
         gpe_h3_scale_of(p.s0[l][0], sw0, inv0);
         if (!L0) { gpe_h3_scale_of(p.s1[l][0], sw1, inv1); ratio = inv1 * sw0; }
-        inv0 *= PM_INV_SA;
+        inv0 *= GPE_STATE_INV_SA;
     }
     const long slot_bytes = 16L * NRT * KP * 4;
     const int al_sv = (H & 3) == 0 ? 16 : ((H & 1) == 0 ? 8 : 4);          // alignment of a unit quad inside [..][4H] / [..][H] rows
@@ -232,11 +186,7 @@ __device__ __forceinline__ void pm_fwd_body(const PmFwdParams& p, const int l, c
         }
     }
 
-    // the storing wave drains its write-through stores, one lane counts the workgroup in
-    auto publish = [&](int slot, int rt) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (lane == 0) __hip_atomic_fetch_add(flags_l + ((long)slot * NRT + rt) * PM_FS, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    };
+    auto publish = [&](int slot, int rt) { gpe_flag_arrive_wave(flags_l + ((long)slot * NRT + rt) * PM_FS); };
 
     // ---- slot 0: the start state of this workgroup's units, split and published like every later state ----
     for (int q = 0; q < nq; ++q) {
@@ -264,8 +214,8 @@ __device__ __forceinline__ void pm_fwd_body(const PmFwdParams& p, const int l, c
     };
     // item (t, rt) reads h_{l,t-1} = slot t of this layer and h_{l-1,t} = slot t + 1 of the layer below
     auto wait_ready = [&](int t, int rt) {
-        pm_spin(flags_l + ((long)t * NRT + rt) * PM_FS, need);
-        if (!L0) pm_spin(flags_dn + ((long)(t + 1) * NRT + rt) * PM_FS, need);
+        gpe_flag_wait(flags_l + ((long)t * NRT + rt) * PM_FS, need);
+        if (!L0) gpe_flag_wait(flags_dn + ((long)(t + 1) * NRT + rt) * PM_FS, need);
     };
     auto issue = [&](PmFwdItem& I, int t, int rt) {
         asm volatile("" ::: "memory");                              // the payload loads stay below the polls
@@ -315,8 +265,8 @@ __device__ __forceinline__ void pm_fwd_body(const PmFwdParams& p, const int l, c
         unsigned pv0 = need, pv1 = need;
         if (more) {
             tile_of(it + 1, t2, rt2);
-            pv0 = __hip_atomic_load(flags_l + ((long)t2 * NRT + rt2) * PM_FS, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (!L0) pv1 = __hip_atomic_load(flags_dn + ((long)(t2 + 1) * NRT + rt2) * PM_FS, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            pv0 = gpe_flag_load(flags_l + ((long)t2 * NRT + rt2) * PM_FS);
+            if (!L0) pv1 = gpe_flag_load(flags_dn + ((long)(t2 + 1) * NRT + rt2) * PM_FS);
         }
         PM_STAMP(0);
         const int row = 16 * rt + j;
@@ -373,9 +323,8 @@ __device__ __forceinline__ void pm_fwd_body(const PmFwdParams& p, const int l, c
                 cn[r] = gf[r] * cp[r] + gi[r] * gg[r];
                 h4[r] = (r < nvalid) ? go[r] * cn[r] : 0.f;
             } else {
-                gi[r] = pm_sigmoid(z[0][r]); gf[r] = pm_sigmoid(z[1][r]); gg[r] = tanhf(z[2][r]); go[r] = pm_sigmoid(z[3][r]);
-                cn[r] = gf[r] * cp[r] + gi[r] * gg[r];
-                h4[r] = (r < nvalid) ? go[r] * tanhf(cn[r]) : 0.f;
+                gpe_lstm_cell_fwd(z[0][r], z[1][r], z[2][r], z[3][r], cp[r], gi[r], gf[r], gg[r], go[r], cn[r]);
+                h4[r] = (r < nvalid) ? gpe_lstm_cell_h(go[r], cn[r]) : 0.f;
             }
         }
         c_keep[qi * 64] = make_float4(cn[0], cn[1], cn[2], cn[3]);
@@ -416,8 +365,8 @@ __global__ __launch_bounds__(64 * PM_NW) void gpe_rnn_pm_fwd_kernel(PmFwdParams 
     const int wbytes = p.KP * 256;                   // one slice: 2 planes x (KP / 8) groups x 64 columns x 16 bytes
     char* W0 = pm_smem;
     char* W1 = pm_smem + wbytes;
-    pm_fill(W0, p.w0[l], p.KP >> 2, 64 * p.NB, 64 * nb);
-    if (l > 0) pm_fill(W1, p.w1[l], p.KP >> 2, 64 * p.NB, 64 * nb);
+    gpe_fill<64, 64 * PM_NW>(W0, p.w0[l], p.KP >> 2, 64 * p.NB, 64 * nb);
+    if (l > 0) gpe_fill<64, 64 * PM_NW>(W1, p.w1[l], p.KP >> 2, 64 * p.NB, 64 * nb);
     __syncthreads();
     // behind the slices: what the waves keep per tile between steps (pm_fwd_body)
     char* keep = pm_smem + (p.L > 1 ? 2 : 1) * wbytes;

@@ -53,8 +53,6 @@ struct WvFwdCell {
 };
 struct WvFwdParams { int Bn, H, Npad, ncell; WvFwdCell cell[WV_MAXCELL]; };
 
-__device__ __forceinline__ float wv_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
-
 // stage rows [row0, row0+64) x K columns of `a` (row pitch `stride`, 16-B aligned, padded to 4) and the packed weight block
 // of this workgroup (columns n0 .. n0+16*NT of a [K/4][Npad][4] packed matrix) into LDS, then run the slab's MFMAs
 template <int NT, int KS>
@@ -234,21 +232,9 @@ __device__ __forceinline__ void wv_commit(const WvRegs<NT, KS>& R, int K, int Np
     }
 }
 
-// f16x3 products of one staged slab: A rows fp32 in LDS, scaled by the power of two `sA` and split into two fp16 terms right
-// after the read; B = the weight's planes in LDS; three MFMAs per 16 x 16 x 32 block, small terms first.  `split` as in wv_mma
-// (a <= 32-row tile: wave w = row tile (w & 1), K half (w >> 1)).
-typedef _Float16 wv_f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 wv_f16x2 __attribute__((ext_vector_type(2)));
-typedef float wv_f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned wv_u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void wv_split2(float a, float b, float s, unsigned& h, unsigned& l)
-{
-    const wv_f32x2 v = {a * s, b * s};
-    const wv_f16x2 hh = __builtin_convertvector(v, wv_f16x2);
-    const wv_f32x2 r = v - __builtin_convertvector(hh, wv_f32x2);
-    h = __builtin_bit_cast(unsigned, hh);
-    l = __builtin_bit_cast(unsigned, __builtin_convertvector(r, wv_f16x2));
-}
+// f16x3 products of one staged slab: A rows fp32 in LDS, scaled by the power of two `sA` (the state rows: GPE_STATE_SA,
+// gpe_device.h) and split into two fp16 terms right after the read; B = the weight's planes in LDS; three MFMAs per 16 x 16 x 32
+// block, small terms first.  `split` as in wv_mma (a <= 32-row tile: wave w = row tile (w & 1), K half (w >> 1)).
 template <int NT>
 __device__ __forceinline__ void wv_mma_h3(const float* As, const float* Ws, int lda, int kp, float sA, f32x4 (&acc)[NT],
                                           bool split = false)
@@ -264,19 +250,19 @@ __device__ __forceinline__ void wv_mma_h3(const float* As, const float* Ws, int 
     for (int st = s0; st < s1; ++st) {
         const float* ar = &As[(16 * rt + j) * lda + 32 * st + 8 * g];
         const float4 a0 = ld4(ar), a1 = ld4(ar + 4);
-        wv_u32x4 ah, al;
-        { unsigned h, l; wv_split2(a0.x, a0.y, sA, h, l); ah[0] = h; al[0] = l; }
-        { unsigned h, l; wv_split2(a0.z, a0.w, sA, h, l); ah[1] = h; al[1] = l; }
-        { unsigned h, l; wv_split2(a1.x, a1.y, sA, h, l); ah[2] = h; al[2] = l; }
-        { unsigned h, l; wv_split2(a1.z, a1.w, sA, h, l); ah[3] = h; al[3] = l; }
+        gpe_u32x4 ah, al;
+        { unsigned h, l; gpe_split2_f16(a0.x, a0.y, sA, h, l); ah[0] = h; al[0] = l; }
+        { unsigned h, l; gpe_split2_f16(a0.z, a0.w, sA, h, l); ah[1] = h; al[1] = l; }
+        { unsigned h, l; gpe_split2_f16(a1.x, a1.y, sA, h, l); ah[2] = h; al[2] = l; }
+        { unsigned h, l; gpe_split2_f16(a1.z, a1.w, sA, h, l); ah[3] = h; al[3] = l; }
         const float* wb = &Ws[(((4 * st + g) * 16 * NT) + j) * 4];
 #pragma unroll
         for (int n = 0; n < NT; ++n) {
-            const wv_u32x4 bh = *reinterpret_cast<const wv_u32x4*>(wb + 64 * n);
-            const wv_u32x4 bl = *reinterpret_cast<const wv_u32x4*>(wb + 64 * n + plane_f);
-            acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(wv_f16x8, al), __builtin_bit_cast(wv_f16x8, bh), acc[n], 0, 0, 0);
-            acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(wv_f16x8, ah), __builtin_bit_cast(wv_f16x8, bl), acc[n], 0, 0, 0);
-            acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(wv_f16x8, ah), __builtin_bit_cast(wv_f16x8, bh), acc[n], 0, 0, 0);
+            const gpe_u32x4 bh = *reinterpret_cast<const gpe_u32x4*>(wb + 64 * n);
+            const gpe_u32x4 bl = *reinterpret_cast<const gpe_u32x4*>(wb + 64 * n + plane_f);
+            acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(gpe_f16x8, al), __builtin_bit_cast(gpe_f16x8, bh), acc[n], 0, 0, 0);
+            acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(gpe_f16x8, ah), __builtin_bit_cast(gpe_f16x8, bl), acc[n], 0, 0, 0);
+            acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(gpe_f16x8, ah), __builtin_bit_cast(gpe_f16x8, bh), acc[n], 0, 0, 0);
         }
     }
 }
@@ -311,12 +297,6 @@ __device__ __forceinline__ void wv_mma(const float* As, const float* Ws, int lda
     }
 }
 
-// The recurrent state enters the fp16 pipe scaled by 2^12: |h| < 1 for every state an LSTM / GRU cell produces (o * tanh(c);
-// a convex combination of tanh values), start states up to |h0| < 16 stay finite, and a state down to 3e-5 keeps both terms
-// normal (smaller ones keep an absolute error < 1.5e-8).
-#define WV_H3_SA 4096.f
-#define WV_H3_INV_SA (1.f / 4096.f)
-
 // G = 4: LSTM (i,f,g,o)   G = 3: GRU (r,z,n).   H3: f16x3 arithmetic (gpe_math_set(4)) — weights as fp16 plane packs with their
 // amax words, the state rows split on the fly, three fp16 MFMAs per product block, fp32 accumulate (wv_mma_h3).
 template <int G, int KS, bool H3 = false>
@@ -344,7 +324,7 @@ __global__ __launch_bounds__(256, (KS <= 128 ? 2 : 1)) void gpe_rnn_wave_fwd_ker
         gpe_h3_scale_of(c.s0[0], sw0, h3_inv0);
         if (c.a1) gpe_h3_scale_of(c.s1[0], sw1, h3_inv1);
         h3_ratio = h3_inv0 * sw1;                     // = inv0 / inv1
-        h3_inv0 *= WV_H3_INV_SA; h3_inv1 *= WV_H3_INV_SA;
+        h3_inv0 *= GPE_STATE_INV_SA; h3_inv1 *= GPE_STATE_INV_SA;
     }
     f32x4 accH[G], accX[G];
 #pragma unroll
@@ -393,8 +373,8 @@ __global__ __launch_bounds__(256, (KS <= 128 ? 2 : 1)) void gpe_rnn_wave_fwd_ker
 #pragma unroll
                         for (int r = 0; r < 4; ++r) accH[n][r] *= h3_ratio;
                 }
-                if (G == 4 || seg == 0) wv_mma_h3<G>(As, Ws, lda, (kslab + 31) & ~31, WV_H3_SA, accH, split);
-                else wv_mma_h3<G>(As, Ws, lda, (kslab + 31) & ~31, WV_H3_SA, accX, split);
+                if (G == 4 || seg == 0) wv_mma_h3<G>(As, Ws, lda, (kslab + 31) & ~31, GPE_STATE_SA, accH, split);
+                else wv_mma_h3<G>(As, Ws, lda, (kslab + 31) & ~31, GPE_STATE_SA, accX, split);
             } else {
                 if (G == 4 || seg == 0) wv_mma<G>(As, Ws, lda, (kslab + 15) & ~15, accH, split);
                 else wv_mma<G>(As, Ws, lda, (kslab + 15) & ~15, accX, split);
@@ -434,15 +414,18 @@ __global__ __launch_bounds__(256, (KS <= 128 ? 2 : 1)) void gpe_rnn_wave_fwd_ker
             const int r = (tid >> 4) + 16 * it;
             if (r < rv) {
                 const long gr = row0 + r;
-                const float ig = wv_sigmoid(cs_at(r, u) + e0[it]);
-                const float fg = wv_sigmoid(cs_at(r, 16 + u) + e1[it]);
+                // gpe_lstm_cell_fwd's formulas in this kernel's own order, each C-tile read right in front of its activation: through
+                // the shared function the reads come first, the compiler then fuses the other product of c_t and every result of
+                // the diagonal launches moves in its last bits
+                const float ig = gpe_sigmoid(cs_at(r, u) + e0[it]);
+                const float fg = gpe_sigmoid(cs_at(r, 16 + u) + e1[it]);
                 const float gg = tanhf(cs_at(r, 32 + u) + e2[it]);
-                const float og = wv_sigmoid(cs_at(r, 48 + u) + e3[it]);
+                const float og = gpe_sigmoid(cs_at(r, 48 + u) + e3[it]);
                 const float cn = fg * e4[it] + ig * gg;
                 float* go = c.saved + gr * 4 * p.H;
                 go[unit] = ig; go[p.H + unit] = fg; go[2 * p.H + unit] = gg; go[3 * p.H + unit] = og;
                 c.c_out[gr * p.H + unit] = cn;
-                c.h_out[gr * c.h_stride + unit] = og * tanhf(cn);
+                c.h_out[gr * c.h_stride + unit] = gpe_lstm_cell_h(og, cn);
             }
         }
     } else {
@@ -451,8 +434,8 @@ __global__ __launch_bounds__(256, (KS <= 128 ? 2 : 1)) void gpe_rnn_wave_fwd_ker
             const int r = (tid >> 4) + 16 * it;
             if (r < rv) {
                 const long gr = row0 + r;
-                const float rg = wv_sigmoid(cs_at(r, u) + cs_at(r, 48 + u) + e0[it]);
-                const float zg = wv_sigmoid(cs_at(r, 16 + u) + cs_at(r, 64 + u) + e1[it]);
+                const float rg = gpe_sigmoid(cs_at(r, u) + cs_at(r, 48 + u) + e0[it]);
+                const float zg = gpe_sigmoid(cs_at(r, 16 + u) + cs_at(r, 64 + u) + e1[it]);
                 const float hn = cs_at(r, 32 + u) + bhn;
                 const float ng = tanhf(cs_at(r, 80 + u) + e2[it] + rg * hn);
                 float* go = c.saved + gr * 4 * p.H;
@@ -603,23 +586,18 @@ struct WvBwdParams { int Bn, H, K, Kpad_n, nz, jslabs, ncell, fuse, Hp; unsigned
 // pointwise kernel filled by atomicMax, transposed plane packs — and dropped: gpe_rnn_seq_bwd 1.00 -> 1.09 ms per step at cfg 2,
 // the atomics + the word memset + the split of 16 short slabs per workgroup cost more than the MFMAs they replace;
 // profiles/r04_e_recurrences.md.)
-// pointwise LSTM cell backward of one element (shared by the stand-alone kernel and the fused epilogue)
+// pointwise LSTM cell backward of one element (shared by the stand-alone kernel and the fused epilogue): the loads and stores
+// around gpe_lstm_cell_bwd
 __device__ __forceinline__ void wv_lstm_cell_bwd(const WvBwdCell& c, int H, long b, int u, long e, float dh)
 {
     const float* sv = c.saved + b * 4 * H;
     float* gx = c.dgx + b * c.dg_stride;
-    const float ig = sv[u], fg = sv[H + u], gg = sv[2 * H + u], og = sv[3 * H + u];
-    const float tc = tanhf(c.c[e]);
-    float dc = dh * og * (1.f - tc * tc);
-    if (c.carry_in) dc += c.carry_in[e];
-    gx[u] = dc * gg * ig * (1.f - ig);
-    gx[H + u] = dc * c.c_prev[e] * fg * (1.f - fg);
-    gx[2 * H + u] = dc * ig * (1.f - gg * gg);
-    gx[3 * H + u] = dh * tc * og * (1.f - og);
-    c.carry_out[e] = dc * fg;
+    float di, df, dg, dgo, cout;
+    gpe_lstm_cell_bwd(sv[u], sv[H + u], sv[2 * H + u], sv[3 * H + u], c.c[e], c.c_prev[e], dh, c.carry_in ? c.carry_in + e : nullptr,
+                      di, df, dg, dgo, cout);
+    gx[u] = di; gx[H + u] = df; gx[2 * H + u] = dg; gx[3 * H + u] = dgo;
+    c.carry_out[e] = cout;
 }
-
-typedef unsigned wv_st4 __attribute__((ext_vector_type(4)));
 
 template <int KS>
 __global__ __launch_bounds__(256) void gpe_rnn_wave_splitk_kernel(WvBwdParams p)
@@ -694,7 +672,7 @@ __global__ __launch_bounds__(256) void gpe_rnn_wave_splitk_kernel(WvBwdParams p)
                         const float4 v2 = ld4(&Cs[(r + 32) * ldc + cq]);
                         v.x += v2.x; v.y += v2.y; v.z += v2.z; v.w += v2.w;
                     }
-                    const wv_st4 o = {__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w)};
+                    const gpe_u32x4 o = {__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w)};
                     __builtin_amdgcn_raw_buffer_store_b128(o, rs, (int)(((long)(row0 + r) * Hp + n0 + cq) * 4), 0, 16);
                 }
             }
@@ -713,19 +691,17 @@ __global__ __launch_bounds__(256) void gpe_rnn_wave_splitk_kernel(WvBwdParams p)
         }
     }
     if (!p.fuse) return;
-    // ---- fused cell backward: count this workgroup in; the block's last arriver owns the pointwise pass (MI355X_MICROARCH.md
-    // "splitk-seam": sc1 partial stores, every storing wave drains, ONE relaxed agent-scope ticket, sc1 partial loads) ----
+    // ---- fused cell backward: count this workgroup in; the block's last arriver owns the pointwise pass (gpe_device.h: hand-off,
+    // the last-arriver ticket; MI355X_MICROARCH.md "splitk-seam") ----
     const int nparts = nsegs * p.nz;
     if (nparts > 1) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        gpe_drain_stores();
         __syncthreads();
-        if (tid == 0)
-            last_sh = __hip_atomic_fetch_add(p.cnt + ((long)ci * gridDim.x + blockIdx.x) * gridDim.y + blockIdx.y, 1u, __ATOMIC_RELAXED,
-                                             __HIP_MEMORY_SCOPE_AGENT);
+        if (tid == 0) last_sh = gpe_flag_ticket(p.cnt + ((long)ci * gridDim.x + blockIdx.x) * gridDim.y + blockIdx.y);
         __syncthreads();
         if (last_sh != (unsigned)(nparts - 1)) return;
     } else if (nparts == 1) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        gpe_drain_stores();
         __syncthreads();
     }
     const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc(c.part, 0, (unsigned)((long)2 * p.nz * p.Bn * Hp * 4), 0x00020000);
@@ -741,7 +717,7 @@ __global__ __launch_bounds__(256) void gpe_rnn_wave_splitk_kernel(WvBwdParams p)
             for (int s = 0; s < 2; ++s)
                 if ((c.nseg_mask >> s) & 1)
                     for (int zq = 0; zq < p.nz; ++zq) {
-                        const wv_st4 v = __builtin_amdgcn_raw_buffer_load_b128(rp, (int)((((long)(s * p.nz + zq) * p.Bn + b) * Hp + n0 + q4) * 4), 0, 16);
+                        const gpe_u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rp, (int)((((long)(s * p.nz + zq) * p.Bn + b) * Hp + n0 + q4) * 4), 0, 16);
                         dh4[0] += __uint_as_float(v[0]); dh4[1] += __uint_as_float(v[1]);
                         dh4[2] += __uint_as_float(v[2]); dh4[3] += __uint_as_float(v[3]);
                     }

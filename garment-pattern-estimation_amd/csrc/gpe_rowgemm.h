@@ -1,10 +1,13 @@
 // Shared pieces of the row-tile GEMM kernels (gpe_rowgemm.hip: LDS-streamed weights, any shape;
 // gpe_edgegemm.hip: register-stationary weights for the shipped edge-MLP sizes).
 #pragma once
-#include "gpe_common.h"
+#include "gpe_device.h"
 
 #define RG_BM 64
 #define RG_KSLAB 256
+#define RG_PB 16          // single-role / split edge kernels: rows a wave stages / finishes per tile
+#define RG_NPW 4          // ... max points per wave per tile (gather / aggregation paths)
+#define GPE_ENOTSUP_SHAPE 12345      // launch plumbing of the edge kernels: no instance for this shape (the caller tries the next family)
 
 enum { A_DENSE = 0, A_GATHER = 1 };
 enum { E_LINEAR = 0, E_EDGE_FWD = 1, E_BWD_INPLACE = 2, E_BWD_GATHER = 3 };
@@ -86,6 +89,39 @@ __device__ __forceinline__ void st4_stream(float* p, float4 v)
     const f32x4 vv = {v.x, v.y, v.z, v.w};
     asm volatile("global_store_dwordx4 %0, %1, off sc1" : : "v"(p), "v"(vv) : "memory");
 }
+
+// A wave has 256 architectural VGPRs + 256 accumulation VGPRs; MFMA takes its B operand from either file.  The resident
+// weights (208 registers) are pinned in AGPRs by hand: left to itself the allocator keeps them architectural and, in the
+// gather variants, spills them to scratch memory — reloaded every chunk behind an s_waitcnt vmcnt(0).
+__device__ __forceinline__ float rg_pin_agpr(float x)
+{
+    float a;
+    asm volatile("v_accvgpr_write_b32 %0, %1" : "=a"(a) : "v"(x));
+    return a;
+}
+__device__ __forceinline__ float4 rg_pin_agpr4(const float4 v)
+{
+    return make_float4(rg_pin_agpr(v.x), rg_pin_agpr(v.y), rg_pin_agpr(v.z), rg_pin_agpr(v.w));
+}
+
+// Wave-uniform choice among the (<= RG_NPW) P rows of a wave's points.  Arguments BY VALUE and selects on values: written
+// as `if (idx == q) dst = arr_q` the compiler turns the phi of loads into a load through a phi of pointers into the lambda
+// closure, which pins the closure AND every captured local (v[], act[], ...) in scratch memory — each access then drags
+// an s_waitcnt vmcnt(0) through the load pipeline.
+__device__ __forceinline__ float4 rg_sel4(const float4 a0, const float4 a1, const float4 a2, const float4 a3, int idx)
+{
+    float4 r = a0;
+    r.x = (idx == 1) ? a1.x : r.x; r.y = (idx == 1) ? a1.y : r.y; r.z = (idx == 1) ? a1.z : r.z; r.w = (idx == 1) ? a1.w : r.w;
+    r.x = (idx == 2) ? a2.x : r.x; r.y = (idx == 2) ? a2.y : r.y; r.z = (idx == 2) ? a2.z : r.z; r.w = (idx == 2) ? a2.w : r.w;
+    r.x = (idx == 3) ? a3.x : r.x; r.y = (idx == 3) ? a3.y : r.y; r.z = (idx == 3) ? a3.z : r.z; r.w = (idx == 3) ? a3.w : r.w;
+    return r;
+}
+
+// row of the [P|Q] table that belongs to (pseudo-)point x: x itself, or x / f = umulhi(x, magic) when a k > 16 point runs as f
+// pseudo-points (RgParams::pmagic).  Two forms: the choice at run time (magic == 0: points) or as a template parameter
+__device__ __forceinline__ long rg_prow(int x, unsigned magic) { return magic ? (long)__umulhi((unsigned)x, magic) : (long)x; }
+template <bool PSEUDO>
+__device__ __forceinline__ long rg_prow(int x, unsigned magic) { return PSEUDO ? (long)__umulhi((unsigned)x, magic) : (long)x; }
 
 // guarded load of 4 consecutive floats p[0..3] of which `nvalid` exist; vec => p is 16-B aligned
 __device__ __forceinline__ float4 ld4_guard(const float* p, int nvalid, bool vec)

@@ -32,8 +32,6 @@ struct SgParams {
     long y_zstride;
 };
 
-__device__ __forceinline__ float sg_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
-
 template <int NT, int EPI>
 __global__ __launch_bounds__(256) void gpe_smallgemm_kernel(SgParams p)
 {
@@ -209,8 +207,8 @@ __global__ __launch_bounds__(256) void gpe_smallgemm_kernel(SgParams p)
                 const int r = (tid >> 4) + 16 * it;
                 if (r < rv) {
                     const long gr = row0 + r;
-                    const float rg = sg_sigmoid(Cs[r * ldc + u] + xr[it]);
-                    const float zg = sg_sigmoid(Cs[r * ldc + 16 + u] + xz[it]);
+                    const float rg = gpe_sigmoid(Cs[r * ldc + u] + xr[it]);
+                    const float zg = gpe_sigmoid(Cs[r * ldc + 16 + u] + xz[it]);
                     const float hn = Cs[r * ldc + 32 + u] + bhn;
                     const float ng = tanhf(xn[it] + rg * hn);
                     float* go = p.gates + gr * 4 * p.H;
@@ -245,12 +243,12 @@ __global__ __launch_bounds__(256) void gpe_smallgemm_kernel(SgParams p)
                     const float zf = Cs[r * ldc + 16 + u] + xf[it];
                     const float zg = Cs[r * ldc + 32 + u] + xg[it];
                     const float zo = Cs[r * ldc + 48 + u] + xo[it];
-                    const float ig = sg_sigmoid(zi), fg = sg_sigmoid(zf), gg = tanhf(zg), og = sg_sigmoid(zo);
-                    const float cn = fg * cp[it] + ig * gg;
+                    float ig, fg, gg, og, cn;
+                    gpe_lstm_cell_fwd(zi, zf, zg, zo, cp[it], ig, fg, gg, og, cn);
                     float* go = p.gates + gr * 4 * p.H;
                     go[unit] = ig; go[p.H + unit] = fg; go[2 * p.H + unit] = gg; go[3 * p.H + unit] = og;
                     p.c_out[gr * p.H + unit] = cn;
-                    p.h_out[gr * p.h_stride + unit] = og * tanhf(cn);
+                    p.h_out[gr * p.h_stride + unit] = gpe_lstm_cell_h(og, cn);
                 }
             }
         }

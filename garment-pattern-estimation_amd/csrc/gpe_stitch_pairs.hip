@@ -17,7 +17,7 @@
 //   kernels (any width / depth) and fed to the same epilogue.
 // gpe_stitch_select: one workgroup per garment; an edge's best pair survives iff its partner's table entry is the same word;
 //   survivors are ranked by order key.
-#include "gpe_common.h"
+#include "gpe_device.h"
 #include <math.h>
 
 #define SP_MAXP 32
@@ -33,7 +33,7 @@ static inline int sp_ldw(int H) { const int np = sp_nb(H) * 16; return (np % 32 
 static inline int sp_lda(int H) { return ((H / 4) | 1) * 4; }                                               // 16 rows x 4 k hit 64 banks
 
 // ---- the shared epilogue ---------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool sp_positive(float x) { return 1.f / (1.f + expf(-x)) > 0.5f; }
+__device__ __forceinline__ bool sp_positive(float x) { return gpe_sigmoid(x) > 0.5f; }
 
 // tab / dense: this garment's table [E] and dense logits [E][E] (or NULL)
 __device__ __forceinline__ void sp_epilogue(float logit, int pi, int r, int pj, int c, int L, int E, unsigned long long* tab,
@@ -210,18 +210,6 @@ __global__ __launch_bounds__(SP_TPB) void gpe_stitch_pairs_fwd_kernel(SpFwdParam
 // 8 x 16 edges = 128 pair rows per workgroup, a wave = 32 rows x all columns (every B fragment feeds two row blocks).
 #define SP3_TI 8
 #define SP3_TJ 16
-typedef _Float16 sp_f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 sp_f16x2 __attribute__((ext_vector_type(2)));
-typedef float sp_f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned sp_u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void sp_split2(float a, float b, float s, unsigned& h, unsigned& l)
-{
-    const sp_f32x2 v = {a * s, b * s};
-    const sp_f16x2 hh = __builtin_convertvector(v, sp_f16x2);
-    const sp_f32x2 r = v - __builtin_convertvector(hh, sp_f32x2);
-    h = __builtin_bit_cast(unsigned, hh);
-    l = __builtin_bit_cast(unsigned, __builtin_convertvector(r, sp_f16x2));
-}
 __device__ __forceinline__ float sp_wave_max(float m)
 {
 #pragma unroll
@@ -282,8 +270,8 @@ __global__ __launch_bounds__(SP_TPB) void gpe_stitch_pairs_h3_kernel(SpFwdParams
                 m = fmaxf(fmaxf(m, fmaxf(v.x, v.y)), fmaxf(v.z, v.w));
             } else {
                 uint2 h, l;
-                sp_split2(v.x, v.y, sa, h.x, l.x);
-                sp_split2(v.z, v.w, sa, h.y, l.y);
+                gpe_split2_f16(v.x, v.y, sa, h.x, l.x);
+                gpe_split2_f16(v.z, v.w, sa, h.y, l.y);
                 *reinterpret_cast<uint2*>(hiP + row * ldh + 4 * q) = h;
                 *reinterpret_cast<uint2*>(loP + row * ldh + 4 * q) = l;
             }
@@ -315,22 +303,22 @@ __global__ __launch_bounds__(SP_TPB) void gpe_stitch_pairs_h3_kernel(SpFwdParams
             SP_SLAB_STORE(Ws, N4);
             __syncthreads();
             if (k0 + 32 < KP) SP_SLAB_LOAD(pl + (long)(k0 + 32) * LDW, N4);
-            sp_u32x4 ah[2], al[2];
+            gpe_u32x4 ah[2], al[2];
 #pragma unroll
             for (int m = 0; m < 2; ++m) {
-                ah[m] = *reinterpret_cast<const sp_u32x4*>(hiP + (row0 + 16 * m + lr) * ldh + k0 + 8 * lq);
-                al[m] = *reinterpret_cast<const sp_u32x4*>(loP + (row0 + 16 * m + lr) * ldh + k0 + 8 * lq);
+                ah[m] = *reinterpret_cast<const gpe_u32x4*>(hiP + (row0 + 16 * m + lr) * ldh + k0 + 8 * lq);
+                al[m] = *reinterpret_cast<const gpe_u32x4*>(loP + (row0 + 16 * m + lr) * ldh + k0 + 8 * lq);
             }
             const float* wb = Ws + (lq * LDW + lr) * 4;
 #pragma unroll
             for (int nb = 0; nb < NB; ++nb) {
-                const sp_u32x4 bh = *reinterpret_cast<const sp_u32x4*>(wb + 64 * nb);
-                const sp_u32x4 bl = *reinterpret_cast<const sp_u32x4*>(wb + 64 * nb + 16 * LDW);
+                const gpe_u32x4 bh = *reinterpret_cast<const gpe_u32x4*>(wb + 64 * nb);
+                const gpe_u32x4 bl = *reinterpret_cast<const gpe_u32x4*>(wb + 64 * nb + 16 * LDW);
 #pragma unroll
                 for (int m = 0; m < 2; ++m) {
-                    acc[m][nb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(sp_f16x8, al[m]), __builtin_bit_cast(sp_f16x8, bh), acc[m][nb], 0, 0, 0);
-                    acc[m][nb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(sp_f16x8, ah[m]), __builtin_bit_cast(sp_f16x8, bl), acc[m][nb], 0, 0, 0);
-                    acc[m][nb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(sp_f16x8, ah[m]), __builtin_bit_cast(sp_f16x8, bh), acc[m][nb], 0, 0, 0);
+                    acc[m][nb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(gpe_f16x8, al[m]), __builtin_bit_cast(gpe_f16x8, bh), acc[m][nb], 0, 0, 0);
+                    acc[m][nb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(gpe_f16x8, ah[m]), __builtin_bit_cast(gpe_f16x8, bl), acc[m][nb], 0, 0, 0);
+                    acc[m][nb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(gpe_f16x8, ah[m]), __builtin_bit_cast(gpe_f16x8, bh), acc[m][nb], 0, 0, 0);
                 }
             }
         }
@@ -376,8 +364,8 @@ __global__ __launch_bounds__(SP_TPB) void gpe_stitch_pairs_h3_kernel(SpFwdParams
         const int row = row0 + 16 * mb + lr;
         float s = 0.f;
         for (int g = lq; g * 8 < H; g += 4) {
-            const sp_f16x8 h8 = *reinterpret_cast<const sp_f16x8*>(hiP + row * ldh + 8 * g);
-            const sp_f16x8 l8 = *reinterpret_cast<const sp_f16x8*>(loP + row * ldh + 8 * g);
+            const gpe_f16x8 h8 = *reinterpret_cast<const gpe_f16x8*>(hiP + row * ldh + 8 * g);
+            const gpe_f16x8 l8 = *reinterpret_cast<const gpe_f16x8*>(loP + row * ldh + 8 * g);
 #pragma unroll
             for (int j = 0; j < 8; ++j)
                 if (8 * g + j < H) s = fmaf((float)h8[j] + (float)l8[j], wf[8 * g + j], s);

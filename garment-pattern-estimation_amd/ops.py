@@ -1239,8 +1239,8 @@ class RNNStackFn(torch.autograd.Function):
             if l > 0:
                 a, b = planned_planes(w_ih, K_GATES_H3)
                 pl_ih.append(a); am_ih.append(b)
-        # (h0_ok: the fp16-pipe kernels scale the state rows by 2^12 before the fp16 split — a start state of magnitude >= 16 would
-        # overflow to inf; rnn_stack decides)
+        # (h0_ok: the fp16-pipe kernels scale the state rows by GPE_STATE_SA = 2^12 (csrc/gpe_device.h) before the fp16 split — a start
+        # state of magnitude >= 16 would overflow to inf; rnn_stack decides)
         h3 = bool(h0_ok) and all(t is not None for t in pl_hh + am_hh + pl_ih[1:] + am_ih[1:])
         keep = (whh, wih, biases, pl_hh, am_hh, pl_ih, am_ih)   # operands stay referenced until the launches are queued
         ws_n = L.query('gpe_rnn_seq_fwd_ws', G, Lr, T, Bn, Hh)    # arrival counters of the persistent launch (0: diagonal launches)
