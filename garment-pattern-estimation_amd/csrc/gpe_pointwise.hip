@@ -1302,7 +1302,8 @@ extern "C" int gpe_gru_cell_bwd(const float* dh_out, long dho_stride, const floa
 
 // ---------------------------------------------------------------------------------------------------------
 // sparsemax over rows of width W <= 32 (sparsemax.Sparsemax(dim=1), /root/reference/nn/nets.py:225; Martins &
-// Astudillo 2016): out = max(z - tau, 0), tau from the sorted-cumsum support rule; backward nz*(g - mean_nz(g)).
+// Astudillo 2016): out = max((z - max) - tau, 0), tau from the sorted-cumsum support rule on the max-shifted row (as the
+// published implementation does); backward nz*(g - mean_nz(g)).
 // One row per lane, the row sorted in registers by a fully unrolled odd-even transposition network.
 // ---------------------------------------------------------------------------------------------------------
 #define SPX_W 32
@@ -1322,15 +1323,19 @@ __global__ __launch_bounds__(256) void gpe_sparsemax_fwd_kernel(const float* __r
             v[i] = fmaxf(a, b); v[i + 1] = fminf(a, b);          // descending
         }
     }
+    // sparsemax(z) = sparsemax(z - c): the rule runs on z - max, where the cumulative sum and tau keep their fp32 precision
+    // whatever the magnitude of the scores (on raw scores near 1e3 the 1e-4 of a support decision is below one ulp of cs)
+    const float mx = v[0];
     float cs = 0.f, tau = 0.f;
 #pragma unroll
     for (int i = 0; i < SPX_W; ++i) {
         if (i < W) {
-            cs += v[i];
-            if (1.f + (float)(i + 1) * v[i] > cs) tau = (cs - 1.f) / (float)(i + 1);   // support grows monotonically
+            const float vi = v[i] - mx;
+            cs += vi;
+            if (1.f + (float)(i + 1) * vi > cs) tau = (cs - 1.f) / (float)(i + 1);   // support grows monotonically
         }
     }
-    for (int i = 0; i < W; ++i) out[r * ldo + i] = fmaxf(z[r * ldz + i] - tau, 0.f);
+    for (int i = 0; i < W; ++i) out[r * ldo + i] = fmaxf((z[r * ldz + i] - mx) - tau, 0.f);
 }
 
 __global__ __launch_bounds__(256) void gpe_sparsemax_bwd_kernel(const float* __restrict__ out, int ldo,
@@ -1394,12 +1399,14 @@ __global__ __launch_bounds__(256) void gpe_sparsemax_loss_kernel(const float* __
                 v[i] = fmaxf(a, b); v[i + 1] = fminf(a, b);
             }
         }
+        const float mx = v[0];                                   // max-shifted scores, as in the forward above
         float cs = 0.f, tau = 0.f;
 #pragma unroll
         for (int i = 0; i < SPX_W; ++i) {
             if (i < W) {
-                cs += v[i];
-                if (1.f + (float)(i + 1) * v[i] > cs) tau = (cs - 1.f) / (float)(i + 1);
+                const float vi = v[i] - mx;
+                cs += vi;
+                if (1.f + (float)(i + 1) * vi > cs) tau = (cs - 1.f) / (float)(i + 1);
             }
         }
         int t = target[r];
@@ -1407,7 +1414,7 @@ __global__ __launch_bounds__(256) void gpe_sparsemax_loss_kernel(const float* __
         const float inv = 1.f / (float)rows;
         float pp = 0.f, dot = 0.f;
         for (int i = 0; i < W; ++i) {
-            const float xi = x[r * ldx + i];
+            const float xi = x[r * ldx + i] - mx;                // <p - e_t, x> == <p - e_t, x - max>: sum(p - e_t) = 0
             const float p = fmaxf(xi - tau, 0.f);
             const float d = p - (i == t ? 1.f : 0.f);
             pp += p * p;
