@@ -35,9 +35,55 @@ static inline int sp_lda(int H) { return ((H / 4) | 1) * 4; }                   
 // ---- the shared epilogue ---------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ bool sp_positive(float x) { return gpe_sigmoid(x) > 0.5f; }
 
-// tab / dense: this garment's table [E] and dense logits [E][E] (or NULL)
+// ---- evaluation against ground-truth stitches (the EVAL instantiations; metrics/composed_loss.py:83-126 over all pairs) -------------
+// what a thread gathers over its pairs: the BCE-with-logits terms (fp32 each, summed in fp64) and the packed counters
+//   a = pairs | correct << 16        b = true positives | predicted positives << 10 | ground-truth positives << 20
+// (a workgroup sees at most 512 pairs, so no field overflows before the workgroup's totals are unpacked)
+struct SpEvalAcc { double loss; int a, b; };
+
+// mask: this garment's label bits [E][ceil(E / 32)]
+__device__ __forceinline__ void sp_eval_pair(float x, int ei, int ej, int E, const unsigned* mask, SpEvalAcc& ev)
+{
+    const bool y = (mask[(long)ei * ((E + 31) >> 5) + (ej >> 5)] >> (ej & 31)) & 1u;
+    const bool pos = sp_positive(x);
+    // relu(-+x) + log1p(exp(-|x|)): both summands are non-negative
+    ev.loss += (double)(fmaxf(y ? -x : x, 0.f) + log1pf(expf(-fabsf(x))));
+    ev.a += 1 + (pos == y ? 1 << 16 : 0);
+    ev.b += (pos && y ? 1 : 0) + (pos ? 1 << 10 : 0) + (y ? 1 << 20 : 0);
+}
+
+// every thread of the workgroup calls this once.  Fixed order: xor butterfly inside a wave, then the waves in order through LDS.
+// The fp64 partial goes to the workgroup's own slot; the integer counters are added to the garment's two words
+//   cnt[0] = pairs | correct << 32       cnt[1] = true positives | predicted positives << 21 | ground-truth positives << 42
+// by integer atomics (order-independent; a garment has fewer than 2^17 pairs).
+__device__ __forceinline__ void sp_eval_commit(SpEvalAcc ev, double* slot, unsigned long long* cnt)
+{
+    __shared__ double s_loss[SP_TPB / 64];
+    __shared__ int s_a[SP_TPB / 64], s_b[SP_TPB / 64];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        ev.loss += __shfl_xor(ev.loss, o);
+        ev.a += __shfl_xor(ev.a, o);
+        ev.b += __shfl_xor(ev.b, o);
+    }
+    const int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { s_loss[w] = ev.loss; s_a[w] = ev.a; s_b[w] = ev.b; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double l = s_loss[0];
+        int a = s_a[0], b = s_b[0];
+        for (int i = 1; i < SP_TPB / 64; ++i) { l += s_loss[i]; a += s_a[i]; b += s_b[i]; }
+        *slot = l;
+        if (a) atomicAdd(cnt, (unsigned long long)(a & 0xffff) | ((unsigned long long)(a >> 16) << 32));
+        if (b) atomicAdd(cnt + 1, (unsigned long long)(b & 1023) | ((unsigned long long)((b >> 10) & 1023) << 21) |
+                                      ((unsigned long long)(b >> 20) << 42));
+    }
+}
+
+// tab / dense: this garment's table [E] and dense logits [E][E] (or NULL); EVAL: mask = this garment's label bits, ev = the thread's sums
+template <bool EVAL>
 __device__ __forceinline__ void sp_epilogue(float logit, int pi, int r, int pj, int c, int L, int E, unsigned long long* tab,
-                                            float* dense)
+                                            float* dense, const unsigned* mask, SpEvalAcc& ev)
 {
     const int ei = pi * L + r, ej = pj * L + c;
     if (dense) dense[(long)ei * E + ej] = logit;
@@ -47,6 +93,7 @@ __device__ __forceinline__ void sp_epilogue(float logit, int pi, int r, int pj, 
         atomicMax(tab + ei, v);
         atomicMax(tab + ej, v);
     }
+    if constexpr (EVAL) sp_eval_pair(logit, ei, ej, E, mask, ev);
 }
 
 __device__ __forceinline__ int sp_count(const int32_t* ne, int L)
@@ -66,12 +113,27 @@ __global__ void gpe_stitch_pairs_pack_kernel(const float* w, int ldw, int N, int
 
 // ---- fused kernels ---------------------------------------------------------------------------------------------------------------
 struct SpFwdParams {
+    static constexpr bool EVAL = false;
     const float* ab; int ldab; int H; int nl;
     const float* wpk; const float* planes; const unsigned* w_amax; const float* last;
     const int32_t* ne; int B, P, L;
     unsigned long long* table; float* dense;
     int lda, nTj, KP;
 };
+// the evaluating instantiations carry the label mask [B][E][ceil(E / 32)], the loss slab [B][ceil(E / 8)^2] (tile (ti, tj) of
+// either kernel owns slot ti * ceil(E / 8) + tj) and the counter words [B][2]
+struct SpEvalParams : SpFwdParams {
+    static constexpr bool EVAL = true;
+    const unsigned* mask; double* slab; unsigned long long* cnt;
+};
+__device__ __forceinline__ const unsigned* sp_mask_of(const SpFwdParams&, int, int) { return nullptr; }
+__device__ __forceinline__ const unsigned* sp_mask_of(const SpEvalParams& p, int b, int E) { return p.mask + (long)b * E * ((E + 31) >> 5); }
+__device__ __forceinline__ void sp_tile_commit(const SpFwdParams&, const SpEvalAcc&, int, int, int, int) {}
+__device__ __forceinline__ void sp_tile_commit(const SpEvalParams& p, const SpEvalAcc& ev, int b, int E, int ti, int tj)
+{
+    const int n8 = (E + 7) >> 3;
+    sp_eval_commit(ev, p.slab + ((long)b * n8 + ti) * n8 + tj, p.cnt + 2 * (long)b);
+}
 
 template <int NB> struct SpLdw { static constexpr int v = (NB * 16) % 32 == 16 ? NB * 16 : NB * 16 + 16; };
 
@@ -117,9 +179,10 @@ __device__ __forceinline__ bool sp_tile_setup(const SpFwdParams& p, int b, int t
                                     SP_ST1(5, dst, n4) SP_ST1(6, dst, n4) SP_ST1(7, dst, n4) SP_ST1(8, dst, n4) } while (0)
 
 // exact fp32: 8 x 8 edges = 64 pair rows, a wave = 16 rows x all columns
-template <int NB>
-__global__ __launch_bounds__(SP_TPB) void gpe_stitch_pairs_fwd_kernel(SpFwdParams p)
+template <int NB, class PT>
+__global__ __launch_bounds__(SP_TPB) void gpe_stitch_pairs_fwd_kernel(PT p)
 {
+    constexpr bool EVAL = PT::EVAL;
     constexpr int LDW = SpLdw<NB>::v, NPRE = (SP_KS * LDW / 4 + SP_TPB - 1) / SP_TPB;
     static_assert(NPRE <= 9, "a slab is at most 9 float4 per thread");
     extern __shared__ float sp_smem[];
@@ -191,15 +254,18 @@ __global__ __launch_bounds__(SP_TPB) void gpe_stitch_pairs_fwd_kernel(SpFwdParam
     for (int k = lq; k < H; k += 4) s = fmaf(act[(row0 + lr) * lda + k], wl[k], s);
     s += __shfl_xor(s, 16);
     s += __shfl_xor(s, 32);
+    SpEvalAcc ev = {0.0, 0, 0};
     if (lq == 0) {
         const int row = row0 + lr;
         const int ii = row >> 3, jj = SP_T + (row & 7);
         const int pi = s_pan[ii], pj = s_pan[jj];
         if (pi >= 0 && pj > pi) {
             const float logit = p.last[2] * fmaxf(s + wl[H], 0.f) + p.last[3];
-            sp_epilogue(logit, pi, s_edg[ii], pj, s_edg[jj], L, E, p.table + (long)b * E, p.dense ? p.dense + (long)b * E * E : nullptr);
+            sp_epilogue<EVAL>(logit, pi, s_edg[ii], pj, s_edg[jj], L, E, p.table + (long)b * E,
+                              p.dense ? p.dense + (long)b * E * E : nullptr, sp_mask_of(p, b, E), ev);
         }
     }
+    sp_tile_commit(p, ev, b, E, ti, tj);
 }
 
 // ---- f16x3: the fp16 pipe on normalised two-term splits, fp32 accumulate ------------------------------------------------------------
@@ -233,9 +299,10 @@ __global__ void gpe_stitch_pairs_planes_kernel(const float* wt, int K, int ldw, 
     out[o + 32 * ldw] = l;
 }
 
-template <int NB>
-__global__ __launch_bounds__(SP_TPB) void gpe_stitch_pairs_h3_kernel(SpFwdParams p)
+template <int NB, class PT>
+__global__ __launch_bounds__(SP_TPB) void gpe_stitch_pairs_h3_kernel(PT p)
 {
+    constexpr bool EVAL = PT::EVAL;
     constexpr int LDW = SpLdw<NB>::v, NPRE = (SP_KS * LDW / 4 + SP_TPB - 1) / SP_TPB, N4 = SP_KS * LDW / 4;
     static_assert(NPRE <= 9, "a slab is at most 9 float4 per thread");
     extern __shared__ float sp_smem[];
@@ -359,6 +426,7 @@ __global__ __launch_bounds__(SP_TPB) void gpe_stitch_pairs_h3_kernel(SpFwdParams
     __syncthreads();
     // H -> 1 on the planes of the last activation: lane (lr, lq) sums the 8-k groups lq, lq + 4, ... of rows row0 + lr, + 16
     const float* wf = wl;
+    SpEvalAcc ev = {0.0, 0, 0};
 #pragma unroll
     for (int mb = 0; mb < 2; ++mb) {
         const int row = row0 + 16 * mb + lr;
@@ -377,10 +445,12 @@ __global__ __launch_bounds__(SP_TPB) void gpe_stitch_pairs_h3_kernel(SpFwdParams
             const int pi = s_pan[ii], pj = s_pan[jj];
             if (pi >= 0 && pj > pi) {
                 const float logit = p.last[2] * fmaxf(fmaf(s, inv_a, wf[H]), 0.f) + p.last[3];
-                sp_epilogue(logit, pi, s_edg[ii], pj, s_edg[jj], L, E, p.table + (long)b * E, p.dense ? p.dense + (long)b * E * E : nullptr);
+                sp_epilogue<EVAL>(logit, pi, s_edg[ii], pj, s_edg[jj], L, E, p.table + (long)b * E,
+                                  p.dense ? p.dense + (long)b * E * E : nullptr, sp_mask_of(p, b, E), ev);
             }
         }
     }
+    sp_tile_commit(p, ev, b, E, ti, tj);
 }
 
 // ---- generic route: rows of the i-edges [c0, c1) (pattern-level ids) -----------------------------------------------------------------
@@ -414,18 +484,44 @@ __global__ void gpe_stitch_pairs_rows_kernel(const float* edges, const int32_t* 
     }
 }
 
+// EVAL: one workgroup per (garment, i-edge) walks the PRESENT edges of the later panels in position order, so that the grouping of
+// the fp64 sums does not depend on how many unused slots the caller's layout has; grid (1, B * (c1 - c0)), slot = the i-edge's id
+template <bool EVAL>
 __global__ void gpe_stitch_pairs_reduce_kernel(const float* y, long ldy, const int32_t* ne, int P, int L, int c0, int c1,
-                                               long rows_chunk, unsigned long long* table, float* dense)
+                                               long rows_chunk, unsigned long long* table, float* dense, const unsigned* mask,
+                                               double* slab, unsigned long long* cnt)
 {
     const int E = P * L;
     const int b = blockIdx.y / (c1 - c0), ei = c0 + blockIdx.y - b * (c1 - c0);
-    const int ej = blockIdx.x * blockDim.x + threadIdx.x;
     const int pi = ei / L, r = ei - pi * L;
-    if (ej < (pi + 1) * L || ej >= E) return;
-    const int pj = ej / L, c = ej - pj * L;
-    if (r >= sp_count(ne + (long)b * P + pi, L) || c >= sp_count(ne + (long)b * P + pj, L)) return;
-    const long row = sp_row_off(ei, L, E) - sp_row_off(c0, L, E) + (ej - (pi + 1) * L);
-    sp_epilogue(y[((long)b * rows_chunk + row) * ldy], pi, r, pj, c, L, E, table + (long)b * E, dense ? dense + (long)b * E * E : nullptr);
+    SpEvalAcc ev = {0.0, 0, 0};
+    if constexpr (EVAL) {
+        __shared__ int s_off[SP_MAXP + 1];
+        if (r >= sp_count(ne + (long)b * P + pi, L)) return;            // block-uniform
+        if (threadIdx.x == 0) {
+            int o = 0;
+            for (int q = 0; q < P; ++q) { s_off[q] = o; o += sp_count(ne + (long)b * P + q, L); }
+            s_off[P] = o;
+        }
+        __syncthreads();
+        const long row0 = sp_row_off(ei, L, E) - sp_row_off(c0, L, E) - (long)(pi + 1) * L;
+        for (int pos = s_off[pi + 1] + threadIdx.x; pos < s_off[P]; pos += blockDim.x) {
+            int pj = pi + 1;
+            while (pos >= s_off[pj + 1]) ++pj;
+            const int c = pos - s_off[pj];
+            sp_epilogue<true>(y[((long)b * rows_chunk + row0 + pj * L + c) * ldy], pi, r, pj, c, L, E, table + (long)b * E,
+                              dense ? dense + (long)b * E * E : nullptr, mask + (long)b * E * ((E + 31) >> 5), ev);
+        }
+        sp_eval_commit(ev, slab + (long)b * E + ei, cnt + 2 * (long)b);
+    } else {
+        const int ej = blockIdx.x * blockDim.x + threadIdx.x;
+        if (ej < (pi + 1) * L || ej >= E) return;
+        const int pj = ej / L, c = ej - pj * L;
+        if (r >= sp_count(ne + (long)b * P + pi, L) || c >= sp_count(ne + (long)b * P + pj, L)) return;
+        const long row = sp_row_off(ei, L, E) - sp_row_off(c0, L, E) + (ej - (pi + 1) * L);
+        sp_epilogue<false>(y[((long)b * rows_chunk + row) * ldy], pi, r, pj, c, L, E, table + (long)b * E,
+                           dense ? dense + (long)b * E * E : nullptr, nullptr, ev);
+    }
 }
 
 // ---- selection -------------------------------------------------------------------------------------------------------------------
@@ -472,6 +568,92 @@ __global__ __launch_bounds__(SP_TPB) void gpe_stitch_select_kernel(const unsigne
     if (tid == 0) nums[b] = cnt;
 }
 
+// ---- ground-truth labels and the finalisation of an evaluating pass -------------------------------------------------------------------
+// mask[b][a][c / 32] bit c % 32 and its transpose for every stitch (a, c) of garment b; ids outside 0 .. E - 1 are ignored.
+// grid (ceil(S / 256), B); integer atomicOr: duplicates and arrival order do not matter
+__global__ void gpe_stitch_pairs_labels_kernel(const int32_t* st, const int32_t* nums, int S, int E, unsigned* mask)
+{
+    const int b = blockIdx.y, s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= min(nums[b], S)) return;
+    const int a = st[((long)b * 2 + 0) * S + s], c = st[((long)b * 2 + 1) * S + s];
+    if (a < 0 || a >= E || c < 0 || c >= E) return;
+    const int W = (E + 31) >> 5;
+    unsigned* m = mask + (long)b * E * W;
+    atomicOr(m + (long)a * W + (c >> 5), 1u << (c & 31));
+    atomicOr(m + (long)c * W + (a >> 5), 1u << (a & 31));
+}
+
+__device__ __forceinline__ float sp_ratio(long long num, long long den) { return den ? (float)num / (float)den : 0.f; }
+
+// ONE workgroup of 16 waves: wave w takes the garments w, w + 16, ...  A garment's slab is `slots` doubles in groups of `group`
+// consecutive slots (<= 64 groups): lane g adds group g in slot order, then the groups are added in order, so zero slots (tiles
+// without a pair, unused edge slots) change nothing; the call's total adds loss_sum[0 .. B) in order.
+#define SP_FIN_TPB 1024
+__global__ __launch_bounds__(SP_FIN_TPB) void gpe_stitch_eval_finalize_kernel(const double* slab, long slots, int group,
+                                                                              const unsigned long long* cnt, const unsigned* mask,
+                                                                              const int32_t* stitches, const int32_t* nums, int B,
+                                                                              int P, int L, double* loss_sum, int32_t* counts,
+                                                                              float* metrics)
+{
+    __shared__ long long s_tot[SP_FIN_TPB / 64][7];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, E = P * L, S = E / 2, W = (E + 31) >> 5;
+    const int ngroups = (int)(slots / group);
+    long long tot[7] = {0, 0, 0, 0, 0, 0, 0};
+    for (int b = w; b < B; b += SP_FIN_TPB / 64) {
+        double g = 0.0;
+        if (lane < ngroups) {
+            const double* src = slab + (long)b * slots + (long)lane * group;
+#pragma unroll 8
+            for (int i = 0; i < group; ++i) g += src[i];
+        }
+        double sum = 0.0;
+#pragma unroll 1
+        for (int q = 0; q < ngroups; ++q) sum += __shfl(g, q);
+        const int n = max(0, min(nums[b], S));
+        int tp = 0;
+        for (int s = lane; s < n; s += 64) {
+            const int a = stitches[((long)b * 2 + 0) * S + s], c = stitches[((long)b * 2 + 1) * S + s];
+            if (a >= 0 && a < E && c >= 0 && c < E) tp += (mask[((long)b * E + a) * W + (c >> 5)] >> (c & 31)) & 1u;
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) tp += __shfl_xor(tp, o);
+        if (lane == 0) {
+            const unsigned long long c0 = cnt[2 * (long)b], c1 = cnt[2 * (long)b + 1];
+            const int v[6] = {(int)(c0 & 0xffffffffull), (int)(c0 >> 32), (int)(c1 & 0x1fffff), (int)((c1 >> 21) & 0x1fffff),
+                              (int)(c1 >> 42), tp};
+            loss_sum[b] = sum;
+            for (int k = 0; k < 6; ++k) { counts[(long)b * 6 + k] = v[k]; tot[k] += v[k]; }
+            tot[6] += n;
+        }
+    }
+    if (lane == 0)
+        for (int k = 0; k < 7; ++k) s_tot[w][k] = tot[k];
+    __threadfence_block();
+    __syncthreads();
+    if (w == 0) {
+        // the first wave reads 64 garments at a time; every lane adds them in garment order (padding adds exact zeros)
+        double total = 0.0;
+        for (int b0 = 0; b0 < B; b0 += 64) {
+            const double v = b0 + lane < B ? loss_sum[b0 + lane] : 0.0;
+#pragma unroll 1
+            for (int q = 0; q < 64; ++q) total += __shfl(v, q);
+        }
+        if (lane == 0) {
+            long long t[7];
+            for (int k = 0; k < 7; ++k) {
+                t[k] = 0;
+                for (int i = 0; i < SP_FIN_TPB / 64; ++i) t[k] += s_tot[i][k];
+            }
+            metrics[0] = t[0] ? (float)(total / (double)t[0]) : 0.f;         // edge_pair_class_loss: the mean over the concatenated pairs
+            metrics[1] = sp_ratio(t[1], t[0]);                               // edge_pair_class_acc
+            metrics[2] = sp_ratio(t[2], t[3]);                               // stitch_precision
+            metrics[3] = sp_ratio(t[2], t[4]);                               // stitch_recall
+            metrics[4] = sp_ratio(t[5], t[6]);                               // selected_precision
+            metrics[5] = sp_ratio(t[5], t[4]);                               // selected_recall
+        }
+    }
+}
+
 // ---- C ABI -------------------------------------------------------------------------------------------------------------------------
 static inline bool sp_dims_ok(int B, int P, int L) { return B > 0 && B <= 65535 && P > 0 && P <= SP_MAXP && L > 0 && L <= SP_MAXL; }
 
@@ -495,43 +677,75 @@ extern "C" int gpe_stitch_pairs_planes(const float* wt, int K, int ldw, const ui
     return GPE_OK;
 }
 
-template <int NB>
-static int sp_launch_fwd(const SpFwdParams& p, bool h3, hipStream_t s)
+template <int NB, class PT>
+static int sp_launch_fwd(const PT& p, bool h3, hipStream_t s)
 {
     constexpr int LDW = SpLdw<NB>::v;
     if (h3) {
         const size_t lds = (size_t)(128 * (p.KP + 8) + SP_KS * LDW) * sizeof(float);
-        GPE_ENSURE_MAX_LDS_N(gpe_stitch_pairs_h3_kernel<NB>, 158 * 1024);
-        hipLaunchKernelGGL(gpe_stitch_pairs_h3_kernel<NB>, dim3(gpe_cdiv(p.P * p.L, SP3_TI) * p.nTj, p.B), dim3(SP_TPB), lds, s, p);
+        GPE_ENSURE_MAX_LDS_N((gpe_stitch_pairs_h3_kernel<NB, PT>), 158 * 1024);
+        hipLaunchKernelGGL((gpe_stitch_pairs_h3_kernel<NB, PT>), dim3(gpe_cdiv(p.P * p.L, SP3_TI) * p.nTj, p.B), dim3(SP_TPB), lds, s, p);
     } else {
         const size_t lds = (size_t)(64 * p.lda + SP_KS * LDW) * sizeof(float);
-        GPE_ENSURE_MAX_LDS_N(gpe_stitch_pairs_fwd_kernel<NB>, 150 * 1024);
-        hipLaunchKernelGGL(gpe_stitch_pairs_fwd_kernel<NB>, dim3(gpe_cdiv(p.P * p.L, SP_T) * p.nTj, p.B), dim3(SP_TPB), lds, s, p);
+        GPE_ENSURE_MAX_LDS_N((gpe_stitch_pairs_fwd_kernel<NB, PT>), 150 * 1024);
+        hipLaunchKernelGGL((gpe_stitch_pairs_fwd_kernel<NB, PT>), dim3(gpe_cdiv(p.P * p.L, SP_T) * p.nTj, p.B), dim3(SP_TPB), lds, s, p);
     }
     GPE_CHECK_LAUNCH();
     return GPE_OK;
 }
 
+template <class PT>
+static int sp_dispatch_fwd(const PT& p, bool h3, hipStream_t s)
+{
+    switch (sp_nb(p.H)) {
+    case 4: return sp_launch_fwd<4>(p, h3, s);
+    case 8: return sp_launch_fwd<8>(p, h3, s);
+    case 13: return sp_launch_fwd<13>(p, h3, s);
+    default: return sp_launch_fwd<16>(p, h3, s);
+    }
+}
+
 extern "C" int gpe_math_get(void);
+
+// checks and operands shared by the prediction and the evaluating entry point; false: bad arguments
+static bool sp_fwd_params(const float* ab, int ldab, int H, int n_layers, const float* wpk, const void* planes, const uint32_t* w_amax,
+                          const float* last_stats, const int32_t* num_edges, int B, int P, int L, uint64_t* table, float* logits,
+                          SpFwdParams& p, bool& h3)
+{
+    if (!ab || !wpk || !last_stats || !num_edges || !table || !sp_dims_ok(B, P, L)) return false;
+    if (H <= 0 || H > 256 || (H & 3) || n_layers < 1 || n_layers > 4 || ldab < 2 * H || (ldab & 3)) return false;
+    if ((((uintptr_t)ab) | ((uintptr_t)wpk) | ((uintptr_t)planes)) & 15) return false;
+    const int E = P * L;
+    // f16x3: planes given, the activation planes of 128 rows fit beside a slab (H <= 224), and the call is past the mode's size gate
+    h3 = planes && w_amax && gpe_math_get() == 4 && H <= 224 && (long)B * E * E / 2 >= gpe_h3_min_rows();
+    p = SpFwdParams{ab, ldab, H, n_layers, wpk, static_cast<const float*>(planes), w_amax, last_stats, num_edges, B, P, L,
+                    reinterpret_cast<unsigned long long*>(table), logits, sp_lda(H), gpe_cdiv(E, h3 ? SP3_TJ : SP_T), (H + 31) & ~31};
+    return true;
+}
 
 extern "C" int gpe_stitch_pairs_fwd(const float* ab, int ldab, int H, int n_layers, const float* wpk, const void* planes,
                                     const uint32_t* w_amax, const float* last_stats, const int32_t* num_edges, int B, int P, int L,
                                     uint64_t* table, float* logits, void* stream)
 {
-    if (!ab || !wpk || !last_stats || !num_edges || !table || !sp_dims_ok(B, P, L)) return GPE_EINVAL;
-    if (H <= 0 || H > 256 || (H & 3) || n_layers < 1 || n_layers > 4 || ldab < 2 * H || (ldab & 3)) return GPE_EINVAL;
-    if ((((uintptr_t)ab) | ((uintptr_t)wpk) | ((uintptr_t)planes)) & 15) return GPE_EINVAL;
-    const int E = P * L;
-    // f16x3: planes given, the activation planes of 128 rows fit beside a slab (H <= 224), and the call is past the mode's size gate
-    const bool h3 = planes && w_amax && gpe_math_get() == 4 && H <= 224 && (long)B * E * E / 2 >= gpe_h3_min_rows();
-    SpFwdParams p{ab, ldab, H, n_layers, wpk, static_cast<const float*>(planes), w_amax, last_stats, num_edges, B, P, L,
-                  reinterpret_cast<unsigned long long*>(table), logits, sp_lda(H), gpe_cdiv(E, h3 ? SP3_TJ : SP_T), (H + 31) & ~31};
-    switch (sp_nb(H)) {
-    case 4: return sp_launch_fwd<4>(p, h3, (hipStream_t)stream);
-    case 8: return sp_launch_fwd<8>(p, h3, (hipStream_t)stream);
-    case 13: return sp_launch_fwd<13>(p, h3, (hipStream_t)stream);
-    default: return sp_launch_fwd<16>(p, h3, (hipStream_t)stream);
-    }
+    SpFwdParams p;
+    bool h3;
+    if (!sp_fwd_params(ab, ldab, H, n_layers, wpk, planes, w_amax, last_stats, num_edges, B, P, L, table, logits, p, h3)) return GPE_EINVAL;
+    return sp_dispatch_fwd(p, h3, (hipStream_t)stream);
+}
+
+extern "C" int gpe_stitch_pairs_eval_fwd(const float* ab, int ldab, int H, int n_layers, const float* wpk, const void* planes,
+                                         const uint32_t* w_amax, const float* last_stats, const int32_t* num_edges, int B, int P, int L,
+                                         uint64_t* table, float* logits, const uint32_t* mask, double* loss_slab, uint64_t* counters,
+                                         void* stream)
+{
+    SpEvalParams p;
+    bool h3;
+    if (!mask || !loss_slab || !counters) return GPE_EINVAL;
+    if (!sp_fwd_params(ab, ldab, H, n_layers, wpk, planes, w_amax, last_stats, num_edges, B, P, L, table, logits, p, h3)) return GPE_EINVAL;
+    p.mask = mask;
+    p.slab = loss_slab;
+    p.cnt = reinterpret_cast<unsigned long long*>(counters);
+    return sp_dispatch_fwd(p, h3, (hipStream_t)stream);
 }
 
 static inline bool sp_chunk_ok(int P, int L, int c0, int c1) { return c0 >= 0 && c0 < c1 && c1 <= P * L; }
@@ -558,8 +772,46 @@ extern "C" int gpe_stitch_pairs_reduce(const float* y, long ldy, const int32_t* 
 {
     if (!y || ldy <= 0 || !num_edges || !table || !sp_dims_ok(B, P, L)) return GPE_EINVAL;
     if (!sp_chunk_ok(P, L, c0, c1) || (long)B * (c1 - c0) > 65535 || rows_chunk <= 0) return GPE_EINVAL;
-    hipLaunchKernelGGL(gpe_stitch_pairs_reduce_kernel, dim3(gpe_cdiv(P * L, 256), B * (c1 - c0)), dim3(256), 0, (hipStream_t)stream, y,
-                       ldy, num_edges, P, L, c0, c1, rows_chunk, reinterpret_cast<unsigned long long*>(table), logits);
+    hipLaunchKernelGGL(gpe_stitch_pairs_reduce_kernel<false>, dim3(gpe_cdiv(P * L, 256), B * (c1 - c0)), dim3(256), 0,
+                       (hipStream_t)stream, y, ldy, num_edges, P, L, c0, c1, rows_chunk, reinterpret_cast<unsigned long long*>(table),
+                       logits, nullptr, nullptr, nullptr);
+    GPE_CHECK_LAUNCH();
+    return GPE_OK;
+}
+
+extern "C" int gpe_stitch_pairs_eval_reduce(const float* y, long ldy, const int32_t* num_edges, int B, int P, int L, int c0, int c1,
+                                            long rows_chunk, uint64_t* table, float* logits, const uint32_t* mask, double* loss_slab,
+                                            uint64_t* counters, void* stream)
+{
+    if (!y || ldy <= 0 || !num_edges || !table || !mask || !loss_slab || !counters || !sp_dims_ok(B, P, L)) return GPE_EINVAL;
+    if (!sp_chunk_ok(P, L, c0, c1) || (long)B * (c1 - c0) > 65535 || rows_chunk <= 0) return GPE_EINVAL;
+    hipLaunchKernelGGL(gpe_stitch_pairs_reduce_kernel<true>, dim3(1, B * (c1 - c0)), dim3(SP_TPB), 0, (hipStream_t)stream, y, ldy,
+                       num_edges, P, L, c0, c1, rows_chunk, reinterpret_cast<unsigned long long*>(table), logits, mask, loss_slab,
+                       reinterpret_cast<unsigned long long*>(counters));
+    GPE_CHECK_LAUNCH();
+    return GPE_OK;
+}
+
+extern "C" int gpe_stitch_pairs_labels(const int32_t* gt_stitches, const int32_t* gt_num_stitches, int B, int P, int L, int S,
+                                       uint32_t* mask, void* stream)
+{
+    if (!gt_num_stitches || !mask || !sp_dims_ok(B, P, L) || S < 0 || (S > 0 && !gt_stitches)) return GPE_EINVAL;
+    if (S == 0) return GPE_OK;
+    hipLaunchKernelGGL(gpe_stitch_pairs_labels_kernel, dim3(gpe_cdiv(S, 256), B), dim3(256), 0, (hipStream_t)stream, gt_stitches,
+                       gt_num_stitches, S, P * L, mask);
+    GPE_CHECK_LAUNCH();
+    return GPE_OK;
+}
+
+extern "C" int gpe_stitch_eval_finalize(const double* loss_slab, long slots, int group, const uint64_t* counters, const uint32_t* mask,
+                                        const int32_t* stitches, const int32_t* num_stitches, int B, int P, int L, double* loss_sum,
+                                        int32_t* counts, float* metrics, void* stream)
+{
+    if (!loss_slab || !counters || !mask || !stitches || !num_stitches || !loss_sum || !counts || !metrics) return GPE_EINVAL;
+    if (!sp_dims_ok(B, P, L) || P * L < 2 || group <= 0 || slots <= 0 || slots % group || slots / group > 64) return GPE_EINVAL;
+    hipLaunchKernelGGL(gpe_stitch_eval_finalize_kernel, dim3(1), dim3(SP_FIN_TPB), 0, (hipStream_t)stream, loss_slab, slots, group,
+                       reinterpret_cast<const unsigned long long*>(counters), mask, stitches, num_stitches, B, P, L, loss_sum, counts,
+                       metrics);
     GPE_CHECK_LAUNCH();
     return GPE_OK;
 }

@@ -257,3 +257,27 @@ class StitchOnEdge3DPairs(BaseModule):
             raise RuntimeError('predict_stitches runs the eval-mode classifier: call .eval() first (the reference does, '
                                'pattern_converter.py:415)')
         return ops.stitch_pairs(edges3d, num_edges, self.mlp, data_stats['f_shift'], data_stats['f_scale'], **kw)
+
+    def evaluate_stitches(self, edges3d, num_edges, gt_stitches, gt_num_stitches, data_stats, **kw):
+        """predict_stitches scored against ground-truth stitches in the same pass: the reference's evaluation of this model over
+        every edge pair of the garments (GarmentStitchPairsDataset with random_pairs_mode False -> self.loss), without the pair rows.
+        gt_stitches integer [B, 2, S] edge ids panel * L + edge (either orientation), gt_num_stitches integer [B].
+        -> (out, loss_dict): out = ops.stitch_pairs_eval's dict (keywords route=, return_logits=); loss_dict has the keys self.loss
+        would produce for its configuration, pooled over the call, as fp32 device scalars (0 where a denominator is empty)."""
+        if self.pair_feature_len % 2:
+            raise ValueError('element_size must be even: a pair row is two edges (got %d)' % self.pair_feature_len)
+        if self.training:
+            raise RuntimeError('evaluate_stitches runs the eval-mode classifier: call .eval() first (the reference does, '
+                               'pattern_converter.py:415)')
+        out = ops.stitch_pairs_eval(edges3d, num_edges, self.mlp, data_stats['f_shift'], data_stats['f_scale'], gt_stitches,
+                                    gt_num_stitches, **kw)
+        m, loss_dict = out['metrics'], {}
+        if 'edge_pair_class' in self.loss.l_components:
+            loss_dict['edge_pair_class_loss'] = m['edge_pair_class_loss']
+        if self.loss.with_quality_eval:
+            if 'edge_pair_class' in self.loss.q_components:
+                loss_dict['edge_pair_class_acc'] = m['edge_pair_class_acc']
+            if 'edge_pair_stitch_recall' in self.loss.q_components:
+                loss_dict['stitch_precision'] = m['stitch_precision']
+                loss_dict['stitch_recall'] = m['stitch_recall']
+        return out, loss_dict

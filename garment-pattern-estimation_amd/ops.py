@@ -1579,9 +1579,9 @@ def _stitch_row_off(e, Lm, E):
     return Lm * q * E - Lm * Lm * (q * (q + 1) // 2) + r * (E - (q + 1) * Lm)
 
 
-def _stitch_fused(edges, ne, blocks, shift, scale, table, dense):
+def _stitch_fused(edges, ne, blocks, shift, scale, table, dense, ev=None):
     """the store-free route: per-edge projections [A | Bv] of the first Linear (standardisation folded in), then one launch that
-    classifies every pair from them"""
+    classifies every pair from them (ev: the workspaces of an evaluating pass, _stitch_eval_ws)"""
     B, P, Lm, Fe = edges.shape
     dev = edges.device
     n = len(blocks) - 1
@@ -1617,10 +1617,17 @@ def _stitch_fused(edges, ne, blocks, shift, scale, table, dense):
                 L.call('gpe_stitch_pairs_pack', W, W.stride(0), 1, H, st[2], wpk[o:], 1)
                 L.call('gpe_fold_bias', W, W.stride(0), 1, H, b, st[3], wpk[o + H:])
         st = bn_from_running(bn.running_mean, bn.running_var, bn.weight, bn.bias, bn.eps)
-    L.call('gpe_stitch_pairs_fwd', ab, 2 * H, H, n, wpk, planes, words, st, ne, B, P, Lm, table, dense)
+    args = (ab, 2 * H, H, n, wpk, planes, words, st, ne, B, P, Lm, table, dense)
+    if ev is None:
+        L.call('gpe_stitch_pairs_fwd', *args)
+    else:
+        n8 = (P * Lm + 7) // 8                  # a slot per 8 x 8 tile position (include/gpe_hip.h)
+        ev['slots'], ev['group'] = n8 * n8, n8
+        ev['slab'] = torch.zeros(B, n8 * n8, device=dev, dtype=torch.float64)
+        L.call('gpe_stitch_pairs_eval_fwd', *args, ev['mask'], ev['slab'], ev['counters'])
 
 
-def _stitch_rows(edges, ne, mlp, shift, scale, table, dense):
+def _stitch_rows(edges, ne, mlp, shift, scale, table, dense, ev=None):
     """the generic route: materialised pair rows of a chunk of i-edges -> the dense-MLP kernels (eval) -> the same epilogue"""
     import ctypes
     B, P, Lm, Fe = edges.shape
@@ -1628,6 +1635,9 @@ def _stitch_rows(edges, ne, mlp, shift, scale, table, dense):
     sh = (ctypes.c_float * (2 * Fe))(*[float(v) for v in shift])
     sc = (ctypes.c_float * (2 * Fe))(*[float(v) for v in scale])
     last = (P - 1) * Lm                         # the edges of the last panel slot have no later partner
+    if ev is not None:
+        ev['slots'], ev['group'] = E, Lm        # a slot per i-edge, shared by the chunks
+        ev['slab'] = torch.zeros(B, E, device=edges.device, dtype=torch.float64)
     c0 = 0
     while c0 < last:
         c1 = c0 + 1
@@ -1638,20 +1648,16 @@ def _stitch_rows(edges, ne, mlp, shift, scale, table, dense):
         rows = torch.empty(B * nrows, 2 * Fe, device=edges.device, dtype=F32)
         L.call('gpe_stitch_pairs_rows', edges, ne, B, P, Lm, Fe, sh, sc, c0, c1, nrows, rows)
         y = dense_mlp(rows, mlp, False)
-        L.call('gpe_stitch_pairs_reduce', y, y.stride(0), ne, B, P, Lm, c0, c1, nrows, table, dense)
+        if ev is None:
+            L.call('gpe_stitch_pairs_reduce', y, y.stride(0), ne, B, P, Lm, c0, c1, nrows, table, dense)
+        else:
+            L.call('gpe_stitch_pairs_eval_reduce', y, y.stride(0), ne, B, P, Lm, c0, c1, nrows, table, dense, ev['mask'], ev['slab'],
+                   ev['counters'])
         c0 = c1
 
 
-def stitch_pairs(edges3d, num_edges, mlp, f_shift, f_scale, route='auto', return_logits=False):
-    """Stitches of B garments from the edge-pair classifier `mlp` (net_blocks.MLP([2 Fe, H x n, 1]), eval mode): what the
-    reference does at prediction time with NNSewingPattern.all_edge_pairs + stitches_from_pair_classifier
-    (nn/data/pattern_converter.py:411-499) with the intended indexing of line 432 (INTEGRATION.md).
-
-    edges3d [B, P, L, Fe] fp32: un-standardised 3D edges per panel slot; num_edges [B, P] int (0 = panel absent); f_shift / f_scale:
-    2 Fe numbers.  -> stitches int32 [B, 2, S] (edge ids panel * L + edge, side 0 = lower panel, ascending (i, j, r, c), zero-padded;
-    S = P * L // 2), num_stitches int32 [B], scores fp32 [B, S] (logits) and, with return_logits, the dense logits [B, P*L, P*L]
-    (NaN where there is no pair).  No host synchronisation.  route: 'fused' (csrc/gpe_stitch_pairs.hip's store-free kernel; ValueError
-    off its menu), 'rows' (materialised rows through the dense-MLP kernels), 'auto' (fused on the menu, rows otherwise)."""
+def _stitch_check(edges3d, num_edges, mlp, f_shift, f_scale, route, gt=None):
+    """the argument checks of stitch_pairs / stitch_pairs_eval, all before any device check -> (blocks, fused)"""
     if route not in STITCH_PAIRS_ROUTES:
         raise ValueError('unknown route %r (choose from %s)' % (route, STITCH_PAIRS_ROUTES))
     if edges3d.dim() != 4:
@@ -1668,11 +1674,44 @@ def stitch_pairs(edges3d, num_edges, mlp, f_shift, f_scale, route='auto', return
         raise RuntimeError('stitch_pairs is a prediction path: call .eval() on the model first (BatchNorm running statistics)')
     if tuple(num_edges.shape) != (B, P) or num_edges.is_floating_point() or num_edges.device != edges3d.device:
         raise ValueError('num_edges must be an integer [B, P] tensor on the device of edges3d')
+    if gt is not None:
+        st, nums = gt
+        if (not torch.is_tensor(st) or st.dim() != 3 or tuple(st.shape[:2]) != (B, 2) or st.is_floating_point() or st.is_complex()
+                or st.dtype == torch.bool or st.device != edges3d.device):
+            raise ValueError('gt_stitches must be an integer [B, 2, S] tensor of edge ids panel * L + edge on the device of edges3d')
+        if (not torch.is_tensor(nums) or tuple(nums.shape) != (B,) or nums.is_floating_point() or nums.is_complex()
+                or nums.dtype == torch.bool or nums.device != edges3d.device):
+            raise ValueError('gt_num_stitches must be an integer [B] tensor on the device of edges3d')
     on_menu = stitch_pairs_on_menu(mlp)
     if route == 'fused' and not on_menu:
         raise ValueError("route='fused' needs 1 - 4 hidden layers of one width <= 256 that is a multiple of 4; use 'auto' or 'rows'")
-    _dev_check(edges3d)
-    fused = on_menu and route != 'rows'
+    return blocks, on_menu and route != 'rows'
+
+
+STITCH_EVAL_METRICS = ('edge_pair_class_loss', 'edge_pair_class_acc', 'stitch_precision', 'stitch_recall', 'selected_precision',
+                       'selected_recall')
+STITCH_EVAL_COUNTS = ('pairs', 'correct', 'true_positives', 'predicted_positives', 'gt_positives', 'selected_tp')
+
+
+def _stitch_eval_ws(gt_stitches, gt_num_stitches, B, P, Lm, dev):
+    """the caller-owned, zeroed workspaces of an evaluating pass (sizes: include/gpe_hip.h) with the label mask filled in"""
+    E, S = P * Lm, gt_stitches.shape[2]
+    ev = {'mask': torch.zeros(B, E, (E + 31) // 32, device=dev, dtype=torch.int32),
+          'counters': torch.zeros(B, 2, device=dev, dtype=torch.int64)}
+    # the kernel ignores ids outside 0 .. E - 1 and clamps the counts itself; wider integers are brought into int32's range first
+    st, nums = gt_stitches.detach(), gt_num_stitches.detach()
+    if st.dtype != torch.int32:
+        st = st.to(torch.int64).clamp(-1, E).to(torch.int32)
+    if nums.dtype != torch.int32:
+        nums = nums.to(torch.int64).clamp(0, S).to(torch.int32)
+    st, nums = st.contiguous(), nums.contiguous()
+    L.call('gpe_stitch_pairs_labels', st if S else None, nums, B, P, Lm, S, ev['mask'])
+    return ev
+
+
+def _stitch_run(edges3d, num_edges, mlp, blocks, fused, f_shift, f_scale, return_logits, gt=None):
+    """classify every pair, select; with gt = (gt_stitches, gt_num_stitches) through the evaluating entry points, then finalise"""
+    B, P, Lm, Fe = edges3d.shape
     dev = edges3d.device
     E, S = P * Lm, P * Lm // 2
     shift, scale = [float(v) for v in f_shift], [float(v) for v in f_scale]
@@ -1681,18 +1720,57 @@ def stitch_pairs(edges3d, num_edges, mlp, f_shift, f_scale, route='auto', return
         ne = num_edges.to(torch.int32).contiguous()
         table = torch.zeros(B, E, device=dev, dtype=torch.int64)
         dense = torch.full((B, E, E), float('nan'), device=dev, dtype=F32) if return_logits else None
+        ev = _stitch_eval_ws(gt[0], gt[1], B, P, Lm, dev) if gt is not None else None
         if fused:
-            _stitch_fused(edges, ne, blocks, shift, scale, table, dense)
+            _stitch_fused(edges, ne, blocks, shift, scale, table, dense, ev)
         else:
-            _stitch_rows(edges, ne, mlp, shift, scale, table, dense)
+            _stitch_rows(edges, ne, mlp, shift, scale, table, dense, ev)
         stitches = torch.empty(B, 2, S, device=dev, dtype=torch.int32)
         nums = torch.empty(B, device=dev, dtype=torch.int32)
         scores = torch.empty(B, S, device=dev, dtype=F32)
         L.call('gpe_stitch_select', table, B, P, Lm, stitches, nums, scores)
-    out = {'stitches': stitches, 'num_stitches': nums, 'scores': scores}
-    if return_logits:
-        out['logits'] = dense
+        out = {'stitches': stitches, 'num_stitches': nums, 'scores': scores}
+        if return_logits:
+            out['logits'] = dense
+        if ev is not None:
+            loss_sum = torch.empty(B, device=dev, dtype=torch.float64)
+            counts = torch.empty(B, 6, device=dev, dtype=torch.int32)
+            metrics = torch.empty(6, device=dev, dtype=F32)
+            L.call('gpe_stitch_eval_finalize', ev['slab'], ev['slots'], ev['group'], ev['counters'], ev['mask'], stitches, nums, B, P,
+                   Lm, loss_sum, counts, metrics)
+            out.update(metrics={k: metrics[i] for i, k in enumerate(STITCH_EVAL_METRICS)}, counts=counts, loss_sum=loss_sum)
     return out
+
+
+def stitch_pairs(edges3d, num_edges, mlp, f_shift, f_scale, route='auto', return_logits=False):
+    """Stitches of B garments from the edge-pair classifier `mlp` (net_blocks.MLP([2 Fe, H x n, 1]), eval mode): what the
+    reference does at prediction time with NNSewingPattern.all_edge_pairs + stitches_from_pair_classifier
+    (nn/data/pattern_converter.py:411-499) with the intended indexing of line 432 (INTEGRATION.md).
+
+    edges3d [B, P, L, Fe] fp32: un-standardised 3D edges per panel slot; num_edges [B, P] int (0 = panel absent); f_shift / f_scale:
+    2 Fe numbers.  -> stitches int32 [B, 2, S] (edge ids panel * L + edge, side 0 = lower panel, ascending (i, j, r, c), zero-padded;
+    S = P * L // 2), num_stitches int32 [B], scores fp32 [B, S] (logits) and, with return_logits, the dense logits [B, P*L, P*L]
+    (NaN where there is no pair).  No host synchronisation.  route: 'fused' (csrc/gpe_stitch_pairs.hip's store-free kernel; ValueError
+    off its menu), 'rows' (materialised rows through the dense-MLP kernels), 'auto' (fused on the menu, rows otherwise)."""
+    blocks, fused = _stitch_check(edges3d, num_edges, mlp, f_shift, f_scale, route)
+    _dev_check(edges3d)
+    return _stitch_run(edges3d, num_edges, mlp, blocks, fused, f_shift, f_scale, return_logits)
+
+
+def stitch_pairs_eval(edges3d, num_edges, mlp, f_shift, f_scale, gt_stitches, gt_num_stitches, route='auto', return_logits=False):
+    """stitch_pairs scored against ground-truth stitches in the same classification pass: the reference's evaluation of this model
+    (GarmentStitchPairsDataset with random_pairs_mode False: the labels of all_edge_pairs, nn/data/pattern_converter.py:458-499, into
+    ComposedLoss, nn/metrics/composed_loss.py:83-126) without a pair row, a logit or a label stored, and without a host read.
+
+    gt_stitches integer [B, 2, S] (S may be 0): edge ids panel * L + edge of both sides, either orientation, the layout of the stitch
+    losses; gt_num_stitches integer [B], clamped to 0 .. S.  Entries with an id outside 0 .. P L - 1 are ignored, duplicates are
+    harmless, and an entry that no enumerated pair matches (same panel, absent edge) counts nowhere.
+    -> the dict of stitch_pairs plus 'metrics' {name: fp32 device scalar} pooled over the call (STITCH_EVAL_METRICS: the loss is the
+    mean over the concatenated pairs; selected_* score the selected stitches; a ratio with denominator 0 is 0), 'counts' int32 [B, 6]
+    (STITCH_EVAL_COUNTS) and 'loss_sum' fp64 [B] (the sum of the BCE-with-logits terms per garment).  Bit-reproducible."""
+    blocks, fused = _stitch_check(edges3d, num_edges, mlp, f_shift, f_scale, route, (gt_stitches, gt_num_stitches))
+    _dev_check(edges3d)
+    return _stitch_run(edges3d, num_edges, mlp, blocks, fused, f_shift, f_scale, return_logits, (gt_stitches, gt_num_stitches))
 
 
 class SparsemaxLossFn(torch.autograd.Function):

@@ -633,6 +633,46 @@ int gpe_stitch_pairs_reduce(const float* y, long ldy, const int32_t* num_edges, 
 int gpe_stitch_select(const uint64_t* table, int B, int P, int L, int32_t* stitches, int32_t* num_stitches, float* scores,
                       void* stream);
 
+/* ---- the same pass scored against ground-truth stitches (nn/metrics/composed_loss.py:83-126 ComposedLoss over the pairs and
+ * labels of all_edge_pairs, nn/data/pattern_converter.py:458-499) ----------------------------------------------------------------
+ * Added without a version bump (gpe_abi_version() stays 7): four compute entry points, nothing else changes.  Every workspace is
+ * the caller's and ZEROED by the caller; sizes are the formulas below (no size query).  With W = ceil(E / 32), N8 = ceil(E / 8):
+ *   mask      uint32 [B][E][W]: bit (e_j % 32) of word [e_i][e_j / 32] = pair (e_i, e_j) is a ground-truth stitch; symmetric.
+ *   loss_slab fp64 [B][slots]: one slot per workgroup of the classifying launch, written (not added to) by its owner.
+ *             gpe_stitch_pairs_eval_fwd: slots = N8 * N8, tile (ti, tj) of either fused kernel owns slot ti * N8 + tj;
+ *             gpe_stitch_pairs_eval_reduce: slots = E, the workgroup of i-edge e owns slot e (all chunks share one slab).
+ *   counters  uint64 [B][2]: word 0 = pairs | correct << 32, word 1 = true positives | predicted positives << 21 |
+ *             ground-truth positives << 42 (a garment has fewer than 2^17 pairs), added by 64-bit integer atomics.
+ * gpe_stitch_pairs_labels: gt_stitches int32 [B][2][S] of edge ids panel * L + edge (the layout of the stitch losses), gt_num_stitches
+ *   int32 [B] clamped to 0 .. S.  Sets bits (a, b) and (b, a) of every stitch; an entry with an id outside 0 .. E - 1 is ignored,
+ *   duplicates are harmless, S = 0 launches nothing.  Bits of same-panel pairs or absent edges are never read: only enumerated
+ *   pairs consult the mask, as `pair_id in stitch_set or reversed in stitch_set` does over the reference's enumeration.
+ * gpe_stitch_pairs_eval_fwd / gpe_stitch_pairs_eval_reduce: the operands and results of gpe_stitch_pairs_fwd / _reduce (table and
+ *   logits are filled bit-identically) plus, for every pair with logit x and label y, the term relu(-x if y else x) +
+ *   log1p(exp(-|x|)) (BCE with logits, both summands non-negative, fp32) accumulated in fp64, and the counters with the class
+ *   sigmoid(x) > 0.5 of the selection.  Inside a workgroup the sums run in a fixed order (xor butterfly in a wave, then the waves
+ *   in order through LDS); no float atomics, no workgroup waits on another: bit-reproducible, and independent of unused panel or
+ *   edge slots (the rows route walks the present edges in position order, one workgroup per i-edge).
+ * gpe_stitch_eval_finalize: one launch of one workgroup after gpe_stitch_select.  `group` consecutive slots form a group
+ *   (slots % group == 0, at most 64 groups: group = N8 after _eval_fwd, group = L after _eval_reduce); a group is added in slot
+ *   order, then the groups in order.  loss_sum fp64 [B]; counts int32 [B][6] = pairs, correct, true positives, predicted positives,
+ *   ground-truth positives, selected_tp (stitches written by gpe_stitch_select whose pair is in the mask); metrics fp32 [6] pooled
+ *   over the call = edge_pair_class_loss (sum of loss_sum in garment order / sum of pairs), edge_pair_class_acc, stitch_precision,
+ *   stitch_recall, selected_precision (selected_tp / stitches selected), selected_recall (selected_tp / ground-truth positives).
+ *   A ratio whose denominator is 0 is 0 (composed_loss.py:123-124). */
+int gpe_stitch_pairs_labels(const int32_t* gt_stitches, const int32_t* gt_num_stitches, int B, int P, int L, int S, uint32_t* mask,
+                            void* stream);
+int gpe_stitch_pairs_eval_fwd(const float* ab, int ldab, int H, int n_layers, const float* wpk, const void* planes,
+                              const uint32_t* w_amax, const float* last_stats, const int32_t* num_edges, int B, int P, int L,
+                              uint64_t* table, float* logits, const uint32_t* mask, double* loss_slab, uint64_t* counters,
+                              void* stream);
+int gpe_stitch_pairs_eval_reduce(const float* y, long ldy, const int32_t* num_edges, int B, int P, int L, int c0, int c1,
+                                 long rows_chunk, uint64_t* table, float* logits, const uint32_t* mask, double* loss_slab,
+                                 uint64_t* counters, void* stream);
+int gpe_stitch_eval_finalize(const double* loss_slab, long slots, int group, const uint64_t* counters, const uint32_t* mask,
+                             const int32_t* stitches, const int32_t* num_stitches, int B, int P, int L, double* loss_sum,
+                             int32_t* counts, float* metrics, void* stream);
+
 
 /* ---- optimizer / input side (nn/trainer.py:162-185; nn/data/transforms.py:35-50) ----------------------------------- */
 /* one torch.optim.Adam step (amsgrad off) over a flat arena of n floats (16-B aligned p, g, m, v); `step` counts from 1;
