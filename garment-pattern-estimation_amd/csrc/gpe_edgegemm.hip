@@ -18,7 +18,7 @@
 // LDS: A[2] + C (3 x 64 x 212 floats = 159 KB of the CU's 160 KB at the shipped sizes).  Two barriers per tile.  The
 // kernel's VGPR allocation is the max of both roles and must stay <= 256 (2 waves/SIMD): consumers 156 (weights) + 48
 // (accumulators) + fragments.
-#include "gpe_rowgemm.h"
+#include "gpe_edge_dispatch.h"
 #include <math.h>
 
 // ---- split-bf16 ("bf16x3") arithmetic ------------------------------------------------------------------------------
@@ -516,84 +516,17 @@ __global__ __launch_bounds__(512, 2) void gpe_edgegemm_kernel(RgParams p, int st
 }
 
 // ---------------------------------------------------------------------------------------------------------
-static int eg_num_cus() { return gpe_num_cus(); }
+struct EgMenu { static constexpr bool has(int, int, int, int) { return true; } };
 
-template <int AQ, int BQ, int KCH, int AMODE, int EMODE, int MATH>
-static int eg_launch(const RgParams& p, int stats_nblk, hipStream_t s)
+// The producer/consumer family: every (amode, emode) pair and tile shape of the menu, exact fp32 or (bf16x3) two-term split-bf16.
+// `p` keeps the generic tiling (R = (64/k)*k <= 64 rows of whole points).
+int gpe_edge_pc(const RgParams& p, int amode, int emode, int NT, int KCH, int bf16x3, int stats_nblk, hipStream_t s)
 {
-    constexpr int NT = 4 * AQ + BQ;
-    constexpr int LDA = 16 * KCH + 4, LDC = 16 * NT + 4;
-    const size_t lds = (size_t)RG_BM * (2 * LDA + LDC) * sizeof(float);
-    GPE_ENSURE_MAX_LDS((gpe_edgegemm_kernel<AQ, BQ, KCH, AMODE, EMODE, MATH>));
-    int gx = eg_num_cus();
-    if (gx > p.num_tiles) gx = p.num_tiles;
-    if (stats_nblk > 0 && gx > stats_nblk) gx = stats_nblk;
-    hipLaunchKernelGGL((gpe_edgegemm_kernel<AQ, BQ, KCH, AMODE, EMODE, MATH>), dim3(gx), dim3(512), lds, s, p, stats_nblk);
-    GPE_CHECK_LAUNCH();
-    return GPE_OK;
-}
-
-template <int AMODE, int EMODE, int MATH>
-static int eg_dispatch_m(int NT, int KCH, const RgParams& p, int stats_nblk, hipStream_t s)
-{
-    if (NT == 13 && KCH == 13) return eg_launch<3, 1, 13, AMODE, EMODE, MATH>(p, stats_nblk, s);
-    if (NT == 13 && KCH == 10) return eg_launch<3, 1, 10, AMODE, EMODE, MATH>(p, stats_nblk, s);
-    if (NT == 10 && KCH == 13) return eg_launch<2, 2, 13, AMODE, EMODE, MATH>(p, stats_nblk, s);
-    if (NT == 10 && KCH == 10) return eg_launch<2, 2, 10, AMODE, EMODE, MATH>(p, stats_nblk, s);
-    return GPE_EINVAL;
-}
-
-static int g_eg_math = 0;            // 0: exact fp32 MFMA, 1: bf16x3, 2: bf16x6 where it fits, 3: f16x3 (gpe_math_set)
-void gpe_edgegemm_set_math(int m) { g_eg_math = m; }
-
-template <int AMODE, int EMODE>
-static int eg_dispatch(int NT, int KCH, const RgParams& p, int stats_nblk, hipStream_t s, int math)
-{
-    return math == 1 ? eg_dispatch_m<AMODE, EMODE, 1>(NT, KCH, p, stats_nblk, s)
-                     : eg_dispatch_m<AMODE, EMODE, 0>(NT, KCH, p, stats_nblk, s);
-}
-
-// Returns 1 and launches when the shape is on the register-stationary menu, 0 when the caller should use the generic
-// LDS-streamed kernel, < 0 on a launch error.
-int gpe_edgegemm_sr_try(const RgParams& p, int amode, int emode, int stats_nblk, hipStream_t s);   // gpe_edgegemm_sr.hip
-int gpe_edgegemm_x6_try(const RgParams& p, int amode, int emode, int stats_nblk, hipStream_t s);   // gpe_edgegemm_x6.hip
-int gpe_edgegemm_h3_try(const RgParams& p, int amode, int emode, int stats_nblk, hipStream_t s);   // gpe_edgegemm_h3.hip
-
-int gpe_edgegemm_try(const RgParams& p, int amode, int emode, int stats_nblk, hipStream_t s)
-{
-    // (r02: a "forward-only bf16x3" mode was measured and dropped — 1785 garments/s, but first-layer weight gradients are
-    // residuals of cancelling sums that amplify ANY 1e-5 perturbation of the stored activations ~1e3 times (1.5e-2 of
-    // max|grad|): nothing short of ~24-bit operands is parity-grade, forward or backward.)
-    const int math = g_eg_math;
-    if (g_eg_math == 2) {                                // bf16x6: three-term split-bf16 single-role kernel where it fits
-        const int r = gpe_edgegemm_x6_try(p, amode, emode, stats_nblk, s);
-        if (r != 0) return r;
-    }
-    if (g_eg_math == 3) {                                // f16x3: two-term split-fp16 single-role kernel, every shipped shape
-        const int r = gpe_edgegemm_h3_try(p, amode, emode, stats_nblk, s);
-        if (r != 0) return r;
-    }
-    // fp16 activation rows / a lazily formed dz3 exist only in the f16x3 single-role kernels: nothing below may touch such buffers
-    if (p.out_half || p.lz_g) return GPE_EINVAL;
-    if ((math == 0 || g_eg_math >= 2) && !(p.dbg & 64)) {   // exact fp32: the single-role software-pipelined kernel
-        const int r = gpe_edgegemm_sr_try(p, amode, emode, stats_nblk, s);
-        if (r != 0) return r;
-    }
-    if (p.N <= 96 || p.N > 208 || p.K <= 96 || p.K > 208) return 0;
-    if (emode != E_EDGE_FWD && (p.N & 3)) return 0;      // the backward epilogues use aligned 16-B coefficient loads
-    if (amode == A_GATHER && (p.K & 3)) return 0;
-    if (amode == A_DENSE && (p.a.inner > 0 || (p.a.stride_outer & 3) || p.a.stride_outer < ((p.K + 3) & ~3) ||
-                             (((uintptr_t)p.a.base) & 15)))
-        return 0;                                        // dense rows must be aligned + padded for plain 16-B loads
-    if (p.R > 64 || p.k > 64) return 0;
-    const int NT = (p.N <= 160) ? 10 : 13;
-    const int KCH = (p.K <= 160) ? 10 : 13;
-    int rc = GPE_EINVAL;
-    if (amode == A_GATHER && emode == E_EDGE_FWD) rc = eg_dispatch<A_GATHER, E_EDGE_FWD>(NT, KCH, p, stats_nblk, s, math);
-    else if (amode == A_DENSE && emode == E_EDGE_FWD) rc = eg_dispatch<A_DENSE, E_EDGE_FWD>(NT, KCH, p, stats_nblk, s, math);
-    else if (amode == A_DENSE && emode == E_BWD_INPLACE)
-        rc = eg_dispatch<A_DENSE, E_BWD_INPLACE>(NT, KCH, p, stats_nblk, s, math);
-    else if (amode == A_DENSE && emode == E_BWD_GATHER)
-        rc = eg_dispatch<A_DENSE, E_BWD_GATHER>(NT, KCH, p, stats_nblk, s, math);
-    return rc == GPE_OK ? 1 : rc;
+    return gpe_edge_select<EgMenu>(amode, emode, NT, KCH, [&](auto m, auto t) {
+        using M = decltype(m);
+        using T = decltype(t);
+        const size_t lds = (size_t)RG_BM * (2 * (16 * T::KCH + 4) + 16 * T::NT + 4) * sizeof(float);   // A[2] + C
+        return bf16x3 ? gpe_edge_launch<gpe_edgegemm_kernel<T::AQ, T::BQ, T::KCH, M::amode, M::emode, 1>, 512, GPE_EDGE_LDS_CAP>(p, stats_nblk, lds, s)
+                      : gpe_edge_launch<gpe_edgegemm_kernel<T::AQ, T::BQ, T::KCH, M::amode, M::emode, 0>, 512, GPE_EDGE_LDS_CAP>(p, stats_nblk, lds, s);
+    });
 }

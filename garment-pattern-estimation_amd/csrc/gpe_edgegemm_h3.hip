@@ -136,48 +136,30 @@ int gpe_h3_pq_passes(unsigned* out, float* part, const float* pq, long rows, int
     GPE_CHECK_LAUNCH();
     return GPE_OK;
 }
-int gpe_h3_absmax(unsigned* out, const float* x, long rows, int cols, long ld, hipStream_t s)
+// one streaming |x| max over rows x cols4 column quads into out[0] (atomicMax: the word must have been cleared on the stream)
+static int h3_absmax_pass(unsigned* out, const float* x, long rows, int cols4, long ld, hipStream_t s)
 {
-    if (!out || !x) return GPE_EINVAL;
-    if (hipMemsetAsync(out, 0, sizeof(unsigned), s) != hipSuccess) return GPE_ELAUNCH;
-    const int cols4 = (cols + 3) >> 2;
-    const long total = rows * cols4;
-    if (total <= 0) return GPE_OK;
-    int gx = (int)((total + 255) / 256);
+    int gx = (int)((rows * cols4 + 255) / 256);
     const int cap = gpe_num_cus() * 8;
     if (gx > cap) gx = cap;
     hipLaunchKernelGGL(gpe_h3_absmax_kernel, dim3(gx), dim3(256), 0, s, x, rows, cols4, ld, out);
     GPE_CHECK_LAUNCH();
     return GPE_OK;
 }
-
-int gpe_edgegemm_w8_dispatch(int amode, int emode, int NT, int KCH, const RgParams& p, int stats_nblk, hipStream_t s);   // gpe_edgegemm_w8.hip
-
-template <int AMODE, int EMODE>
-static int h3_dispatch(int NT, int KCH, const RgParams& p, int stats_nblk, hipStream_t s)
+int gpe_h3_absmax(unsigned* out, const float* x, long rows, int cols, long ld, hipStream_t s)
 {
-    if (NT == 13 && KCH == 13) return x6_launch<SplitF16x2, 3, 1, 13, AMODE, EMODE>(p, stats_nblk, s);
-    if (NT == 13 && KCH == 10) return x6_launch<SplitF16x2, 3, 1, 10, AMODE, EMODE>(p, stats_nblk, s);
-    if (NT == 10 && KCH == 13) return x6_launch<SplitF16x2, 2, 2, 13, AMODE, EMODE>(p, stats_nblk, s);
-    if (NT == 10 && KCH == 10) return x6_launch<SplitF16x2, 2, 2, 10, AMODE, EMODE>(p, stats_nblk, s);
-    return GPE_ENOTSUP_SHAPE;
+    if (!out || !x) return GPE_EINVAL;
+    if (hipMemsetAsync(out, 0, sizeof(unsigned), s) != hipSuccess) return GPE_ELAUNCH;
+    const int cols4 = (cols + 3) >> 2;
+    if (rows * cols4 <= 0) return GPE_OK;
+    return h3_absmax_pass(out, x, rows, cols4, ld, s);
 }
 
-// Returns 1 and launches when the shape is on this kernel's menu, 0 when the caller should try the next kernel,
-// < 0 on a launch error.  Needs the f16x3 words of the caller's workspace; without them (or below gpe_h3_min_rows() rows, where the
-// scale passes cost more than the kernel saves) the exact kernels run.
-int gpe_edgegemm_h3_try(const RgParams& p_in, int amode, int emode, int stats_nblk, hipStream_t s)
+// The operand scales of an f16x3 launch (both f16x3 families), measured on the stream into the workspace words p.ws.h3 where the
+// caller gave none.  `p` is the re-tiled copy, npts the rows of the per-point table (p.k may count pseudo-point rows).
+int gpe_edge_f16x3_scales(RgParams& p, long npts, int amode, int emode, int KCH, hipStream_t s)
 {
-    unsigned* slots = p_in.ws.h3;
-    if (!slots || p_in.M < gpe_h3_min_rows()) return 0;
-    RgParams p;
-    GpeFold fold;
-    if (!x6_prepare(p_in, amode, emode, stats_nblk, p, fold)) return 0;
-    const long npts = p_in.k > 0 ? p_in.M / p_in.k : 0;   // rows of the per-point table (p.k may now count pseudo-point rows)
-    const int NT = (p.N <= 160) ? 10 : 13;
-    const int KCH = (p.K <= 160) ? 10 : 13;
-    if (amode == A_GATHER && !p.user_amax_a && (p.H & 3)) return 0;
-
+    unsigned* slots = p.ws.h3;
     // the largest magnitude this launch writes to `out` (forward activations, in-place dz: tensors the next edge GEMM reads as
     // its A operand) goes to the caller's word; the gathered backward writes dz of block 0, which no GEMM of this library reads
     const bool tracks = emode == E_EDGE_FWD || emode == E_BWD_INPLACE;
@@ -185,43 +167,28 @@ int gpe_edgegemm_h3_try(const RgParams& p_in, int amode, int emode, int stats_nb
     const long wn = (long)16 * KCH * p.Npad;              // the packed weight: 4 KCH k-quads x Npad columns x 4 (gpe_packed_size)
     // (w_ready: the caller's gpe_pack_fold launch left the weight's amax in slots[1], cleared slots[0] and the output word; only
     // honoured when no pass of this call accumulates into slots[0] afterwards — i.e. the A operand's word is the caller's)
-    const bool w_ready = p_in.w_ready && p.user_amax_a;
+    const bool w_ready = p.w_ready && p.user_amax_a;
     if (!reuse && !w_ready) {
         hipLaunchKernelGGL(gpe_h3_wmax_kernel, dim3(1), dim3(1024), 0, s, p.wp, wn, slots, tracks ? p.user_amax_out : nullptr);
         GPE_CHECK_LAUNCH();
     }
-    if (reuse) {
-        p.h3_amax_a = slots;
-    } else if (p.user_amax_a) {
-        p.h3_amax_a = p.user_amax_a;
-    } else if (amode == A_DENSE) {
-        const int cols4 = (p.K + 3) >> 2;
-        const long total = p.M * cols4;
-        int gx = (int)((total + 255) / 256);
-        const int cap = gpe_num_cus() * 8;
-        if (gx > cap) gx = cap;
-        hipLaunchKernelGGL(gpe_h3_absmax_kernel, dim3(gx), dim3(256), 0, s, p.a.base, p.M, cols4, (long)p.a.stride_outer, slots);
-        GPE_CHECK_LAUNCH();
-        p.h3_amax_a = slots;
-    } else {
-        // the per-point table behind the gathered operand
-        const int rc_pq = gpe_h3_pq_passes(slots, reinterpret_cast<float*>(slots + 2), p.pq, npts, p.H, (long)p.ldpq, s);
-        if (rc_pq != GPE_OK) return rc_pq;
-        p.h3_amax_a = slots;
+    p.h3_amax_a = (p.user_amax_a && !reuse) ? p.user_amax_a : slots;
+    if (!p.user_amax_a && !reuse) {
+        // dense rows: gpe_h3_wmax_kernel has just cleared slots[0]; gathered: the per-point table behind the operand
+        const int rc = amode == A_DENSE ? h3_absmax_pass(slots, p.a.base, p.M, (p.K + 3) >> 2, (long)p.a.stride_outer, s)
+                                        : gpe_h3_pq_passes(slots, reinterpret_cast<float*>(slots + 2), p.pq, npts, p.H, (long)p.ldpq, s);
+        if (rc != GPE_OK) return rc;
     }
     p.h3_amax_w = slots + 1;
     p.amax_out = tracks ? p.user_amax_out : nullptr;
+    return GPE_OK;
+}
 
-    // k = 16 at the shipped widths: two waves per SIMD (gpe_edgegemm_w8.hip); everything else the single-role kernel
-    int rc = gpe_edgegemm_w8_dispatch(amode, emode, NT, KCH, p, stats_nblk, s);
-    if (rc != GPE_ENOTSUP_SHAPE) { /* launched (or refused with an error) */ }
-    else if (amode == A_GATHER && emode == E_EDGE_FWD) rc = h3_dispatch<A_GATHER, E_EDGE_FWD>(NT, KCH, p, stats_nblk, s);
-    else if (amode == A_DENSE && emode == E_EDGE_FWD) rc = h3_dispatch<A_DENSE, E_EDGE_FWD>(NT, KCH, p, stats_nblk, s);
-    else if (amode == A_DENSE && emode == E_BWD_INPLACE) rc = h3_dispatch<A_DENSE, E_BWD_INPLACE>(NT, KCH, p, stats_nblk, s);
-    else if (amode == A_DENSE && emode == E_BWD_GATHER) rc = h3_dispatch<A_DENSE, E_BWD_GATHER>(NT, KCH, p, stats_nblk, s);
-    if (rc == GPE_ENOTSUP_SHAPE) return 0;
-    if (rc == GPE_OK) rc = gpe_edge_pseudo_fold(p, fold, s);
-    if (rc != GPE_OK) return rc;
-    if (tracks && p_in.user_amax_out && p_in.tracked) *p_in.tracked = 1;
-    return 1;
+// Two planes of a 200 x 200 weight fit a lone wave: every tile shape, every k (k = 16 / 5 / 4 at the shipped widths run on the
+// two-waves-per-SIMD kernel first: gpe_edgegemm_w8.hip)
+struct F16x3Menu { static constexpr bool has(int, int, int, int) { return true; } };
+
+int gpe_edge_f16x3(const RgParams& p, int amode, int emode, int NT, int KCH, int stats_nblk, hipStream_t s)
+{
+    return split_select<SplitF16x2, F16x3Menu>(p, amode, emode, NT, KCH, stats_nblk, s);
 }

@@ -28,7 +28,7 @@
 //     four partial products meet in LDS — in the rows of the just-consumed A buffer that the SAME wave re-stages next, so no
 //     extra barrier — and are summed in a fixed order (bit-reproducible).
 #pragma once
-#include "gpe_rowgemm.h"
+#include "gpe_edge_dispatch.h"
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -835,7 +835,7 @@ __global__ __launch_bounds__(256, 1) void gpe_edgegemm_split_kernel(RgParams p, 
 // Left-over scheme (template parameter LEFT) per kernel kind of the k = 16 two-plane instances.  GPE_H3_LEFT = four digits
 // "F2 F3 B3 B2" (gather forward, dense forward, in-place backward, gathered backward), each 0 or 2, overrides the table
 // (scheme 1 was measured — profiles/r04_c_left_schemes.md — never the fastest, and is no longer instantiated).
-static int x6_left_scheme(int amode, int emode)
+static int split_left_scheme(int kind)
 {
     static int tab[4] = {-1, 0, 0, 0};
     if (tab[0] < 0) {
@@ -847,106 +847,72 @@ static int x6_left_scheme(int amode, int emode)
             tab[i] = v;
         }
     }
-    const int kind = (emode == E_EDGE_FWD) ? (amode == A_GATHER ? 0 : 1) : (emode == E_BWD_INPLACE ? 2 : 3);
     return tab[kind];
 }
 
 template <class SP, int AQ, int BQ, int KCH, int AMODE, int EMODE, bool K16, bool PSEUDO = false, int AGGT = -1, int LEFT = 0,
           bool LAZY = false>
-static int x6_launch_k(const RgParams& p, int stats_nblk, hipStream_t s)
+static int split_launch_k(const RgParams& p, int stats_nblk, hipStream_t s)
 {
     constexpr int NT = 4 * AQ + BQ;
     constexpr int LDA = 16 * KCH + 4, LDC = x6_ldc<SP>(NT, KCH);
     constexpr int AWORDS = SP::SCALED ? (2 * RG_BM * 16 * x6_pchunks(KCH)) / 4 : RG_BM * LDA;
     const size_t lds = (size_t)(2 * AWORDS + RG_BM * LDC) * sizeof(float);
     // 16 bytes of static __shared__ (amax_sh) sit beside the dynamic image
-    GPE_ENSURE_MAX_LDS_N((gpe_edgegemm_split_kernel<SP, AQ, BQ, KCH, AMODE, EMODE, K16, PSEUDO, AGGT, LEFT, LAZY>), 160 * 1024 - 64);
-    int gx = gpe_num_cus();
-    if (gx > p.num_tiles) gx = p.num_tiles;
-    if (stats_nblk > 0 && gx > stats_nblk) gx = stats_nblk;
-    hipLaunchKernelGGL((gpe_edgegemm_split_kernel<SP, AQ, BQ, KCH, AMODE, EMODE, K16, PSEUDO, AGGT, LEFT, LAZY>), dim3(gx), dim3(256), lds, s, p, stats_nblk);
-    GPE_CHECK_LAUNCH();
-    return GPE_OK;
+    return gpe_edge_launch<gpe_edgegemm_split_kernel<SP, AQ, BQ, KCH, AMODE, EMODE, K16, PSEUDO, AGGT, LEFT, LAZY>, 256, GPE_EDGE_LDS_CAP_STATIC>(
+        p, stats_nblk, lds, s);
 }
 
 template <class SP, int AQ, int BQ, int KCH, int AMODE, int EMODE>
-static int x6_launch(const RgParams& p, int stats_nblk, hipStream_t s)
+static int split_launch(const RgParams& p, int stats_nblk, hipStream_t s)
 {
     // only the k = 16 aggregated dense forward of the scaled policy stores fp16 rows / only its in-place backward forms dz3 lazily
     if (p.out_half && !(SP::SCALED && EMODE == E_EDGE_FWD && AMODE == A_DENSE && p.k == 16 && p.agg && !p.pmagic)) return GPE_EINVAL;
     if (p.lz_g && !(SP::SCALED && EMODE == E_BWD_INPLACE && AMODE == A_DENSE && p.k == 16)) return GPE_EINVAL;
     if constexpr (EMODE != E_BWD_INPLACE) {          // the in-place backward needs nothing per point: never pseudo-points
         if (p.pmagic)
-            return p.k == 16 ? x6_launch_k<SP, AQ, BQ, KCH, AMODE, EMODE, true, true>(p, stats_nblk, s)
-                             : x6_launch_k<SP, AQ, BQ, KCH, AMODE, EMODE, false, true>(p, stats_nblk, s);
+            return p.k == 16 ? split_launch_k<SP, AQ, BQ, KCH, AMODE, EMODE, true, true>(p, stats_nblk, s)
+                             : split_launch_k<SP, AQ, BQ, KCH, AMODE, EMODE, false, true>(p, stats_nblk, s);
     }
     if constexpr (SP::SCALED) {
         // the benchmark configuration (k = 16, whole points): forward with the aggregation tracking compiled in / out, and the
-        // left-over scheme of the kernel kind (x6_left_scheme: GPE_H3_LEFT overrides for A/B measurements)
+        // left-over scheme of the kernel kind (split_left_scheme: GPE_H3_LEFT overrides for A/B measurements)
         if (p.k == 16) {
-            const int left = x6_left_scheme(AMODE, EMODE);
+            const int left = split_left_scheme(gpe_edge_kind(AMODE, EMODE));
             if constexpr (EMODE == E_EDGE_FWD) {
                 if (p.agg) {
                     if constexpr (AMODE == A_DENSE) {
                         // fp16 activation rows (row g): the aggregated dense forward only
                         if (p.out_half) {
-                            if (left == 2) return x6_launch_k<SP, AQ, BQ, KCH, AMODE, EMODE, true, false, 2, 2>(p, stats_nblk, s);
-                            return x6_launch_k<SP, AQ, BQ, KCH, AMODE, EMODE, true, false, 2, 0>(p, stats_nblk, s);
+                            if (left == 2) return split_launch_k<SP, AQ, BQ, KCH, AMODE, EMODE, true, false, 2, 2>(p, stats_nblk, s);
+                            return split_launch_k<SP, AQ, BQ, KCH, AMODE, EMODE, true, false, 2, 0>(p, stats_nblk, s);
                         }
                     }
-                    if (left == 2) return x6_launch_k<SP, AQ, BQ, KCH, AMODE, EMODE, true, false, 1, 2>(p, stats_nblk, s);
-                    return x6_launch_k<SP, AQ, BQ, KCH, AMODE, EMODE, true, false, 1, 0>(p, stats_nblk, s);
+                    if (left == 2) return split_launch_k<SP, AQ, BQ, KCH, AMODE, EMODE, true, false, 1, 2>(p, stats_nblk, s);
+                    return split_launch_k<SP, AQ, BQ, KCH, AMODE, EMODE, true, false, 1, 0>(p, stats_nblk, s);
                 }
-                if (left == 2) return x6_launch_k<SP, AQ, BQ, KCH, AMODE, EMODE, true, false, 0, 2>(p, stats_nblk, s);
-                return x6_launch_k<SP, AQ, BQ, KCH, AMODE, EMODE, true, false, 0, 0>(p, stats_nblk, s);
+                if (left == 2) return split_launch_k<SP, AQ, BQ, KCH, AMODE, EMODE, true, false, 0, 2>(p, stats_nblk, s);
+                return split_launch_k<SP, AQ, BQ, KCH, AMODE, EMODE, true, false, 0, 0>(p, stats_nblk, s);
             } else {
                 if constexpr (EMODE == E_BWD_INPLACE && AMODE == A_DENSE) {
                     // lazy dz3: always the rotated-slab instance (the in-loop scheme spills 33 registers to scratch with the extra
                     // per-lane coefficient quads; the rotated one does not)
-                    if (p.lz_g) return x6_launch_k<SP, AQ, BQ, KCH, AMODE, EMODE, true, false, -1, 2, true>(p, stats_nblk, s);
+                    if (p.lz_g) return split_launch_k<SP, AQ, BQ, KCH, AMODE, EMODE, true, false, -1, 2, true>(p, stats_nblk, s);
                 }
-                if (left == 2) return x6_launch_k<SP, AQ, BQ, KCH, AMODE, EMODE, true, false, -1, 2>(p, stats_nblk, s);
-                return x6_launch_k<SP, AQ, BQ, KCH, AMODE, EMODE, true, false, -1, 0>(p, stats_nblk, s);
+                if (left == 2) return split_launch_k<SP, AQ, BQ, KCH, AMODE, EMODE, true, false, -1, 2>(p, stats_nblk, s);
+                return split_launch_k<SP, AQ, BQ, KCH, AMODE, EMODE, true, false, -1, 0>(p, stats_nblk, s);
             }
         }
     }
-    return p.k == 16 ? x6_launch_k<SP, AQ, BQ, KCH, AMODE, EMODE, true>(p, stats_nblk, s)
-                     : x6_launch_k<SP, AQ, BQ, KCH, AMODE, EMODE, false>(p, stats_nblk, s);
+    return p.k == 16 ? split_launch_k<SP, AQ, BQ, KCH, AMODE, EMODE, true>(p, stats_nblk, s)
+                     : split_launch_k<SP, AQ, BQ, KCH, AMODE, EMODE, false>(p, stats_nblk, s);
 }
 
-// Shape checks + re-tiling shared by both policies.  Returns 1 when the shape is on the single-role split kernels' menu (then
-// `p` is the re-tiled copy: every wave owns whole points, R = 4 * npw * k with npw * k <= 16; `fold` says what to fold after the
-// launch when a k > 16 point ran as pseudo-points), 0 when it is not.
-static int x6_prepare(const RgParams& p_in, int amode, int emode, int stats_nblk, RgParams& p, GpeFold& fold)
+// Both policies: every (amode, emode) pair; the tile shapes are the policy's (MENU::has, gpe_edge_select)
+template <class SP, class MENU>
+static int split_select(const RgParams& p, int amode, int emode, int NT, int KCH, int stats_nblk, hipStream_t s)
 {
-    p = p_in;
-    fold = GpeFold{};
-    fold.f = 1;
-    if (p.N <= 96 || p.N > 208 || p.K <= 96 || p.K > 208) return 0;
-    if (emode != E_EDGE_FWD && (p.N & 3)) return 0;      // the backward epilogues use aligned 16-B coefficient loads
-    if (amode == A_GATHER && (p.K & 3)) return 0;
-    if (amode == A_DENSE && (p.a.inner > 0 || (p.a.stride_outer & 3) || p.a.stride_outer < ((p.K + 3) & ~3) ||
-                             (((uintptr_t)p.a.base) & 15)))
-        return 0;                                        // dense rows must be aligned + padded for plain 16-B loads
-    if (p.k < 1) return 0;
-    const bool per_point = amode == A_GATHER || emode == E_BWD_GATHER || (emode == E_EDGE_FWD && p.agg);
-    // k > 16: rows that need nothing per point are tiled 4 rows per "point"; the per-point variants run a point as f pseudo-points
-    // of <= 16 rows whose results are folded afterwards (gpe_edge_pseudo_setup / _fold, gpe_edgegemm_sr.hip)
-    if (!gpe_edge_pseudo_setup(p, per_point, emode, fold)) return 0;
-    const int npw = RG_PB / p.k;                         // points per wave per tile
-    if (per_point && npw > RG_NPW) return 0;
-    p.R = 4 * npw * p.k;
-    p.num_tiles = gpe_cdiv(p.M, p.R);
-    p.pin_tpc = 0;
-    if ((amode == A_GATHER || emode == E_BWD_GATHER) && p.pin_clouds > 0 && gpe_pin_clouds(p.pin_clouds) &&
-        p.pin_clouds % GPE_NXCD == 0) {
-        // gather variants only (dense streaming tiles have nothing to keep in L2): tiles must not straddle clouds and
-        // the launcher must keep gridDim.x a multiple of 8 with gridDim.x / 8 <= tiles per cloud
-        const long rows_per_cloud = p.M / p.pin_clouds;
-        const int gx = gpe_num_cus();
-        if (rows_per_cloud % p.R == 0 && gx % GPE_NXCD == 0 && gx <= p.num_tiles &&
-            (stats_nblk <= 0 || gx <= stats_nblk) && rows_per_cloud / p.R >= gx / GPE_NXCD)
-            p.pin_tpc = (int)(rows_per_cloud / p.R);
-    }
-    return 1;
+    return gpe_edge_select<MENU>(amode, emode, NT, KCH, [&](auto m, auto t) {
+        return split_launch<SP, decltype(t)::AQ, decltype(t)::BQ, decltype(t)::KCH, decltype(m)::amode, decltype(m)::emode>(p, stats_nblk, s);
+    });
 }

@@ -22,7 +22,7 @@
 #include "gpe_edgegemm_sr_kernel.h"
 
 // dense-A variants live in gpe_edgegemm_sr_dense.hip (compiled with another scheduling strategy)
-int gpe_sr_dispatch_dense(int emode, int NT, int KCH, const RgParams& p, int stats_nblk, hipStream_t s);
+int gpe_edge_sr_dense(const RgParams& p, int amode, int emode, int NT, int KCH, int stats_nblk, hipStream_t s);
 
 // ---- k > 16: merging the per-pseudo-point results ------------------------------------------------------------------------
 // A point with k > 16 neighbours is processed as f pseudo-points of kq = k / f rows (kq <= 16, so every wave still owns whole
@@ -74,50 +74,6 @@ __global__ void gpe_sr_fold_sum_kernel(const float* __restrict__ t, long npts, i
     st4(y + pt * ld + c, s);
 }
 
-// Shared by the single-role kernels (exact fp32 here, the split-precision ones of gpe_edgegemm_split_kernel.h): re-tiles a
-// k > 16 launch.  Returns 0 when the shape cannot run that way (the caller falls through to the producer/consumer kernel).
-int gpe_edge_pseudo_setup(RgParams& p, bool per_point, int emode, GpeFold& fd)
-{
-    fd = GpeFold{};
-    fd.f = 1;
-    if (p.k <= RG_PB) return 1;
-    if (!per_point) { p.k = 4; return 1; }
-    const long npts = p.M / p.k;
-    int best = 0;
-    for (int kq = RG_PB; kq >= RG_PB / RG_NPW; --kq)
-        if (p.k % kq == 0 && (RG_PB / kq) * kq > (best ? (RG_PB / best) * best : 0)) best = kq;
-    if (!best || npts * (p.k / best) >= (1L << 31) || (p.oldagg & 3) || (p.lddp & 3)) return 0;
-    fd.f = p.k / best; fd.kq = best; fd.npts = npts;
-    const long nps = npts * fd.f;                                     // pseudo-points
-    const bool want_agg = emode == E_EDGE_FWD && p.agg, want_dp = emode == E_BWD_GATHER;
-    const size_t agg_f = want_agg ? (size_t)nps * p.oldagg : 0, dp_f = want_dp ? (size_t)nps * p.lddp : 0;
-    const size_t bytes = (2 * agg_f + dp_f) * sizeof(float) + 2 * agg_f + 256;
-    char* ws = (bytes > 256 && bytes <= p.ws.pseudo_bytes) ? p.ws.pseudo : nullptr;
-    if (bytes > 256 && !ws) return 0;                                 // no workspace: the producer/consumer kernel runs it
-    if (want_agg) {
-        fd.mx = p.mx; fd.mn = p.mn; fd.amx = p.oamx; fd.amn = p.oamn;
-        p.mx = (float*)ws; p.mn = p.mx + agg_f;
-        p.oamx = (uint8_t*)(p.mn + agg_f); p.oamn = p.oamx + agg_f;
-    }
-    if (want_dp) { fd.dp = p.dP; p.dP = (float*)ws; }
-    p.k = best;
-    p.pmagic = (unsigned)(((1ull << 32) + fd.f - 1) / fd.f);          // x / f == umulhi(x, pmagic) for x < 2^31 / f
-    return 1;
-}
-
-// bytes of the pseudo-point part of an edge workspace for k neighbours, widths <= Cmax (0 for k <= 16)
-size_t gpe_edge_pseudo_bytes(long npts, int k, int Cmax)
-{
-    if (k <= RG_PB) return 0;
-    int best = 0;
-    for (int kq = RG_PB; kq >= RG_PB / RG_NPW; --kq)
-        if (k % kq == 0 && (RG_PB / kq) * kq > (best ? (RG_PB / best) * best : 0)) best = kq;
-    if (!best) return 0;
-    const size_t nps = (size_t)npts * (k / best), ld = (size_t)((Cmax + 3) & ~3);
-    // forward with aggregation: mx, mn (floats) + amx, amn (bytes); gathered backward: dP (floats) — the larger of the two
-    return nps * ld * (2 * sizeof(float) + 2) + 256;
-}
-
 // after the launch: folds the per-pseudo-point rows of the scratch image into the caller's per-point outputs
 int gpe_edge_pseudo_fold(const RgParams& p, const GpeFold& fd, hipStream_t s)
 {
@@ -136,49 +92,15 @@ int gpe_edge_pseudo_fold(const RgParams& p, const GpeFold& fd, hipStream_t s)
     return GPE_OK;
 }
 
-// Returns 1 and launches when the shape is on this kernel's menu, 0 when the caller should try the next kernel,
-// < 0 on a launch error.  `p` comes with the generic tiling (R = (64/k)*k); this kernel re-tiles so that every wave
-// owns whole points: R = 4 * npw * k with npw * k <= 16.
-int gpe_edgegemm_sr_try(const RgParams& p_in, int amode, int emode, int stats_nblk, hipStream_t s)
+// The exact-fp32 single-role family.  `p` is re-tiled (gpe_edge_retile): every wave owns whole points.
+int gpe_edge_sr(const RgParams& p_in, int amode, int emode, int NT, int KCH, int stats_nblk, hipStream_t s)
 {
+    // K = N = 200 with the in-place backward epilogue does not fit 512 VGPRs without heavy spilling (the instances exist, as they
+    // always did): left to the producer/consumer kernel; no shipped layer has that shape
+    if (NT == 13 && KCH == 13 && emode == E_BWD_INPLACE) return GPE_EDGE_NOT_MINE;
     RgParams p = p_in;
-    if (p.N <= 96 || p.N > 208 || p.K <= 96 || p.K > 208) return 0;
-    if (emode != E_EDGE_FWD && (p.N & 3)) return 0;      // the backward epilogues use aligned 16-B coefficient loads
-    if (amode == A_GATHER && (p.K & 3)) return 0;
-    if (amode == A_DENSE && (p.a.inner > 0 || (p.a.stride_outer & 3) || p.a.stride_outer < ((p.K + 3) & ~3) ||
-                             (((uintptr_t)p.a.base) & 15)))
-        return 0;                                        // dense rows must be aligned + padded for plain 16-B loads
-    if (p.k < 1) return 0;
-    const bool per_point = amode == A_GATHER || emode == E_BWD_GATHER || (emode == E_EDGE_FWD && p.agg);
-    // k > 16: rows that need nothing per point can be tiled any way (4 rows per "point": 64-row tiles); the per-point
-    // variants split a point into f pseudo-points of kq rows and fold the per-pseudo-point results afterwards
-    GpeFold fold;
-    if (!gpe_edge_pseudo_setup(p, per_point, emode, fold)) return 0;
-    const int npw = RG_PB / p.k;                         // points per wave per tile
-    if (per_point && npw > RG_NPW) return 0;
-    p.R = 4 * npw * p.k;
-    p.num_tiles = gpe_cdiv(p.M, p.R);
-    p.pin_tpc = 0;
-    if ((amode == A_GATHER || emode == E_BWD_GATHER) && p.pin_clouds > 0 && gpe_pin_clouds(p.pin_clouds) &&
-        p.pin_clouds % GPE_NXCD == 0) {
-        // gather variants only (dense streaming tiles have nothing to keep in L2): tiles must not straddle clouds and
-        // the launcher must keep gridDim.x a multiple of 8 with gridDim.x / 8 <= tiles per cloud
-        const long rows_per_cloud = p.M / p.pin_clouds;
-        const int gx = gpe_num_cus();
-        if (rows_per_cloud % p.R == 0 && gx % GPE_NXCD == 0 && gx <= p.num_tiles &&
-            (stats_nblk <= 0 || gx <= stats_nblk) && rows_per_cloud / p.R >= gx / GPE_NXCD)
-            p.pin_tpc = (int)(rows_per_cloud / p.R);
-    }
-    const int NT = (p.N <= 160) ? 10 : 13;
-    const int KCH = (p.K <= 160) ? 10 : 13;
     // dummy image of the straight-line instances: 64 rows x 512 floats (row pitches here are <= 256 floats)
     p.dummy = (p.ldo <= 512 && p.oldagg <= 512 && p.lddp <= 512) ? p.ws.dummy : nullptr;
-    int rc = GPE_EINVAL;
-    if (amode == A_GATHER && emode == E_EDGE_FWD) rc = sr_dispatch<A_GATHER, E_EDGE_FWD>(NT, KCH, p, stats_nblk, s);
-    else if (amode == A_DENSE && (emode == E_EDGE_FWD || emode == E_BWD_INPLACE))
-        rc = gpe_sr_dispatch_dense(emode, NT, KCH, p, stats_nblk, s);
-    else if (amode == A_DENSE && emode == E_BWD_GATHER) rc = sr_dispatch<A_DENSE, E_BWD_GATHER>(NT, KCH, p, stats_nblk, s);
-    if (rc == GPE_ENOTSUP_SHAPE) return 0;
-    if (rc == GPE_OK) rc = gpe_edge_pseudo_fold(p, fold, s);
-    return rc == GPE_OK ? 1 : rc;
+    return (amode == A_DENSE && emode != E_BWD_GATHER) ? gpe_edge_sr_dense(p, amode, emode, NT, KCH, stats_nblk, s)
+                                                       : sr_select<false>(p, amode, emode, NT, KCH, stats_nblk, s);
 }

@@ -4,9 +4,7 @@
 // variants do not.  /root/reference/nn/net_blocks.py:43-47,124-135.
 #include "gpe_edgegemm_sr_kernel.h"
 
-int gpe_sr_dispatch_dense(int emode, int NT, int KCH, const RgParams& p, int stats_nblk, hipStream_t s)
+int gpe_edge_sr_dense(const RgParams& p, int amode, int emode, int NT, int KCH, int stats_nblk, hipStream_t s)
 {
-    if (emode == E_EDGE_FWD) return sr_dispatch<A_DENSE, E_EDGE_FWD>(NT, KCH, p, stats_nblk, s);
-    if (emode == E_BWD_INPLACE) return sr_dispatch<A_DENSE, E_BWD_INPLACE>(NT, KCH, p, stats_nblk, s);
-    return GPE_EINVAL;
+    return sr_select<true>(p, amode, emode, NT, KCH, stats_nblk, s);
 }

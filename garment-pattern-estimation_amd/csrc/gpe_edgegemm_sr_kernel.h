@@ -5,7 +5,7 @@
 // (A/B in one session, scripts/sr_probe.py + GPE_HIP_LIB, us per launch at cfg 2: in-place backward 723 -> 676 under max-ilp,
 // dense forward 729 -> 712; the gather forward 790 -> 825 and the gathered backward unchanged, hence the split.)
 #pragma once
-#include "gpe_rowgemm.h"
+#include "gpe_edge_dispatch.h"
 #include <math.h>
 
 // K16: k == 16 (the benchmark configuration): every wave owns exactly ONE point per tile, so the slot index of a row is
@@ -514,22 +514,13 @@ __global__ __launch_bounds__(256, 1) void gpe_edgegemm_sr_kernel(RgParams p, int
 }
 
 // ---------------------------------------------------------------------------------------------------------
-static int sr_num_cus() { return gpe_num_cus(); }
-
 template <int AQ, int BQ, int KCH, int AMODE, int EMODE, int KC, bool HALF = false, int AGG = -1>
 static int sr_launch_k(const RgParams& p, int stats_nblk, hipStream_t s)
 {
     constexpr int NT = 4 * AQ + BQ;
     constexpr int LDA = 16 * KCH + 4, LDC = 16 * NT + 4;
     const size_t lds = (size_t)RG_BM * (2 * LDA + LDC) * sizeof(float);
-    GPE_ENSURE_MAX_LDS((gpe_edgegemm_sr_kernel<AQ, BQ, KCH, AMODE, EMODE, KC, HALF, AGG>));
-    int gx = sr_num_cus();
-    if (gx > p.num_tiles) gx = p.num_tiles;
-    if (stats_nblk > 0 && gx > stats_nblk) gx = stats_nblk;
-    hipLaunchKernelGGL((gpe_edgegemm_sr_kernel<AQ, BQ, KCH, AMODE, EMODE, KC, HALF, AGG>), dim3(gx), dim3(256), lds, s, p,
-                       stats_nblk);
-    GPE_CHECK_LAUNCH();
-    return GPE_OK;
+    return gpe_edge_launch<gpe_edgegemm_sr_kernel<AQ, BQ, KCH, AMODE, EMODE, KC, HALF, AGG>, 256, GPE_EDGE_LDS_CAP>(p, stats_nblk, lds, s);
 }
 
 template <int AQ, int BQ, int KCH, int AMODE, int EMODE>
@@ -565,16 +556,15 @@ static int sr_launch(const RgParams& p, int stats_nblk, hipStream_t s)
                 : sr_launch_k<AQ, BQ, KCH, AMODE, EMODE, 0>(p, stats_nblk, s);
 }
 
-template <int AMODE, int EMODE>
-static int sr_dispatch(int NT, int KCH, const RgParams& p, int stats_nblk, hipStream_t s)
+// The instances of this family, by translation unit (DENSE_TU: gpe_edgegemm_sr_dense.hip holds the dense forward and the in-place
+// backward)
+template <bool DENSE_TU> struct SrMenu {
+    static constexpr bool has(int amode, int emode, int NT, int KCH) { return (amode == A_DENSE && emode != E_BWD_GATHER) == DENSE_TU; }
+};
+template <bool DENSE_TU>
+static int sr_select(const RgParams& p, int amode, int emode, int NT, int KCH, int stats_nblk, hipStream_t s)
 {
-    // (K = N = 200 with the in-place backward epilogue does not fit 512 VGPRs without heavy spilling: left to the
-    // producer/consumer kernel; no shipped layer has that shape)
-    if (NT == 13 && KCH == 13 && EMODE == E_BWD_INPLACE) return GPE_ENOTSUP_SHAPE;
-    if (NT == 13 && KCH == 13) return sr_launch<3, 1, 13, AMODE, EMODE>(p, stats_nblk, s);
-    if (NT == 13 && KCH == 10) return sr_launch<3, 1, 10, AMODE, EMODE>(p, stats_nblk, s);
-    if (NT == 10 && KCH == 13) return sr_launch<2, 2, 13, AMODE, EMODE>(p, stats_nblk, s);
-    if (NT == 10 && KCH == 10) return sr_launch<2, 2, 10, AMODE, EMODE>(p, stats_nblk, s);
-    return GPE_EINVAL;
+    return gpe_edge_select<SrMenu<DENSE_TU>>(amode, emode, NT, KCH, [&](auto m, auto t) {
+        return sr_launch<decltype(t)::AQ, decltype(t)::BQ, decltype(t)::KCH, decltype(m)::amode, decltype(m)::emode>(p, stats_nblk, s);
+    });
 }
-

@@ -19,10 +19,8 @@
 //   single-role kernel (round 4)    443   462   524   499
 #include "gpe_edgegemm_w8_kernel.h"
 
-int gpe_w8_launch_f3(const RgParams& p, int stats_nblk, hipStream_t s);     // gpe_edgegemm_w8_f3.hip
-int gpe_w8_dispatch_k5(int amode, int emode, int NT, int KCH, const RgParams& p, int stats_nblk, hipStream_t s);   // gpe_edgegemm_w8_k5.hip
-int gpe_w8_dispatch_k4(int amode, int emode, int NT, int KCH, const RgParams& p, int stats_nblk, hipStream_t s);   // gpe_edgegemm_w8_k4.hip
-int gpe_w8_launch_b3(const RgParams& p, int stats_nblk, hipStream_t s);     // gpe_edgegemm_w8_b3.hip
+int gpe_w8_select_k5(const RgParams& p, int amode, int emode, int NT, int KCH, int stats_nblk, hipStream_t s);   // gpe_edgegemm_w8_k5.hip
+int gpe_w8_select_k4(const RgParams& p, int amode, int emode, int NT, int KCH, int stats_nblk, hipStream_t s);   // gpe_edgegemm_w8_k4.hip
 
 static int w8_enabled(int kind)
 {
@@ -39,32 +37,21 @@ static int w8_enabled(int kind)
     return tab[kind];
 }
 
-// `p` is the re-tiled copy x6_prepare made (R = 64 for k = 16) with the scale words in place.  Returns GPE_ENOTSUP_SHAPE when the
-// launch is not on this kernel's menu.
-int gpe_edgegemm_w8_dispatch(int amode, int emode, int NT, int KCH, const RgParams& p, int stats_nblk, hipStream_t s)
+// `p` is the re-tiled copy gpe_edge_retile made (R = 64 for k = 16) with the scale words in place.
+int gpe_edge_w8(const RgParams& p, int amode, int emode, int NT, int KCH, int stats_nblk, hipStream_t s)
 {
     // k = 16 (64-row tiles), k = 5 (60-row tiles: gpe_edgegemm_w8_k5.hip) or four-row (pseudo-)points (k = 20 as 5 x 4, and the rows
     // of any k > 16 that need nothing per point: gpe_edgegemm_w8_k4.hip); whole points only
     if (!((p.k == 16 && p.R == 64 && !p.pmagic) || (p.k == 5 && p.R == 60 && !p.pmagic) || (p.k == 4 && p.R == 64)) || p.M % p.k)
-        return GPE_ENOTSUP_SHAPE;
+        return GPE_EDGE_NOT_MINE;
     // the K-partials of the split tiles lie in the first 384 / 256 bytes of a plane row: bytes every commit rewrites
     const int kbytes = 2 * ((p.K + 3) & ~3);
-    if (kbytes < (KCH == 13 ? 384 : 256)) return GPE_ENOTSUP_SHAPE;
-    if (p.k != 16) {
-        const int kind = (emode == E_EDGE_FWD) ? (amode == A_GATHER ? 0 : 1) : (emode == E_BWD_INPLACE ? 2 : 3);
-        if (p.out_half || p.lz_g) return GPE_EINVAL;
-        if (!w8_enabled(kind)) return GPE_ENOTSUP_SHAPE;
-        return p.k == 5 ? gpe_w8_dispatch_k5(amode, emode, NT, KCH, p, stats_nblk, s) : gpe_w8_dispatch_k4(amode, emode, NT, KCH, p, stats_nblk, s);
-    }
-    if (p.out_half && !(emode == E_EDGE_FWD && amode == A_DENSE && p.agg)) return GPE_EINVAL;
-    if (p.lz_g && !(emode == E_BWD_INPLACE && amode == A_DENSE)) return GPE_EINVAL;
-    if (amode == A_GATHER && emode == E_EDGE_FWD && NT == 13 && KCH == 13 && !p.agg && w8_enabled(0))
-        return w8_launch<13, 13, A_GATHER, E_EDGE_FWD, 0, false>(p, stats_nblk, s);
-    if (amode == A_DENSE && emode == E_EDGE_FWD && NT == 10 && KCH == 13 && p.agg && w8_enabled(1))
-        return gpe_w8_launch_f3(p, stats_nblk, s);
-    if (amode == A_DENSE && emode == E_BWD_INPLACE && NT == 13 && KCH == 10 && w8_enabled(2))
-        return gpe_w8_launch_b3(p, stats_nblk, s);
-    if (amode == A_DENSE && emode == E_BWD_GATHER && NT == 13 && KCH == 13 && w8_enabled(3))
-        return w8_launch<13, 13, A_DENSE, E_BWD_GATHER, -1, false>(p, stats_nblk, s);
-    return GPE_ENOTSUP_SHAPE;
+    if (kbytes < (KCH == 13 ? 384 : 256)) return GPE_EDGE_NOT_MINE;
+    // fp16 activation rows: the k = 16 aggregated dense forward only; lazy dz3: the k = 16 in-place backward only
+    if (p.out_half && !(p.k == 16 && emode == E_EDGE_FWD && amode == A_DENSE && p.agg)) return GPE_EINVAL;
+    if (p.lz_g && !(p.k == 16 && emode == E_BWD_INPLACE && amode == A_DENSE)) return GPE_EINVAL;
+    if (!w8_enabled(gpe_edge_kind(amode, emode))) return GPE_EDGE_NOT_MINE;
+    return p.k == 16 ? w8_select<16>(p, amode, emode, NT, KCH, stats_nblk, s)
+           : p.k == 5 ? gpe_w8_select_k5(p, amode, emode, NT, KCH, stats_nblk, s)
+                      : gpe_w8_select_k4(p, amode, emode, NT, KCH, stats_nblk, s);
 }

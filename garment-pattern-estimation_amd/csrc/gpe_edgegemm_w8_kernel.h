@@ -47,7 +47,7 @@ __device__ __forceinline__ void w8_pin4(float4& v) { asm volatile("" : "+v"(v.x)
 // KK = rows per point, compile time: 16 (BASELINE cfg 2 / 3 / 5: one point of 16 rows per wave and tile), 5 (the shipped YAMLs,
 // models/att/att.yaml:94: three points of 5 rows per wave, 60-row tiles — rows 60..63 of the LDS tile belong to nobody: they are
 // multiplied like the others and never read) or 4 (BASELINE cfg 4, k = 20: a point runs as five PSEUDO-points of four rows whose
-// per-point results are folded afterwards — gpe_edge_pseudo_setup / _fold, gpe_edgegemm_sr.hip; RgParams::pmagic != 0 then turns
+// per-point results are folded afterwards — gpe_edge_retile / gpe_edge_pseudo_fold; RgParams::pmagic != 0 then turns
 // a pseudo-point number into its P row; rows that need nothing per point are simply tiled by four).  Every per-row decision (which point, which slot, where a point ends) is a
 // compile-time function of the row number u, so the slots stay straight-line code for both.
 template <int NT, int KCH, int AMODE, int EMODE, int AGGT, bool LAZY, int KK = 16>
@@ -768,11 +768,36 @@ static int w8_launch(const RgParams& p, int stats_nblk, hipStream_t s)
     constexpr int AWORDS = (2 * RG_BM * 16 * x6_pchunks(KCH)) / 4;
     const size_t lds = (size_t)(2 * AWORDS + RG_BM * LDC) * sizeof(float);
     // 32 bytes of static __shared__ (amax_sh, flag_sh) sit beside the dynamic image
-    GPE_ENSURE_MAX_LDS_N((gpe_edgegemm_w8_kernel<NT, KCH, AMODE, EMODE, AGGT, LAZY, KK>), 160 * 1024 - 64);
-    int gx = gpe_num_cus();
-    if (gx > p.num_tiles) gx = p.num_tiles;
-    if (stats_nblk > 0 && gx > stats_nblk) gx = stats_nblk;
-    hipLaunchKernelGGL((gpe_edgegemm_w8_kernel<NT, KCH, AMODE, EMODE, AGGT, LAZY, KK>), dim3(gx), dim3(512), lds, s, p, stats_nblk);
-    GPE_CHECK_LAUNCH();
-    return GPE_OK;
+    return gpe_edge_launch<gpe_edgegemm_w8_kernel<NT, KCH, AMODE, EMODE, AGGT, LAZY, KK>, 512, GPE_EDGE_LDS_CAP_STATIC>(p, stats_nblk, lds, s);
+}
+
+// The menu of this family: the four launches of an EdgeConv layer at the shipped widths —
+//   F2  gather forward 200 -> 200, no aggregation   (13 output tiles x 13 K chunks)
+//   F3  dense forward 200 -> 150 + max / min        (10 x 13)
+//   B3  in-place backward 150 -> 200                (13 x 10)
+//   B2  gathered backward 200 -> 200                (13 x 13)
+struct W8Menu {
+    static constexpr bool has(int amode, int emode, int NT, int KCH)
+    {
+        const int kind = gpe_edge_kind(amode, emode);
+        return kind == GPE_EDGE_F3 ? (NT == 10 && KCH == 13) : kind == GPE_EDGE_B3 ? (NT == 13 && KCH == 10) : (NT == 13 && KCH == 13);
+    }
+};
+// k = 16: F3 and B3 are instantiated in translation units of their own (other compile flags: table in gpe_edgegemm_w8.hip), with
+// their fp16-row / lazy-dz3 variants
+int gpe_w8_launch_f3(const RgParams& p, int stats_nblk, hipStream_t s);     // gpe_edgegemm_w8_f3.hip
+int gpe_w8_launch_b3(const RgParams& p, int stats_nblk, hipStream_t s);     // gpe_edgegemm_w8_b3.hip
+
+// ... for KK rows per point: instantiated once per KK, each from its own translation unit (gpe_edgegemm_w8.hip, _k5, _k4)
+template <int KK>
+static int w8_select(const RgParams& p, int amode, int emode, int NT, int KCH, int stats_nblk, hipStream_t s)
+{
+    return gpe_edge_select<W8Menu>(amode, emode, NT, KCH, [&](auto m, auto t) -> int {
+        using M = decltype(m);
+        using T = decltype(t);
+        if ((M::kind == GPE_EDGE_F2 && p.agg) || (M::kind == GPE_EDGE_F3 && !p.agg)) return GPE_EDGE_NOT_MINE;
+        if constexpr (KK == 16 && M::kind == GPE_EDGE_F3) return gpe_w8_launch_f3(p, stats_nblk, s);
+        else if constexpr (KK == 16 && M::kind == GPE_EDGE_B3) return gpe_w8_launch_b3(p, stats_nblk, s);
+        else return w8_launch<T::NT, T::KCH, M::amode, M::emode, M::kind == GPE_EDGE_F2 ? 0 : M::kind == GPE_EDGE_F3 ? 1 : -1, false, KK>(p, stats_nblk, s);
+    });
 }

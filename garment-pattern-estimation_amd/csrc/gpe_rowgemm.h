@@ -7,7 +7,6 @@
 #define RG_KSLAB 256
 #define RG_PB 16          // single-role / split edge kernels: rows a wave stages / finishes per tile
 #define RG_NPW 4          // ... max points per wave per tile (gather / aggregation paths)
-#define GPE_ENOTSUP_SHAPE 12345      // launch plumbing of the edge kernels: no instance for this shape (the caller tries the next family)
 
 enum { A_DENSE = 0, A_GATHER = 1 };
 enum { E_LINEAR = 0, E_EDGE_FWD = 1, E_BWD_INPLACE = 2, E_BWD_GATHER = 3 };
@@ -39,7 +38,7 @@ struct RgParams {
     int pin_tpc;
     int rev;                                     // walk the tile sequence from the far end (gpe_common.h GpeTileSeq)
     int pin_clouds;         // B when the caller's rows are B equal clouds (edge kernels), else 0
-    // k > 16 on the single-role kernels: a point's k rows are handled as f pseudo-points of k/f rows (gpe_edgegemm_sr.hip);
+    // k > 16 on the single-role kernels: a point's k rows are handled as f pseudo-points of k/f rows (gpe_edge_dispatch.hip);
     // the P row of pseudo-point x is then x / f = umulhi(x, pmagic).  0 = pseudo-points are points.
     unsigned pmagic;
     // 64 KB+ scratch image that absorbs the epilogue stores of a wave with nothing valid to finish (straight-line instances of
@@ -68,15 +67,14 @@ struct RgParams {
     int* tracked;                   // set to 1 by a kernel path that filled user_amax_out itself
 };
 
-// k > 16 on the single-role kernels (gpe_edgegemm_sr.hip): what gpe_edge_pseudo_setup redirected to scratch, for the fold
+// k > 16 on the single-role kernels: what gpe_edge_retile (gpe_edge_dispatch.hip) redirected to scratch, for the fold
 struct GpeFold {
     int f, kq;              // pseudo-points per point (1 = nothing to fold), rows per pseudo-point
     long npts;
     float *mx, *mn, *dp;    // the caller's per-point outputs (NULL = not redirected)
     uint8_t *amx, *amn;
 };
-int gpe_edge_pseudo_setup(RgParams& p, bool per_point, int emode, GpeFold& fd);
-int gpe_edge_pseudo_fold(const RgParams& p, const GpeFold& fd, hipStream_t s);
+int gpe_edge_pseudo_fold(const RgParams& p, const GpeFold& fd, hipStream_t s);   // gpe_edgegemm_sr.hip
 
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }

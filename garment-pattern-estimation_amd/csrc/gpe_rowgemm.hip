@@ -18,7 +18,7 @@
 // everything else (LDS traffic, gathers from L2/MALL, stores) hides underneath.
 #include "gpe_common.h"
 
-#include "gpe_rowgemm.h"
+#include "gpe_edge_dispatch.h"
 
 // ---------------------------------------------------------------------------------------------------------
 // A-tile producers: fill As[64][lda] columns [0, kp) for the K slab [ks, ks+kslab)
@@ -203,12 +203,11 @@ static int rg_pick_nt_single(int N)   // smallest instantiated NT whose block co
 
 // single-stage kernel for latency-bound shapes (gpe_smallgemm.hip)
 int gpe_smallgemm_linear(const RgParams& r, hipStream_t s);
-// register-stationary fast path for the shipped edge-MLP sizes (gpe_edgegemm.hip): 1 launched, 0 not on its menu
+// register-stationary fast path for the shipped edge-MLP sizes (gpe_edge_dispatch.hip): 1 launched, 0 not on its menu, < 0 error
 int gpe_edgegemm_try(const RgParams& p, int amode, int emode, int stats_nblk, hipStream_t s);
 
 void gpe_edgegemm_set_math(int m);
 void gpe_redgemm_set_math(int m);
-size_t gpe_edge_pseudo_bytes(long npts, int k, int Cmax);   // gpe_edgegemm_sr.hip
 
 int gpe_gemm_x6_linear(const GpeRows& a, const float* wp, int Npad, int Kq, const float* bias, const GpeRows& addend, float* y,
                        long y_so, long y_si, int y_inner, long M, int N, int K, int act, hipStream_t s);      // gpe_gemm_x6.hip
@@ -388,7 +387,7 @@ extern "C" int gpe_edge_lazy_dz3_ok(int B, int N, int k, int F, int Cprev)
 {
     static const int dbg_off = gpe_dbg_env("GPE_LAZY_DZ3", 1) == 0;   // A/B measurements
     if (dbg_off || (g_gpe_dbg & 512) || g_gpe_math != 4 || k != 16 || B <= 0 || N <= 0) return 0;    // gpe_debug_set(512): eager dz3
-    if (F <= 96 || F > 208 || Cprev <= 96 || Cprev > 208 || (Cprev & 3)) return 0;
+    if (!gpe_edge_width_ok(F) || !gpe_edge_width_ok(Cprev) || (Cprev & 3)) return 0;
     if (gpe_cdiv(Cprev, 16) != 13 || (gpe_cdiv(F, 16) != 10 && gpe_cdiv(F, 16) != 13)) return 0;   // the fp16 reduce-GEMM's instantiated shapes
     const long rows = (long)B * N * k;
     return rows >= gpe_h3_min_rows() && rows < (1L << 31) && rows / 32 >= 4L * 2 * gpe_num_cus();
