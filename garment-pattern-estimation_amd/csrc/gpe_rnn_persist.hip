@@ -28,8 +28,7 @@
 // normalised PER WAVE by the largest magnitude the wave just loaded (each wave owns its partial accumulator, so the scale is
 // undone before the partials meet) — no amax words, no atomics.
 #include "gpe_device.h"
-
-extern "C" int gpe_debug_get(void);
+#include "gpe_rnn_seq.h"
 
 #define PS_MAXL 4
 #define PS_LDC 68                 // forward C tile pitch (64 gate columns + 4)
@@ -386,122 +385,73 @@ __global__ __launch_bounds__(256) void gpe_rnn_persist_bwd_kernel(PsBwdParams p)
 // =====================================================================================================================
 // host side
 // =====================================================================================================================
-struct PsPlan { int NB, NRT, RG, grid; };
-
 // gpe_debug_set bits (measurement aids): 1024 = never the persistent kernels; 2048 / 4096 = allow them for a stack whose row tiles
 // outnumber the row groups the chip can hold (forward / backward: several row tiles per workgroup)
-static bool ps_plan(int gates, int L, int T, int Bn, int H, bool bwd, PsPlan& pl)
+static bool ps_plan(int gates, int L, int T, int Bn, int H, bool bwd, GpeRnnPlan& pl)
 {
-    const int dbg = gpe_debug_get();
-    if (gates != 4 || L < 1 || L > PS_MAXL || T < 1 || Bn < 1 || H < 1 || H > 256 || (dbg & 1024)) return false;
-    pl.NB = gpe_cdiv(H, 16);
-    pl.NRT = gpe_cdiv(Bn, 16);
-    const int cus = gpe_num_cus();
-    const int per = L * pl.NB;
-    if (cus <= 0 || per > cus) return false;
-    pl.RG = cus / per < pl.NRT ? cus / per : pl.NRT;
-    if (pl.RG < pl.NRT && !(dbg & (bwd ? 4096 : 2048))) return false;
-    pl.grid = per * pl.RG;
+    if (!gpe_rnn_plan_begin(gates, L, PS_MAXL, T, Bn, H, 1024, pl)) return false;
+    pl.RG = pl.rgmax;
+    if (pl.RG < pl.NRT && !(gpe_debug_get() & (bwd ? 4096 : 2048))) return false;
+    pl.grid = pl.per * pl.RG;
     return true;
 }
 
-// bytes of the arrival counters (0: this stack does not run persistently)
-static long ps_flag_bytes(int L, int T, const PsPlan& pl) { return (((long)L * T * pl.NRT * 4) + 255) & ~255L; }
-static long ps_trace_bytes(int T, const PsPlan& pl) { return (gpe_debug_get() & 8192) ? (long)pl.grid * T * 8 * 8 : 0; }
+// [L][T][NRT] arrival counters | trace; zeroed as ONE image in front of every launch
+static GpeRnnWs ps_ws_layout(int L, int T, const GpeRnnPlan& pl)
+{
+    return {(((long)L * T * pl.NRT * 4) + 255) & ~255L, 0, (gpe_debug_get() & 8192) ? (long)pl.grid * T * 8 * 8 : 0};
+}
 
 long gpe_rnn_persist_ws_bytes(int gates, int L, int T, int Bn, int H, int bwd)
 {
-    PsPlan pl;
+    GpeRnnPlan pl;
     if (!ps_plan(gates, L, T, Bn, H, bwd != 0, pl)) return 0;
-    return ps_flag_bytes(L, T, pl) + ps_trace_bytes(T, pl);
+    return ps_ws_layout(L, T, pl).total();
 }
 
-// 1 = launched, 0 = not eligible (the caller runs the diagonal launches), < 0 = error
-int gpe_rnn_persist_fwd(int L, int T, int Bn, int H, const float* xproj0, long xp0_sb, long xp0_st, const void* const* whh,
-                        const void* const* wih, const void* const* bias, float* hs, long hs_sl, long hs_sb, long hs_st, float* cs,
-                        long cs_sl, long cs_st, float* saved, long sv_sl, long sv_st, bool h3, const void* const* whh_amax,
-                        const void* const* wih_amax, void* ws, long ws_bytes, hipStream_t s)
+int gpe_rnn_persist_fwd(const GpeRnnSeq& q)
 {
-    PsPlan pl;
-    if (!ps_plan(4, L, T, Bn, H, false, pl)) return 0;
-    const long need = ps_flag_bytes(L, T, pl), ntrace = ps_trace_bytes(T, pl);
-    if (!ws || ws_bytes < need + ntrace || (((uintptr_t)ws) & 7)) return 0;
-    if ((long)Bn * hs_sb * 4 >= (1L << 31) || (hs_sb & 3) || (hs_st & 3) || (((uintptr_t)hs) & 15)) return 0;
-    const int KP = h3 ? gpe_round_up(H, 32) : gpe_round_up(H, 16);
-    const size_t lds = (size_t)(L > 1 ? 2 : 1) * KP * 256 + 4 * 16 * PS_LDC * 4;
-    if (lds > 160 * 1024) return 0;
+    GpeRnnPlan pl;
+    if (!ps_plan(q.G, q.L, q.T, q.Bn, q.H, false, pl)) return GPE_RNN_NOT_MINE;
+    const GpeRnnWs lay = ps_ws_layout(q.L, q.T, pl);
+    if (!lay.fits(q.ws, q.ws_bytes, 8)) return GPE_RNN_NOT_MINE;
+    if ((long)q.Bn * q.hs_sb * 4 >= (1L << 31) || (q.hs_sb & 3) || (q.hs_st & 3) || (((uintptr_t)q.hs) & 15)) return GPE_RNN_NOT_MINE;
+    const int KP = q.f16 ? gpe_round_up(q.H, 32) : gpe_round_up(q.H, 16);
+    const size_t lds = (size_t)(q.L > 1 ? 2 : 1) * KP * 256 + 4 * 16 * PS_LDC * 4;
+    if (lds > GPE_RNN_LDS_CAP) return GPE_RNN_NOT_MINE;
     PsFwdParams p = {};
-    p.L = L; p.T = T; p.Bn = Bn; p.H = H; p.NB = pl.NB; p.RG = pl.RG; p.NRT = pl.NRT;
-    p.xproj0 = xproj0; p.xp0_sb = xp0_sb; p.xp0_st = xp0_st;
-    for (int l = 0; l < L; ++l) {
-        p.w0[l] = whh[l];
-        if (!whh[l] || (((uintptr_t)whh[l]) & 15)) return 0;
-        if (h3) p.s0[l] = (const unsigned*)whh_amax[l];
-        if (l > 0) {
-            if (!wih[l] || (((uintptr_t)wih[l]) & 15) || !bias[l]) return 0;
-            p.w1[l] = wih[l];
-            p.bias[l] = (const float*)bias[l];
-            if (h3) p.s1[l] = (const unsigned*)wih_amax[l];
-        }
-    }
-    p.hs = hs; p.hs_sl = hs_sl; p.hs_sb = hs_sb; p.hs_st = hs_st;
-    p.cs = cs; p.cs_sl = cs_sl; p.cs_st = cs_st;
-    p.saved = saved; p.sv_sl = sv_sl; p.sv_st = sv_st;
-    p.flags = (unsigned*)ws;
-    p.trace = ntrace ? (unsigned long long*)((char*)ws + need) : nullptr;
-    if (hipMemsetAsync(ws, 0, (size_t)(need + ntrace), s) != hipSuccess) return GPE_ELAUNCH;
-    if (h3) {
-        GPE_ENSURE_MAX_LDS(gpe_rnn_persist_fwd_kernel<true>);
-        hipLaunchKernelGGL(gpe_rnn_persist_fwd_kernel<true>, dim3(pl.grid), dim3(256), lds, s, p);
-    } else {
-        GPE_ENSURE_MAX_LDS(gpe_rnn_persist_fwd_kernel<false>);
-        hipLaunchKernelGGL(gpe_rnn_persist_fwd_kernel<false>, dim3(pl.grid), dim3(256), lds, s, p);
-    }
-    GPE_CHECK_LAUNCH();
-    return 1;
+    if (!gpe_rnn_fill_fwd(p, q, pl)) return GPE_RNN_NOT_MINE;
+    p.flags = (unsigned*)q.ws; p.trace = lay.trace_at(q.ws);
+    if (hipMemsetAsync(q.ws, 0, (size_t)lay.total(), q.s) != hipSuccess) return GPE_ELAUNCH;
+    return gpe_rnn_for_bool(q.f16, [&](auto h3) {
+        return gpe_rnn_launch<gpe_rnn_persist_fwd_kernel<decltype(h3)::value>, GPE_RNN_LDS_CAP>(dim3(pl.grid), 256, lds, q.s, p);
+    });
 }
 
-int gpe_rnn_persist_bwd(int L, int T, int Bn, int H, const float* dtop, long dt_sb, long dt_st, const float* d_hN,
-                        const float* d_cN, const void* const* whh_t, const void* const* wih_t, int KP, const float* cs, long cs_sl,
-                        long cs_st, const float* saved, long sv_sl, long sv_st, float* dgx, long dg_sl, long dg_sb, long dg_st,
-                        float* carry, bool h3, const void* const* whh_amax, const void* const* wih_amax, void* ws, long ws_bytes,
-                        hipStream_t s)
+int gpe_rnn_persist_bwd(const GpeRnnSeqBwd& q)
 {
-    PsPlan pl;
-    if (!ps_plan(4, L, T, Bn, H, true, pl)) return 0;
-    const long need = ps_flag_bytes(L, T, pl), ntrace = ps_trace_bytes(T, pl);
-    if (!ws || ws_bytes < need + ntrace || (((uintptr_t)ws) & 7)) return 0;
-    if ((long)Bn * dg_sb * 4 >= (1L << 31) || (dg_sb & 3) || (dg_st & 3) || (((uintptr_t)dgx) & 15) || (dg_sl & 3)) return 0;
-    if (KP < 4 * H || KP > 1024 || (KP & (h3 ? 31 : 15))) return 0;
-    const size_t lds = (size_t)(L > 1 ? 2 : 1) * KP * 64 + 4 * 16 * PS_LDB * 4;
-    if (lds > 160 * 1024) return 0;
+    GpeRnnPlan pl;
+    if (!ps_plan(q.G, q.L, q.T, q.Bn, q.H, true, pl)) return GPE_RNN_NOT_MINE;
+    const GpeRnnWs lay = ps_ws_layout(q.L, q.T, pl);
+    if (!lay.fits(q.part, lay.total(), 8)) return GPE_RNN_NOT_MINE;           // (gpe_rnn_seq_bwd_ws covers this layout)
+    if ((long)q.Bn * q.dg_sb * 4 >= (1L << 31) || (q.dg_sb & 3) || (q.dg_st & 3) || (((uintptr_t)q.dgx) & 15) || (q.dg_sl & 3))
+        return GPE_RNN_NOT_MINE;
+    // padded K (= 4H) extent of the transposed packs
+    const int K = 4 * q.H, KP = q.f16 ? gpe_round_up(K, 32) : (int)(gpe_packed_size(q.H, K) / gpe_round_up(q.H, 16));
+    if (KP < K || KP > 1024 || (KP & (q.f16 ? 31 : 15))) return GPE_RNN_NOT_MINE;
+    const size_t lds = (size_t)(q.L > 1 ? 2 : 1) * KP * 64 + 4 * 16 * PS_LDB * 4;
+    if (lds > GPE_RNN_LDS_CAP) return GPE_RNN_NOT_MINE;
     PsBwdParams p = {};
-    p.L = L; p.T = T; p.Bn = Bn; p.H = H; p.NB = pl.NB; p.RG = pl.RG; p.NRT = pl.NRT; p.KP = KP;
-    p.dtop = dtop; p.dt_sb = dt_sb; p.dt_st = dt_st; p.d_hN = d_hN; p.d_cN = d_cN;
-    for (int l = 0; l < L; ++l) {
-        if (!whh_t[l] || (((uintptr_t)whh_t[l]) & 15)) return 0;
-        p.w0[l] = whh_t[l];
-        if (h3) p.s0[l] = (const unsigned*)whh_amax[l];
-        if (l < L - 1) {
-            if (!wih_t[l + 1] || (((uintptr_t)wih_t[l + 1]) & 15)) return 0;
-            p.w1[l] = wih_t[l + 1];
-            if (h3) p.s1[l] = (const unsigned*)wih_amax[l + 1];
-        }
-    }
-    p.cs = cs; p.cs_sl = cs_sl; p.cs_st = cs_st;
-    p.saved = saved; p.sv_sl = sv_sl; p.sv_st = sv_st;
-    p.dgx = dgx; p.dg_sl = dg_sl; p.dg_sb = dg_sb; p.dg_st = dg_st;
-    p.carry = carry;
-    p.flags = (unsigned*)ws;
-    p.trace = ntrace ? (unsigned long long*)((char*)ws + need) : nullptr;
-    if (hipMemsetAsync(ws, 0, (size_t)(need + ntrace), s) != hipSuccess) return GPE_ELAUNCH;
-    if (h3) {
-        GPE_ENSURE_MAX_LDS(gpe_rnn_persist_bwd_kernel<true>);
-        hipLaunchKernelGGL(gpe_rnn_persist_bwd_kernel<true>, dim3(pl.grid), dim3(256), lds, s, p);
-    } else {
-        GPE_ENSURE_MAX_LDS(gpe_rnn_persist_bwd_kernel<false>);
-        hipLaunchKernelGGL(gpe_rnn_persist_bwd_kernel<false>, dim3(pl.grid), dim3(256), lds, s, p);
-    }
-    GPE_CHECK_LAUNCH();
-    return 1;
+    p.L = q.L; p.T = q.T; p.Bn = q.Bn; p.H = q.H; p.NB = pl.NB; p.RG = pl.RG; p.NRT = pl.NRT; p.KP = KP;
+    p.dtop = q.dtop; p.dt_sb = q.dt_sb; p.dt_st = q.dt_st; p.d_hN = q.d_hN; p.d_cN = q.d_cN;
+    if (!gpe_rnn_fill_tables(p, q.L, 1, q.f16 ? q.whh_tpl : q.whh_t, q.f16 ? q.wih_tpl : q.wih_t, q.whh_amax, q.wih_amax, q.f16))
+        return GPE_RNN_NOT_MINE;
+    p.cs = q.cs; p.cs_sl = q.cs_sl; p.cs_st = q.cs_st;
+    p.saved = q.saved; p.sv_sl = q.sv_sl; p.sv_st = q.sv_st;
+    p.dgx = q.dgx; p.dg_sl = q.dg_sl; p.dg_sb = q.dg_sb; p.dg_st = q.dg_st;
+    p.carry = q.carry; p.flags = (unsigned*)q.part; p.trace = lay.trace_at(q.part);
+    if (hipMemsetAsync(q.part, 0, (size_t)lay.total(), q.s) != hipSuccess) return GPE_ELAUNCH;
+    return gpe_rnn_for_bool(q.f16, [&](auto h3) {
+        return gpe_rnn_launch<gpe_rnn_persist_bwd_kernel<decltype(h3)::value>, GPE_RNN_LDS_CAP>(dim3(pl.grid), 256, lds, q.s, p);
+    });
 }

@@ -21,8 +21,7 @@
 // (workgroup, tile, step).
 // Counter (l, slot, rt) counts the unit blocks that published h_{l, slot - 1} of tile rt; slot 0 = the start state.
 #include "gpe_device.h"
-
-extern "C" int gpe_debug_get(void);
+#include "gpe_rnn_seq.h"
 
 #define PM_MAXL 4
 #define PM_MAXS 8                 // k-steps of 32: K (= units) <= 256
@@ -377,84 +376,57 @@ __global__ __launch_bounds__(64 * PM_NW) void gpe_rnn_pm_fwd_kernel(PmFwdParams 
 // =====================================================================================================================
 // host side
 // =====================================================================================================================
-struct PmPlan { int NB, NRT, RG, KP, grid; };
-
 // gpe_debug_set bit 131072 (measurement aid): never these kernels (the diagonal launches run instead)
-static bool pm_plan(int gates, int L, int T, int Bn, int H, PmPlan& pl)
+static bool pm_plan(int gates, int L, int T, int Bn, int H, GpeRnnPlan& pl)
 {
-    if (gates != 4 || L < 1 || L > PM_MAXL || T < 1 || Bn < 1 || H < 1 || H > 256 || (gpe_debug_get() & (1024 | 131072))) return false;
-    pl.NB = gpe_cdiv(H, 16);
-    pl.NRT = gpe_cdiv(Bn, 16);
+    if (!gpe_rnn_plan_begin(gates, L, PM_MAXL, T, Bn, H, 1024 | 131072, pl)) return false;
     pl.KP = gpe_round_up(H, 32);
     if (pl.KP != 16 * pl.NB) return false;            // every k-group of a published row is written by a unit block
-    const int cus = gpe_num_cus();
-    const int per = L * pl.NB;
-    if (cus <= 0 || per > cus) return false;
-    int rgmax = cus / per < pl.NRT ? cus / per : pl.NRT;
     // the critical wave walks ceil(ceil(NRT / RG) / 4) tiles per step: the fewest row groups that reach the minimum
     // (fewer readers of every state row, CUs left to other streams)
     static const int dbg_rg = gpe_dbg_env("GPE_PM_RG", 0);
-    int best = rgmax;
+    int best = pl.rgmax;
     auto crit = [&](int rgv) { return gpe_cdiv(gpe_cdiv(pl.NRT, rgv), 4); };       // per SIMD (PM_NW / 4 waves each)
-    for (int rgv = rgmax; rgv >= 1; --rgv) if (crit(rgv) <= crit(rgmax)) best = rgv;
-    if (dbg_rg > 0 && dbg_rg <= rgmax) best = dbg_rg;
+    for (int rgv = pl.rgmax; rgv >= 1; --rgv) if (crit(rgv) <= crit(pl.rgmax)) best = rgv;
+    if (dbg_rg > 0 && dbg_rg <= pl.rgmax) best = dbg_rg;
     pl.RG = best;
-    pl.grid = per * pl.RG;
+    pl.grid = pl.per * pl.RG;
     return true;
 }
 
-static long pm_flag_bytes(int L, int T, const PmPlan& pl) { return (long)L * (T + 1) * pl.NRT * PM_FS * 4; }
-static long pm_hsplit_bytes(int L, int T, const PmPlan& pl) { return (long)L * (T + 1) * 16 * pl.NRT * pl.KP * 4; }
-static long pm_trace_bytes(int T, const PmPlan& pl) { return (gpe_debug_get() & 8192) ? (long)pl.grid * PM_NW * T * PM_MAXQ * 8 * 8 : 0; }
+// [L][T + 1][NRT] arrival counters of PM_FS words | hsplit | trace; the counters (and the trace) are zeroed in front of every launch
+static GpeRnnWs pm_ws_layout(int L, int T, const GpeRnnPlan& pl)
+{
+    return {(long)L * (T + 1) * pl.NRT * PM_FS * 4, (long)L * (T + 1) * 16 * pl.NRT * pl.KP * 4,
+            (gpe_debug_get() & 8192) ? (long)pl.grid * PM_NW * T * PM_MAXQ * 8 * 8 : 0};
+}
 
 long gpe_rnn_pm_ws_bytes(int gates, int L, int T, int Bn, int H, int bwd)
 {
-    PmPlan pl;
+    GpeRnnPlan pl;
     if (bwd || !pm_plan(gates, L, T, Bn, H, pl)) return 0;
-    return pm_flag_bytes(L, T, pl) + pm_hsplit_bytes(L, T, pl) + pm_trace_bytes(T, pl);
+    return pm_ws_layout(L, T, pl).total();
 }
 
-// 1 = launched, 0 = not eligible (the caller runs the diagonal launches), < 0 = error
-int gpe_rnn_pm_fwd(int L, int T, int Bn, int H, const float* xproj0, long xp0_sb, long xp0_st, const void* const* whh,
-                   const void* const* wih, const void* const* bias, float* hs, long hs_sl, long hs_sb, long hs_st, float* cs,
-                   long cs_sl, long cs_st, float* saved, long sv_sl, long sv_st, const void* const* whh_amax,
-                   const void* const* wih_amax, void* ws, long ws_bytes, hipStream_t s)
+int gpe_rnn_pm_fwd(const GpeRnnSeq& q)
 {
-    PmPlan pl;
-    if (!pm_plan(4, L, T, Bn, H, pl)) return 0;
-    const long nflag = pm_flag_bytes(L, T, pl), nsplit = pm_hsplit_bytes(L, T, pl), ntrace = pm_trace_bytes(T, pl);
-    if (!ws || ws_bytes < nflag + nsplit + ntrace || (((uintptr_t)ws) & 15)) return 0;
-    if (16L * pl.NRT * pl.KP * 4 >= (1L << 31) || (hs_sb & 3) || (hs_st & 3) || (hs_sl & 3) || (((uintptr_t)hs) & 15)) return 0;
+    GpeRnnPlan pl;
+    if (!q.f16 || !pm_plan(q.G, q.L, q.T, q.Bn, q.H, pl)) return GPE_RNN_NOT_MINE;       // the weights are read as fp16 planes
+    const GpeRnnWs lay = pm_ws_layout(q.L, q.T, pl);
+    if (!lay.fits(q.ws, q.ws_bytes, 16)) return GPE_RNN_NOT_MINE;
+    if (16L * pl.NRT * pl.KP * 4 >= (1L << 31) || (q.hs_sb & 3) || (q.hs_st & 3) || (q.hs_sl & 3) || (((uintptr_t)q.hs) & 15))
+        return GPE_RNN_NOT_MINE;
     // LDS: the weight slices, behind them 16 KB of cell states; a layer-0 workgroup (one slice) also keeps 64 KB of addends there
     const size_t keep0 = (size_t)16 * 1024 * 5, keepn = (size_t)16 * 1024 + 256;
     size_t lds = (size_t)pl.KP * 256 + keep0;
-    if (L > 1 && (size_t)2 * pl.KP * 256 + keepn > lds) lds = (size_t)2 * pl.KP * 256 + keepn;
-    if (lds > 160 * 1024) return 0;
-    if (gpe_cdiv(gpe_cdiv(pl.NRT, pl.RG), PM_NW) > PM_MAXQ) return 0;
+    if (q.L > 1 && (size_t)2 * pl.KP * 256 + keepn > lds) lds = (size_t)2 * pl.KP * 256 + keepn;
+    if (lds > GPE_RNN_LDS_CAP) return GPE_RNN_NOT_MINE;
+    if (gpe_cdiv(gpe_cdiv(pl.NRT, pl.RG), PM_NW) > PM_MAXQ) return GPE_RNN_NOT_MINE;
     PmFwdParams p = {};
-    p.L = L; p.T = T; p.Bn = Bn; p.H = H; p.NB = pl.NB; p.RG = pl.RG; p.NRT = pl.NRT; p.KP = pl.KP;
-    p.xproj0 = xproj0; p.xp0_sb = xp0_sb; p.xp0_st = xp0_st;
-    for (int l = 0; l < L; ++l) {
-        if (!whh[l] || (((uintptr_t)whh[l]) & 15) || !whh_amax[l]) return 0;
-        p.w0[l] = whh[l];
-        p.s0[l] = (const unsigned*)whh_amax[l];
-        if (l > 0) {
-            if (!wih[l] || (((uintptr_t)wih[l]) & 15) || !bias[l] || !wih_amax[l]) return 0;
-            p.w1[l] = wih[l];
-            p.bias[l] = (const float*)bias[l];
-            p.s1[l] = (const unsigned*)wih_amax[l];
-        }
-    }
-    p.hs = hs; p.hs_sl = hs_sl; p.hs_sb = hs_sb; p.hs_st = hs_st;
-    p.cs = cs; p.cs_sl = cs_sl; p.cs_st = cs_st;
-    p.saved = saved; p.sv_sl = sv_sl; p.sv_st = sv_st;
-    p.flags = (unsigned*)ws;
-    p.hsplit = (char*)ws + nflag;
-    p.trace = ntrace ? (unsigned long long*)((char*)ws + nflag + nsplit) : nullptr;
-    if (hipMemsetAsync(ws, 0, (size_t)nflag, s) != hipSuccess) return GPE_ELAUNCH;
-    if (ntrace && hipMemsetAsync(p.trace, 0, (size_t)ntrace, s) != hipSuccess) return GPE_ELAUNCH;
-    GPE_ENSURE_MAX_LDS(gpe_rnn_pm_fwd_kernel);
-    hipLaunchKernelGGL(gpe_rnn_pm_fwd_kernel, dim3(pl.grid), dim3(64 * PM_NW), lds, s, p);
-    GPE_CHECK_LAUNCH();
-    return 1;
+    p.KP = pl.KP;
+    if (!gpe_rnn_fill_fwd(p, q, pl)) return GPE_RNN_NOT_MINE;       // (q.f16 holds: every amax word is checked)
+    p.flags = (unsigned*)q.ws; p.hsplit = lay.planes_at(q.ws); p.trace = lay.trace_at(q.ws);
+    if (hipMemsetAsync(q.ws, 0, (size_t)lay.flags, q.s) != hipSuccess) return GPE_ELAUNCH;
+    if (lay.trace && hipMemsetAsync(p.trace, 0, (size_t)lay.trace, q.s) != hipSuccess) return GPE_ELAUNCH;
+    return gpe_rnn_launch<gpe_rnn_pm_fwd_kernel, GPE_RNN_LDS_CAP>(dim3(pl.grid), 64 * PM_NW, lds, q.s, p);
 }

@@ -3,7 +3,7 @@
 //
 // A stack of L layers over T steps is L*T dependent cells when run layer by layer, but cell (l, t) only needs (l, t-1)
 // and (l-1, t): all cells of one anti-diagonal d = l + t are independent.  The two entry points below walk the T + L - 1
-// diagonals and launch every cell of a diagonal TOGETHER (blockIdx.z = cell):
+// diagonals (gpe_rnn_walk_diagonals, gpe_rnn_seq.h) and launch every cell of a diagonal TOGETHER (blockIdx.z = cell):
 //   forward : one fused launch per diagonal — gates = h_{l,t-1}.W_hh^T (+ h_{l-1,t}.W_ih^T for layers > 0, a second K
 //             segment) + addend, then the LSTM / GRU cell update in the epilogue (gate-interleaved packed weights, so
 //             the gates of a unit sit in one accumulator row);
@@ -13,34 +13,9 @@
 // Arithmetic: exact fp32 MFMA (v_mfma_f32_16x16x4_f32), same staging scheme as gpe_smallgemm.hip: a workgroup stages a
 // whole K slab (<= 256) of 64 rows and of its packed weight block, one barrier pair per slab.
 #include "gpe_rowgemm.h"
+#include "gpe_rnn_seq.h"
 #include <math.h>
 #include <stdlib.h>
-
-extern "C" int gpe_math_get(void);
-extern "C" int gpe_debug_get(void);
-extern "C" long gpe_packed_size(int N, int K);
-
-// gpe_rnn_persist.hip: the whole stack as ONE persistent launch (LSTM, <= 256 units, one workgroup per CU); 1 = launched,
-// 0 = not eligible, < 0 = error
-long gpe_rnn_persist_ws_bytes(int gates, int L, int T, int Bn, int H, int bwd);
-int gpe_rnn_persist_fwd(int L, int T, int Bn, int H, const float* xproj0, long xp0_sb, long xp0_st, const void* const* whh,
-                        const void* const* wih, const void* const* bias, float* hs, long hs_sl, long hs_sb, long hs_st, float* cs,
-                        long cs_sl, long cs_st, float* saved, long sv_sl, long sv_st, bool h3, const void* const* whh_amax,
-                        const void* const* wih_amax, void* ws, long ws_bytes, hipStream_t s);
-int gpe_rnn_persist_bwd(int L, int T, int Bn, int H, const float* dtop, long dt_sb, long dt_st, const float* d_hN,
-                        const float* d_cN, const void* const* whh_t, const void* const* wih_t, int KP, const float* cs, long cs_sl,
-                        long cs_st, const float* saved, long sv_sl, long sv_st, float* dgx, long dg_sl, long dg_sb, long dg_st,
-                        float* carry, bool h3, const void* const* whh_amax, const void* const* wih_amax, void* ws, long ws_bytes,
-                        hipStream_t s);
-
-// gpe_rnn_persist_mt.hip: the same for stacks with several row tiles per workgroup (f16x3 only; waves own row tiles)
-long gpe_rnn_pm_ws_bytes(int gates, int L, int T, int Bn, int H, int bwd);
-int gpe_rnn_pm_fwd(int L, int T, int Bn, int H, const float* xproj0, long xp0_sb, long xp0_st, const void* const* whh,
-                   const void* const* wih, const void* const* bias, float* hs, long hs_sl, long hs_sb, long hs_st, float* cs,
-                   long cs_sl, long cs_st, float* saved, long sv_sl, long sv_st, const void* const* whh_amax,
-                   const void* const* wih_amax, void* ws, long ws_bytes, hipStream_t s);
-
-#define WV_MAXCELL 4
 
 struct WvFwdCell {
     const float* a0; long a0_stride; const float* w0;       // h_{l,t-1} rows, gate-packed W_hh_l
@@ -53,98 +28,11 @@ struct WvFwdCell {
 };
 struct WvFwdParams { int Bn, H, Npad, ncell; WvFwdCell cell[WV_MAXCELL]; };
 
-// stage rows [row0, row0+64) x K columns of `a` (row pitch `stride`, 16-B aligned, padded to 4) and the packed weight block
-// of this workgroup (columns n0 .. n0+16*NT of a [K/4][Npad][4] packed matrix) into LDS, then run the slab's MFMAs
-template <int NT, int KS>
-__device__ __forceinline__ void wv_segment(const float* __restrict__ a, long stride, const float* __restrict__ wp, int K,
-                                           int Npad, int row0, int rv, int n0, float* As, float* Ws, int lda,
-                                           f32x4 (&acc)[NT], bool split = false)
-{
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int j = lane & 15, g = lane >> 4;
-    for (int ks = 0; ks < K; ks += KS) {
-        const int kslab = (K - ks < KS) ? (K - ks) : KS;
-        const int kp = (kslab + 15) & ~15;
-        __syncthreads();
-        {
-            const int c = lane << 2;
-            if (c < kp) {
-                const int nvalid = kslab - c;
-                const int cc = (nvalid > 0) ? c : 0;
-                float4 v[RG_BM / 4];
-#pragma unroll
-                for (int q = 0; q < RG_BM / 4; ++q) {
-                    const int r = wave + 4 * q;
-                    v[q] = ld4(a + (long)(row0 + (r < rv ? r : rv - 1)) * stride + ks + cc);
-                }
-#pragma unroll
-                for (int q = 0; q < RG_BM / 4; ++q) {
-                    const int r = wave + 4 * q;
-                    float4 o = v[q];
-                    if (r >= rv || nvalid <= 0) o = make_float4(0.f, 0.f, 0.f, 0.f);
-                    else {
-                        if (nvalid < 2) o.y = 0.f;
-                        if (nvalid < 3) o.z = 0.f;
-                        if (nvalid < 4) o.w = 0.f;
-                    }
-                    st4(&As[r * lda + c], o);
-                }
-            }
-        }
-        {
-            const int planes = (kp >> 4) * 4;
-            constexpr int per_plane = 16 * NT;
-            const int chunk0 = ks >> 4;
-            const int total = planes * per_plane;
-            constexpr int WB = 8;
-            for (int e0 = tid; e0 < total; e0 += 256 * WB) {
-                float4 v[WB];
-#pragma unroll
-                for (int u = 0; u < WB; ++u) {
-                    const int e = e0 + 256 * u;
-                    const int ec = (e < total) ? e : total - 1;
-                    const int pl = ec / per_plane, n = ec - pl * per_plane;
-                    const int nn = (n0 + n < Npad) ? n0 + n : Npad - 1;
-                    v[u] = ld4(wp + (((long)(chunk0 * 4 + pl)) * Npad + nn) * 4);
-                }
-#pragma unroll
-                for (int u = 0; u < WB; ++u) {
-                    const int e = e0 + 256 * u;
-                    if (e < total) {
-                        const int n = e % per_plane;
-                        st4(&Ws[e * 4], (n0 + n < Npad) ? v[u] : make_float4(0.f, 0.f, 0.f, 0.f));
-                    }
-                }
-            }
-        }
-        __syncthreads();
-        const int nchunks = kp >> 4;
-        // split: see wv_mma (defined below) — row tile (wave & 1), K half (wave >> 1)
-        const int rt = split ? (wave & 1) : wave;
-        const int half = (nchunks + 1) >> 1;
-        const int kc0 = (split && (wave >> 1)) ? half : 0;
-        const int kc1 = (split && !(wave >> 1)) ? half : nchunks;
-        for (int kc = kc0; kc < kc1; ++kc) {
-            const float4 a4 = ld4(&As[(16 * rt + j) * lda + kc * 16 + 4 * g]);
-            const float av[4] = {a4.x, a4.y, a4.z, a4.w};
-            float4 b4[NT];
-#pragma unroll
-            for (int n = 0; n < NT; ++n) b4[n] = ld4(&Ws[(((kc * 4 + g) * 16 * NT) + 16 * n + j) * 4]);
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-#pragma unroll
-                for (int n = 0; n < NT; ++n) {
-                    const float bv = (t == 0) ? b4[n].x : (t == 1) ? b4[n].y : (t == 2) ? b4[n].z : b4[n].w;
-                    acc[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[t], bv, acc[n], 0, 0, 0);
-                }
-            }
-        }
-    }
-}
-
-// ---- the same slab staging, split into fetch (global -> registers) / commit (registers -> LDS) / multiply, so that the
-// forward kernel can keep the NEXT slab's loads in flight under the current slab's MFMAs (a cell is 2-4 slabs: with the
-// loads exposed every slab cost ~2.5 us of L2 latency on top of ~2 us of matrix work) ----------------------------------------
+// ---- slab staging: rows [row0, row0+64) x K columns of `a` (row pitch `stride`, 16-B aligned, padded to 4) and the packed weight
+// block of this workgroup (columns n0 .. n0+16*NT of a [K/4][Npad][4] packed matrix) go into LDS, then the slab's MFMAs run — as
+// fetch (global -> registers) / commit (registers -> LDS) / multiply, so that the forward kernel can keep the NEXT slab's loads in
+// flight under the current slab's MFMAs (a cell is 2-4 slabs: with the loads exposed every slab cost ~2.5 us of L2 latency on top
+// of ~2 us of matrix work) -------------------------------------------------------------------------------------------------------
 template <int NT, int KS>
 struct WvRegs {
     float4 a[RG_BM / 4];
@@ -460,20 +348,6 @@ static int wv_ks()
     return ks;
 }
 
-template <int G, int KS, bool H3 = false>
-static int wv_fwd_launch_ks(const WvFwdParams& p, hipStream_t s)
-{
-    const int kp_max = gpe_round_up(p.H < KS ? p.H : KS, H3 ? 32 : 16);
-    const int lda = kp_max + 4, ldc = 16 * 2 * G + 4;
-    const size_t lds = ((size_t)RG_BM * (lda > ldc ? lda : ldc) + (size_t)kp_max * 16 * G) * sizeof(float);
-    if (lds > 160 * 1024) return GPE_EINVAL;
-    GPE_ENSURE_MAX_LDS((gpe_rnn_wave_fwd_kernel<G, KS, H3>));
-    hipLaunchKernelGGL((gpe_rnn_wave_fwd_kernel<G, KS, H3>), dim3(gpe_cdiv(p.Bn, RG_BM), gpe_cdiv(p.H, 16), p.ncell), dim3(256),
-                       lds, s, p);
-    GPE_CHECK_LAUNCH();
-    return GPE_OK;
-}
-
 template <int G>
 static int wv_fwd_launch(const WvFwdParams& p, bool h3, hipStream_t s)
 {
@@ -481,81 +355,60 @@ static int wv_fwd_launch(const WvFwdParams& p, bool h3, hipStream_t s)
     // (a 96-wide slab — 50 KB, three workgroups per CU, the 576-workgroup panel diagonal in one round — measured slower:
     // 686 vs 641 us per panel-decoder forward; three slabs per segment instead of two)
     const bool wide = wv_ks() == 256 || p.Bn <= RG_BM;
-    if (h3) return wide ? wv_fwd_launch_ks<G, 256, true>(p, s) : wv_fwd_launch_ks<G, 128, true>(p, s);
-    return wide ? wv_fwd_launch_ks<G, 256>(p, s) : wv_fwd_launch_ks<G, 128>(p, s);
+    return gpe_rnn_for_bool(h3, [&](auto h3c) {
+        return gpe_rnn_for_ks(wide ? 256 : 128, [&](auto ksc) {
+            constexpr bool H3 = decltype(h3c)::value;
+            constexpr int KS = decltype(ksc)::value;
+            const int kp_max = gpe_round_up(p.H < KS ? p.H : KS, H3 ? 32 : 16);
+            const int lda = kp_max + 4, ldc = 16 * 2 * G + 4;
+            const size_t lds = ((size_t)RG_BM * (lda > ldc ? lda : ldc) + (size_t)kp_max * 16 * G) * sizeof(float);
+            if (lds > GPE_RNN_LDS_CAP) return GPE_EINVAL;
+            return gpe_rnn_launch<gpe_rnn_wave_fwd_kernel<G, KS, H3>, GPE_RNN_LDS_CAP>(
+                dim3(gpe_cdiv(p.Bn, RG_BM), gpe_cdiv(p.H, 16), p.ncell), 256, lds, s, p);
+        });
+    });
 }
 
-extern "C" int gpe_rnn_seq_fwd(int gates, int L, int T, int Bn, int H, const float* xproj0, long xp0_sb, long xp0_st,
-                               const void* const* whh, const void* const* wih, const void* const* bias,
-                               const void* const* bhn, float* hs, long hs_sl, long hs_sb, long hs_st, float* cs, long cs_sl, long cs_st,
-                               float* saved, long sv_sl, long sv_st, const void* const* whh_pl, const void* const* wih_pl,
-                               const void* const* whh_amax, const void* const* wih_amax, void* ws, long ws_bytes, void* stream)
+// one fused launch per group of a diagonal's cells; takes every stack
+int gpe_rnn_wave_fwd(const GpeRnnSeq& q)
 {
-    if ((gates != 3 && gates != 4) || L <= 0 || T <= 0 || Bn <= 0 || H <= 0 || !xproj0 || !whh || !hs || !saved ||
-        (L > 1 && (!wih || !bias)) || (gates == 4 && !cs) || (gates == 3 && !bhn) || (hs_sb & 3) || (hs_st & 3))
-        return GPE_EINVAL;
-    const int G = gates;
-    // f16x3: the gate products on the fp16 pipe when the arithmetic mode asks for it and the caller supplies the plane packs and
-    // amax words of every weight (gpe_pack_multi kinds 9 + 8); else the exact fp32 instruction
-    static const int dbg_f32 = gpe_dbg_env("GPE_RNN_F32", 0);        // A/B measurements: keep the exact kernels
-    bool h3 = !dbg_f32 && gpe_math_get() == 4 && whh_pl && whh_amax && (L == 1 || (wih_pl && wih_amax));
-    for (int l = 0; h3 && l < L; ++l)
-        if (!whh_pl[l] || !whh_amax[l] || (l > 0 && (!wih_pl[l] || !wih_amax[l]))) h3 = false;
-    if (G == 4) {
-        // one persistent launch for the whole stack when it fits the chip (gpe_rnn_persist.hip)
-        const int rc = gpe_rnn_persist_fwd(L, T, Bn, H, xproj0, xp0_sb, xp0_st, h3 ? whh_pl : whh, h3 ? wih_pl : wih, bias, hs, hs_sl,
-                                           hs_sb, hs_st, cs, cs_sl, cs_st, saved, sv_sl, sv_st, h3, whh_amax, wih_amax, ws, ws_bytes,
-                                           (hipStream_t)stream);
-        if (rc != 0) return rc < 0 ? rc : GPE_OK;
-        if (h3) {
-            const int rc2 = gpe_rnn_pm_fwd(L, T, Bn, H, xproj0, xp0_sb, xp0_st, whh_pl, wih_pl, bias, hs, hs_sl, hs_sb, hs_st, cs, cs_sl,
-                                           cs_st, saved, sv_sl, sv_st, whh_amax, wih_amax, ws, ws_bytes, (hipStream_t)stream);
-            if (rc2 != 0) return rc2 < 0 ? rc2 : GPE_OK;
-        }
-    }
-    for (int d = 0; d <= T + L - 2; ++d) {
-        const int l_lo = (d - (T - 1) > 0) ? d - (T - 1) : 0;
-        const int l_hi = (d < L - 1) ? d : L - 1;
-        for (int l0 = l_lo; l0 <= l_hi; l0 += WV_MAXCELL) {
-            WvFwdParams p = {};
-            p.Bn = Bn; p.H = H; p.Npad = 16 * G * gpe_cdiv(H, 16);
-            int n = 0;
-            // highest layer first: workgroups are dispatched in blockIdx.z order and a 3-cell panel diagonal is 576
-            // workgroups on 512 slots — the second round should be the cheap layer-0 cells (one K segment instead of two)
-            const int l_top = (l_hi < l0 + WV_MAXCELL - 1) ? l_hi : l0 + WV_MAXCELL - 1;
-            for (int l = l_top; l >= l0; --l, ++n) {
-                const int t = d - l;
-                WvFwdCell& c = p.cell[n];
-                c.a0 = hs + l * hs_sl + (long)t * hs_st;             // h_{l,t-1} lives at time slot t
-                c.a0_stride = hs_sb;
-                c.w0 = (const float*)(h3 ? whh_pl[l] : whh[l]);
-                c.s0 = h3 ? (const unsigned*)whh_amax[l] : nullptr;
-                if (l > 0) {
-                    c.a1 = hs + (l - 1) * hs_sl + (long)(t + 1) * hs_st;   // h_{l-1,t} at slot t+1
-                    c.a1_stride = hs_sb;
-                    c.w1 = (const float*)(h3 ? wih_pl[l] : wih[l]);
-                    c.s1 = h3 ? (const unsigned*)wih_amax[l] : nullptr;
-                    c.xproj = (const float*)bias[l];
-                    c.xp_stride = 0;
-                } else {
-                    c.xproj = xproj0 + (long)t * xp0_st;
-                    c.xp_stride = xp0_sb;
-                }
-                if (G == 4) {
-                    c.c_prev = cs + l * cs_sl + (long)t * cs_st;
-                    c.c_out = cs + l * cs_sl + (long)(t + 1) * cs_st;
-                } else
-                    c.bhn = (const float*)bhn[l];
-                c.saved = saved + l * sv_sl + (long)t * sv_st;
-                c.h_out = hs + l * hs_sl + (long)(t + 1) * hs_st;
-                c.h_stride = hs_sb;
+    const int G = q.G;
+    return gpe_rnn_walk_diagonals(q.L, q.T, false, [&](int d, int l0, int l_top) {
+        WvFwdParams p = {};
+        p.Bn = q.Bn; p.H = q.H; p.Npad = 16 * G * gpe_cdiv(q.H, 16);
+        int n = 0;
+        // highest layer first: workgroups are dispatched in blockIdx.z order and a 3-cell panel diagonal is 576
+        // workgroups on 512 slots — the second round should be the cheap layer-0 cells (one K segment instead of two)
+        for (int l = l_top; l >= l0; --l, ++n) {
+            const int t = d - l;
+            WvFwdCell& c = p.cell[n];
+            c.a0 = q.h(l, t);                                    // h_{l,t-1} lives at time slot t
+            c.a0_stride = q.hs_sb;
+            c.w0 = (const float*)q.whh[l];
+            c.s0 = q.f16 ? (const unsigned*)q.whh_amax[l] : nullptr;
+            if (l > 0) {
+                c.a1 = q.h(l - 1, t + 1);                        // h_{l-1,t} at slot t+1
+                c.a1_stride = q.hs_sb;
+                c.w1 = (const float*)q.wih[l];
+                c.s1 = q.f16 ? (const unsigned*)q.wih_amax[l] : nullptr;
+                c.xproj = (const float*)q.bias[l];
+                c.xp_stride = 0;
+            } else {
+                c.xproj = q.xproj0 + (long)t * q.xp0_st;
+                c.xp_stride = q.xp0_sb;
             }
-            p.ncell = n;
-            const int rc = (G == 4) ? wv_fwd_launch<4>(p, h3, (hipStream_t)stream) : wv_fwd_launch<3>(p, h3, (hipStream_t)stream);
-            if (rc != GPE_OK) return rc;
+            if (G == 4) {
+                c.c_prev = q.c(l, t);
+                c.c_out = q.c(l, t + 1);
+            } else
+                c.bhn = (const float*)q.bhn[l];
+            c.saved = q.gates(l, t);
+            c.h_out = q.h(l, t + 1);
+            c.h_stride = q.hs_sb;
         }
-    }
-    return GPE_OK;
+        p.ncell = n;
+        return (G == 4) ? wv_fwd_launch<4>(p, q.f16, q.s) : wv_fwd_launch<3>(p, q.f16, q.s);
+    });
 }
 
 // =====================================================================================================================
@@ -767,52 +620,20 @@ __global__ void gpe_rnn_wave_cell_bwd_kernel(WvBwdParams p)
     }
 }
 
-extern "C" long gpe_rnn_seq_fwd_ws(int gates, int L, int T, int Bn, int H)
+// floats of the diagonal backward's workspace: partial images (row pitch H rounded up to 4: the fused kernel stores them in 16-byte
+// pieces) + one arrival counter per (diagonal, cell, row tile, column block) of the fused split-K + cell-backward launches
+long gpe_rnn_wave_bwd_ws_floats(int gates, int L, int T, int Bn, int H)
 {
-    if ((gates != 3 && gates != 4) || L <= 0 || T <= 0 || Bn <= 0 || H <= 0) return GPE_EINVAL;
-    const long a = gpe_rnn_persist_ws_bytes(gates, L, T, Bn, H, 0), b = gpe_rnn_pm_ws_bytes(gates, L, T, Bn, H, 0);
-    return a > b ? a : b;
-}
-
-extern "C" long gpe_rnn_seq_bwd_ws(int gates, int L, int T, int Bn, int H)
-{
-    if ((gates != 3 && gates != 4) || L <= 0 || T <= 0 || Bn <= 0 || H <= 0) return GPE_EINVAL;
     const int nz = gpe_cdiv(gates * H, 128);              // sized for the narrow slab (the wide one needs half)
     const int ncell = L < WV_MAXCELL ? L : WV_MAXCELL;
-    // partial images (row pitch H rounded up to 4: the fused kernel stores them in 16-byte pieces) + one arrival counter per
-    // (diagonal, cell, row tile, column block) of the fused split-K + cell-backward launches
-    const long diag = (long)ncell * 2 * nz * Bn * gpe_round_up(H, 4) + (long)(T + L) * WV_MAXCELL * gpe_cdiv(Bn, RG_BM) * gpe_cdiv(H, 64) + 64;
-    const long pers = gpe_rnn_persist_ws_bytes(gates, L, T, Bn, H, 1) / 4;     // arrival counters of the persistent kernel
-    return diag > pers ? diag : pers;
+    return (long)ncell * 2 * nz * Bn * gpe_round_up(H, 4) + (long)(T + L) * WV_MAXCELL * gpe_cdiv(Bn, RG_BM) * gpe_cdiv(H, 64) + 64;
 }
 
-// dgx / dgh: [L][Bn][T][G*H] (for LSTM pass the same buffer twice); carry: [2][L][Bn][H] scratch;
-// whh_t / wih_t: host arrays [L] of device pointers to the plain TRANSPOSED packs (gpe_pack_weight(.., transpose = 1));
-// d_hN / d_cN: gradients of the final states [L][Bn][H] or NULL.  On return carry[0 or 1] holds dc_0 / the z-gated dh_0 of
-// every layer at carry + (T & 1 ? .. ) — see carry_final below: the slot index written last is returned through *carry_slot.
-extern "C" int gpe_rnn_seq_bwd(int gates, int L, int T, int Bn, int H, const float* dtop, long dt_sb, long dt_st,
-                               const float* d_hN, const float* d_cN, const void* const* whh_t, const void* const* wih_t,
-                               const float* hs, long hs_sl, long hs_sb, long hs_st, const float* cs, long cs_sl, long cs_st,
-                               const float* saved, long sv_sl, long sv_st, float* dgx, float* dgh, long dg_sl, long dg_sb,
-                               long dg_st, float* part, float* carry, const void* const* whh_tpl, const void* const* wih_tpl,
-                               const void* const* whh_amax, const void* const* wih_amax, void* stream)
+// two launches per group of a diagonal's cells (split-K products, pointwise cell backward); takes every stack.  On return
+// carry slot 0 holds dc_0 / the z-gated dh_0 of every layer
+int gpe_rnn_wave_bwd(const GpeRnnSeqBwd& q)
 {
-    if ((gates != 3 && gates != 4) || L <= 0 || T <= 0 || Bn <= 0 || H <= 0 || !whh_t || !hs || !saved || !dgx || !dgh ||
-        !part || !carry || (L > 1 && !wih_t) || (gates == 4 && !cs) || (dg_sb & 3) || (dg_st & 3))
-        return GPE_EINVAL;
-    const int G = gates, K = G * H;
-    if (G == 4) {
-        // one persistent launch for the whole stack when it fits the chip (gpe_rnn_persist.hip); f16x3: the transposed plane packs
-        // (gpe_pack_multi kind 10) and amax words of every weight
-        bool h3 = gpe_math_get() == 4 && whh_tpl && whh_amax && (L == 1 || (wih_tpl && wih_amax));
-        for (int l = 0; h3 && l < L; ++l)
-            if (!whh_tpl[l] || !whh_amax[l] || (l > 0 && (!wih_tpl[l] || !wih_amax[l]))) h3 = false;
-        const int KP = h3 ? gpe_round_up(K, 32) : (int)(gpe_packed_size(H, K) / gpe_round_up(H, 16));
-        const int rc = gpe_rnn_persist_bwd(L, T, Bn, H, dtop, dt_sb, dt_st, d_hN, d_cN, h3 ? whh_tpl : whh_t, h3 ? wih_tpl : wih_t, KP,
-                                           cs, cs_sl, cs_st, saved, sv_sl, sv_st, dgx, dg_sl, dg_sb, dg_st, carry, h3, whh_amax, wih_amax,
-                                           part, gpe_rnn_persist_ws_bytes(4, L, T, Bn, H, 1), (hipStream_t)stream);
-        if (rc != 0) return rc < 0 ? rc : GPE_OK;
-    }
+    const int G = q.G, L = q.L, T = q.T, Bn = q.Bn, H = q.H, K = G * H;
     const int KS = wv_ks();
     // big batches: four slabs per workgroup (a 3-cell panel diagonal: 2304 single-slab workgroups in 4.5 rounds -> 480 in one,
     // a quarter of the partial images; measured 804 / 717 / 621 / 689 us per backward at 1 / 2 / 4 / 8 slabs); a single row
@@ -822,7 +643,6 @@ extern "C" int gpe_rnn_seq_bwd(int gates, int L, int T, int Bn, int H, const flo
     if (dbg_bj > 0 && Bn > 3 * RG_BM) jslabs = dbg_bj < gpe_cdiv(K, KS) ? dbg_bj : gpe_cdiv(K, KS);
     const int nz = gpe_cdiv(gpe_cdiv(K, KS), jslabs);
     const long BH = (long)Bn * H;
-    hipStream_t s = (hipStream_t)stream;
     // LSTM, gpe_debug_set(65536): the pointwise cell backward runs in the split-K launch itself (the last partial of an output block
     // to arrive does it): one launch per diagonal instead of two.  Built, bit-compatible (same tests), and
     // MEASURED SLOWER — cfg 2, one session, twice each: gpe_rnn_seq_bwd 0.838 ms with two launches, 1.115 / 1.117 ms fused (step
@@ -834,67 +654,59 @@ extern "C" int gpe_rnn_seq_bwd(int gates, int L, int T, int Bn, int H, const flo
     const long BHp = (long)Bn * Hp;
     const int gxr = gpe_cdiv(Bn, RG_BM), gyc = gpe_cdiv(H, 64);
     const int ncell_max = L < WV_MAXCELL ? L : WV_MAXCELL;
-    unsigned* cnt_base = reinterpret_cast<unsigned*>(part + (((long)ncell_max * 2 * nz * BHp + 15) & ~15L));
+    unsigned* cnt_base = reinterpret_cast<unsigned*>(q.part + (((long)ncell_max * 2 * nz * BHp + 15) & ~15L));
     const long cnt_per_launch = (long)WV_MAXCELL * gxr * gyc;
     int launch_no = 0;
-    if (fuse && hipMemsetAsync(cnt_base, 0, (size_t)(T + L) * cnt_per_launch * sizeof(unsigned), s) != hipSuccess) return GPE_ELAUNCH;
+    if (fuse && hipMemsetAsync(cnt_base, 0, (size_t)(T + L) * cnt_per_launch * sizeof(unsigned), q.s) != hipSuccess) return GPE_ELAUNCH;
     const size_t lds = ((size_t)RG_BM * (KS + 4) + (size_t)KS * 64) * sizeof(float);
-    if (KS == 256) GPE_ENSURE_MAX_LDS_N((gpe_rnn_wave_splitk_kernel<256>), 160 * 1024 - 64);     // (4 bytes of static __shared__ beside the dynamic image)
-    else GPE_ENSURE_MAX_LDS_N((gpe_rnn_wave_splitk_kernel<128>), 160 * 1024 - 64);
-    for (int d = T + L - 2; d >= 0; --d) {
-        const int l_lo = (d - (T - 1) > 0) ? d - (T - 1) : 0;
-        const int l_hi = (d < L - 1) ? d : L - 1;
-        for (int l0 = l_lo; l0 <= l_hi; l0 += WV_MAXCELL) {
-            WvBwdParams p = {};
-            p.Bn = Bn; p.H = H; p.K = K; p.Kpad_n = gpe_round_up(H, 16); p.nz = nz; p.jslabs = jslabs;
-            p.fuse = fuse; p.Hp = Hp; p.cnt = cnt_base + (long)launch_no * cnt_per_launch;
-            ++launch_no;
-            int n = 0, any_seg = 0;
-            for (int l = l0; l <= l_hi && n < WV_MAXCELL; ++l, ++n) {
-                const int t = d - l;
-                WvBwdCell& c = p.cell[n];
-                c.part = part + (long)n * 2 * nz * BHp;
-                if (t < T - 1) {                 // recurrent path: dGh_{l,t+1} . W_hh_l
-                    c.a[0] = dgh + l * dg_sl + (long)(t + 1) * dg_st; c.as[0] = dg_sb; c.w[0] = (const float*)whh_t[l];
-                    c.nseg_mask |= 1;
-                }
-                if (l < L - 1) {                 // from the layer above: dGx_{l+1,t} . W_ih_{l+1}
-                    c.a[1] = dgx + (l + 1) * dg_sl + (long)t * dg_st; c.as[1] = dg_sb; c.w[1] = (const float*)wih_t[l + 1];
-                    c.nseg_mask |= 2;
-                }
-                any_seg |= c.nseg_mask;
-                if (l == L - 1 && dtop) { c.dh_out = dtop + (long)t * dt_st; c.dho_stride = dt_sb; }
-                if (t == T - 1) {
-                    if (d_hN) c.dh_extra = d_hN + (long)l * BH;
-                    c.carry_in = (G == 4 && d_cN) ? d_cN + (long)l * BH : nullptr;
-                } else
-                    c.carry_in = carry + ((long)((t + 1) & 1) * L + l) * BH;
-                c.carry_out = carry + ((long)(t & 1) * L + l) * BH;
-                c.saved = saved + l * sv_sl + (long)t * sv_st;
-                if (G == 4) {
-                    c.c = cs + l * cs_sl + (long)(t + 1) * cs_st;
-                    c.c_prev = cs + l * cs_sl + (long)t * cs_st;
-                } else {
-                    c.h_prev = hs + l * hs_sl + (long)t * hs_st; c.hp_stride = hs_sb;
-                }
-                c.dgx = dgx + l * dg_sl + (long)t * dg_st;
-                c.dgh = dgh + l * dg_sl + (long)t * dg_st;
-                c.dg_stride = dg_sb;
+    return gpe_rnn_walk_diagonals(L, T, true, [&](int d, int l0, int l_top) {
+        WvBwdParams p = {};
+        p.Bn = Bn; p.H = H; p.K = K; p.Kpad_n = gpe_round_up(H, 16); p.nz = nz; p.jslabs = jslabs;
+        p.fuse = fuse; p.Hp = Hp; p.cnt = cnt_base + (long)launch_no * cnt_per_launch;
+        ++launch_no;
+        int n = 0, any_seg = 0;
+        for (int l = l0; l <= l_top; ++l, ++n) {
+            const int t = d - l;
+            WvBwdCell& c = p.cell[n];
+            c.part = q.part + (long)n * 2 * nz * BHp;
+            if (t < T - 1) {                 // recurrent path: dGh_{l,t+1} . W_hh_l
+                c.a[0] = q.dh(l, t + 1); c.as[0] = q.dg_sb; c.w[0] = (const float*)q.whh_t[l];
+                c.nseg_mask |= 1;
             }
-            p.ncell = n;
-            if (any_seg || fuse) {
-                const dim3 grid(gpe_cdiv(Bn, RG_BM), gpe_cdiv(H, 64), n * 2 * nz);
-                if (KS == 256) hipLaunchKernelGGL(gpe_rnn_wave_splitk_kernel<256>, grid, dim3(256), lds, s, p);
-                else hipLaunchKernelGGL(gpe_rnn_wave_splitk_kernel<128>, grid, dim3(256), lds, s, p);
-                GPE_CHECK_LAUNCH();
+            if (l < L - 1) {                 // from the layer above: dGx_{l+1,t} . W_ih_{l+1}
+                c.a[1] = q.dx(l + 1, t); c.as[1] = q.dg_sb; c.w[1] = (const float*)q.wih_t[l + 1];
+                c.nseg_mask |= 2;
             }
-            if (fuse) continue;
-            if (G == 4)
-                hipLaunchKernelGGL((gpe_rnn_wave_cell_bwd_kernel<4>), dim3(gpe_cdiv(BH, 256), n), dim3(256), 0, s, p);
-            else
-                hipLaunchKernelGGL((gpe_rnn_wave_cell_bwd_kernel<3>), dim3(gpe_cdiv(BH, 256), n), dim3(256), 0, s, p);
-            GPE_CHECK_LAUNCH();
+            any_seg |= c.nseg_mask;
+            if (l == L - 1 && q.dtop) { c.dh_out = q.dtop + (long)t * q.dt_st; c.dho_stride = q.dt_sb; }
+            if (t == T - 1) {
+                if (q.d_hN) c.dh_extra = q.d_hN + (long)l * BH;
+                c.carry_in = (G == 4 && q.d_cN) ? q.d_cN + (long)l * BH : nullptr;
+            } else
+                c.carry_in = q.carry_at(t + 1, l);
+            c.carry_out = q.carry_at(t, l);
+            c.saved = q.gates(l, t);
+            if (G == 4) {
+                c.c = q.c(l, t + 1);
+                c.c_prev = q.c(l, t);
+            } else {
+                c.h_prev = q.h(l, t); c.hp_stride = q.hs_sb;
+            }
+            c.dgx = q.dx(l, t);
+            c.dgh = q.dh(l, t);
+            c.dg_stride = q.dg_sb;
         }
-    }
-    return GPE_OK;
+        p.ncell = n;
+        if (any_seg || fuse) {
+            // (4 bytes of static __shared__ beside the dynamic image)
+            const int rc = gpe_rnn_for_ks(KS, [&](auto ksc) {
+                return gpe_rnn_launch<gpe_rnn_wave_splitk_kernel<decltype(ksc)::value>, GPE_RNN_LDS_CAP_STATIC>(
+                    dim3(gxr, gyc, n * 2 * nz), 256, lds, q.s, p);
+            });
+            if (rc < 0 || fuse) return rc;
+        }
+        const dim3 grid(gpe_cdiv(BH, 256), n);
+        return (G == 4) ? gpe_rnn_launch<gpe_rnn_wave_cell_bwd_kernel<4>, 0>(grid, 256, 0, q.s, p)
+                        : gpe_rnn_launch<gpe_rnn_wave_cell_bwd_kernel<3>, 0>(grid, 256, 0, q.s, p);
+    });
 }

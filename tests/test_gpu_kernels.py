@@ -673,6 +673,57 @@ def test_recurrences_on_the_fp16_pipe(gpe, kind, Bn, In, Hh, T, L):
         gpe.set_math(prev)
 
 
+@pytest.mark.parametrize('kind,Bn,In,Hh,T,L', [('lstm', 5, 12, 20, 5, 5), ('gru', 5, 12, 20, 5, 5), ('lstm', 17, 12, 20, 7, 6), ('gru', 17, 12, 20, 7, 6),
+                                               ('lstm', 5, 12, 20, 3, 5), ('gru', 5, 12, 20, 3, 5), ('lstm', 20, 24, 260, 3, 2)])
+def test_diagonal_launches_in_several_groups_and_slabs(gpe, kind, Bn, In, Hh, T, L):
+    """Branches of the diagonal launches (csrc/gpe_rnn_wave.hip behind gpe_rnn_walk_diagonals, csrc/gpe_rnn_seq.h) that the shipped
+    decoders never take: a diagonal of more than WV_MAXCELL = 4 cells, split into several launches (5 layers: groups 4 + 1; 6 layers:
+    4 + 2 with a ragged row tile; T < L: diagonals clipped at both ends), and an LSTM wider than 256 units (K slabs 256 + 4).  Both
+    directions, exact and f16x3 arithmetic, against torch's own module in fp64 at the bars of test_recurrences_on_the_fp16_pipe
+    (torch's fp32 against fp64 at these shapes and seeds: 3.2e-7 outputs, 6.1e-7 gradients).  More than four layers, more than 256
+    units and GRUs are off the persistent menu: the workspace query says so, a case cannot move onto another kernel unnoticed."""
+    from gpe_amd import ops, net_blocks
+    from gpe_amd import _lib as Lb
+    torch.manual_seed(Bn + T)
+    rnn = (torch.nn.LSTM if kind == 'lstm' else torch.nn.GRU)(In, Hh, L, batch_first=True)
+    ref = copy.deepcopy(rnn).double()
+    rnn = rnn.cuda()
+    G = 4 if kind == 'lstm' else 3
+    g = torch.Generator().manual_seed(3)
+    x = torch.randn(Bn, In, generator=g)
+    h0 = torch.randn(L, Bn, Hh, generator=g) * 0.3
+    c0 = torch.randn(L, Bn, Hh, generator=g) * 0.3
+    wgt = torch.randn(Bn, T, Hh, generator=g)
+    xr = x.double().requires_grad_()
+    seq = xr[:, None, :].expand(Bn, T, In)
+    out_r, _ = ref(seq, (h0.double(), c0.double())) if kind == 'lstm' else ref(seq, h0.double())
+    (out_r * wgt.double()).sum().backward()
+    params = net_blocks._rnn_params(rnn, L)
+    plan = ops.PackPlan()
+    net_blocks._register_rnn_packs(plan, rnn, L, Hh, G)
+    assert Lb.query('gpe_rnn_seq_fwd_ws', G, L, T, Bn, Hh) == 0               # the diagonal launches run
+    for mode in ('f32', 'f16x3'):
+        prev = gpe.set_math(mode)
+        try:
+            plan.refresh()
+            if mode == 'f16x3':
+                assert ops.planned_planes(rnn.weight_hh_l0, ops.K_GATES_H3)[0] is not None
+            for p in rnn.parameters():
+                p.grad = None
+            xd = x.cuda().requires_grad_()
+            top, _, _ = ops.rnn_stack(xd, h0.cuda(), c0.cuda() if kind == 'lstm' else None, T, L, kind, params)
+            (top * wgt.cuda()).sum().backward()
+            errs = {'out': relerr(top, out_r), 'dx': relerr(xd.grad, xr.grad)}
+            errs.update({n: relerr(p.grad, q.grad) for (n, p), q in zip(rnn.named_parameters(), ref.parameters())})
+            print('diagonal groups %s %s %s: out %.2e, largest gradient error %.2e' %
+                  (kind, (Bn, In, Hh, T, L), mode, errs['out'], max(v for n, v in errs.items() if n != 'out')))
+            assert errs.pop('out') < 2e-5, mode
+            for n, e in errs.items():
+                assert e < 1e-4, (mode, n, e)
+        finally:
+            gpe.set_math(prev)
+
+
 @pytest.mark.parametrize('Bn,In,Hh,T,L,dbg', [(32, 250, 250, 23, 2, 0), (5, 20, 20, 3, 1, 0), (33, 40, 44, 6, 3, 0), (16, 64, 256, 4, 4, 0),
                                               (100, 250, 250, 5, 2, 0), (736, 250, 250, 14, 3, 2048 | 4096), (2000, 30, 36, 4, 2, 2048 | 4096)])
 def test_persistent_lstm_stack_matches_the_diagonal_launches(gpe, Bn, In, Hh, T, L, dbg):
