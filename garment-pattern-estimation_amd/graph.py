@@ -5,6 +5,9 @@ cfg 1, N = 1024, batch 8, k = 5 — is ~200 launches of 3 - 30 us each; the Pyth
     for feats, gt in loader:
         loss = sg.step(feats, gt)          # the first `warmup` calls run eagerly; then one capture; then replays
 
+forward_loss may also return (loss, loss_dict, ...): what follows the loss is kept as `sg.extras`, so the metrics of a replayed step can
+be logged (the stitch classifier: lambda f, g: model.loss(model(f), g)[:2], then sg.extras[0]['stitch_recall']).
+
 What a replay cannot carry in frozen kernel arguments is fed through device memory in front of the graph launch:
   * the reference draws the LSTM start states (and dropout masks) on the CPU generator inside forward() (nn/net_blocks.py:391-392):
     every such tensor has a static device buffer; before each replay the host draws them IN THE SAME ORDER from the same generator
@@ -60,7 +63,10 @@ class HostDrawn:
 
 class StepGraph:
     def __init__(self, forward_loss, optimizer, warmup=2, device=None):
-        """forward_loss(*inputs) -> scalar loss tensor (forward + loss; backward and optimizer.step() are run here).
+        """forward_loss(*inputs) -> scalar loss tensor (forward + loss; backward and optimizer.step() are run here), or a tuple /
+        list whose first element is that loss: what follows it (tensors, or nested dicts / lists / tuples of tensors — a loss dict)
+        is kept, detached, as the tuple `self.extras`: the step's own values during the warm-up, from the capture on the static
+        tensors that every replay overwrites (None for a plain tensor return).  step() returns the loss either way.
         optimizer: optim.FusedAdam.  warmup: eager steps before the capture (>= 1: lazily built state — pack plans, workspaces,
         kernel attributes — must exist before a capture)."""
         if not (hasattr(optimizer, 'step_captured') and hasattr(optimizer, 'advance_captured')):
@@ -76,6 +82,7 @@ class StepGraph:
         self.graph = None
         self.static_in = None
         self.loss = None
+        self.extras = None
         self.guards = []             # (HalfActGuard, amax word) pairs met during the capture
         self.hyper = []              # per arena run: streams.Staged of Adam's two step-dependent floats
         self.runs = None
@@ -115,8 +122,28 @@ class StepGraph:
             if d.data_ptr() != s.data_ptr():
                 d.copy_(s, non_blocking=True)
 
+    def _detached(self, obj):
+        if isinstance(obj, torch.Tensor):
+            return obj.detach()
+        if isinstance(obj, dict):
+            return {k: self._detached(v) for k, v in obj.items()}
+        if isinstance(obj, (list, tuple)):
+            return type(obj)(self._detached(v) for v in obj)
+        return obj
+
+    def _forward(self):
+        """-> the loss of forward_loss; what it returned behind the loss becomes self.extras"""
+        r = self.forward_loss(*self.static_in)
+        if isinstance(r, (tuple, list)):
+            if not r:
+                raise ValueError('StepGraph: forward_loss returned an empty %s (the first element is the loss)' % type(r).__name__)
+            self.extras = self._detached(tuple(r[1:]))
+            return r[0]
+        self.extras = None
+        return r
+
     def _eager(self):
-        loss = self.forward_loss(*self.static_in)
+        loss = self._forward()
         loss.backward()
         self.opt.step()
         return loss
@@ -131,7 +158,7 @@ class StepGraph:
         ops.CAPTURE = self
         try:
             with torch.cuda.graph(self.graph, stream=self.stream):
-                loss = self.forward_loss(*self.static_in)
+                loss = self._forward()
                 loss.backward()
                 self.runs = self.opt.step_captured(self)
         finally:

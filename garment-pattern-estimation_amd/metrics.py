@@ -70,7 +70,12 @@ class PanelLoopLoss:
 
 class ComposedLoss:
     """nn/metrics/composed_loss.py:11-128 (the base used by StitchOnEdge3DPairs): BCE-with-logits on edge pairs.
-    Caller-side torch ops (§8f rank 4 row; the model's MLP is the kernel path)."""
+    On fp32 device predictions (what StitchOnEdge3DPairs produces) the loss and the quality counters are ONE forward launch and the
+    gradient ONE backward launch (ops.PairClassLossFn), with no host read: the call can be captured by
+    graph.StepGraph with `with_quality_eval` on.  The values of the loss dict are then 0-dim fp32 views of the kernel's one output;
+    on an empty denominator `stitch_precision` / `stitch_recall` are a device 0. there, where the torch expressions below (and the
+    reference) give the Python int 0 — as StitchOnEdge3DPairs.evaluate_stitches already does.
+    CPU tensors and other dtypes keep the reference's torch expressions (there is no kernel to route around for them)."""
 
     def __init__(self, data_config, in_config={}):
         self.config = {'loss_components': [], 'quality_components': []}
@@ -85,6 +90,8 @@ class ComposedLoss:
     def __call__(self, preds, ground_truth, names=None, epoch=1000):
         self.device = preds.device
         ground_truth = ground_truth.to(self.device)
+        if preds.is_cuda and preds.dtype == torch.float32:
+            return self._on_device(preds, ground_truth)
         full_loss, loss_dict = 0., {}
         if 'edge_pair_class' in self.l_components:
             pair_loss = self.bce_logits_loss(preds.view(-1), ground_truth.view(-1).float())
@@ -100,6 +107,28 @@ class ComposedLoss:
                     n_pred, n_gt = (cls == 1).sum().float(), (ground_truth == 1).sum().float()
                     loss_dict.update(stitch_precision=hit / n_pred if n_pred else 0,
                                      stitch_recall=hit / n_gt if n_gt else 0)
+        return full_loss, loss_dict, False
+
+    def _on_device(self, preds, ground_truth):
+        """the same keys from ops.pair_class_loss: [loss, accuracy, precision, recall] in one launch"""
+        from . import ops
+        with_loss = 'edge_pair_class' in self.l_components
+        wanted = [k for k in self.q_components if k in ('edge_pair_class', 'edge_pair_stitch_recall')] if self.with_quality_eval else []
+        full_loss, loss_dict = 0., {}
+        if not with_loss and not wanted:
+            return full_loss, loss_dict, False
+        if with_loss:
+            out = ops.pair_class_loss(preds, ground_truth)
+            full_loss = out[0]
+            loss_dict.update(edge_pair_class_loss=full_loss)
+        else:
+            with torch.no_grad():
+                out = ops.pair_class_loss(preds, ground_truth)
+        m = out.detach()
+        if 'edge_pair_class' in wanted:
+            loss_dict.update(edge_pair_class_acc=m[1])
+        if 'edge_pair_stitch_recall' in wanted:
+            loss_dict.update(stitch_precision=m[2], stitch_recall=m[3])
         return full_loss, loss_dict, False
 
     def eval(self):

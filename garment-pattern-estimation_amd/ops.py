@@ -1959,6 +1959,65 @@ class StitchLossFn(torch.autograd.Function):
         return g_tags, g_mask, None, None, None, None, None, None, None
 
 
+PAIR_LOSS_METRICS = ('edge_pair_class_loss', 'edge_pair_class_acc', 'stitch_precision', 'stitch_recall')
+PAIR_LOSS_COUNTS = ('pairs', 'correct', 'true_positives', 'predicted_positives', 'gt_positives')
+PAIR_LOSS_SLOTS = 64          # partial sums of gpe_pair_loss_fwd: part of the result's bits, so a constant and not a device property
+
+
+def _pair_labels(labels, M):
+    """-> (flat labels as the kernel reads them, kind): bool as a uint8 view, uint8 and fp32 as they are, anything else cast once"""
+    if labels.numel() != M:
+        raise ValueError('pair_class_loss: %d labels for %d logits' % (labels.numel(), M))
+    y = labels.reshape(-1)
+    if y.dtype == torch.bool:
+        return y.contiguous().view(torch.uint8), 0
+    if y.dtype == torch.uint8:
+        return y.contiguous(), 0
+    return (y if y.dtype == F32 else y.to(F32)).contiguous(), 1
+
+
+class PairClassLossFn(torch.autograd.Function):
+    """ComposedLoss (nn/metrics/composed_loss.py:83-126) on the logits of a batch of pair rows: BCEWithLogitsLoss and the counters
+    behind edge_pair_class_acc / stitch_precision / stitch_recall in one forward launch, the gradient in one backward launch, no
+    host read.  Returns (out [4] fp32 in the order of PAIR_LOSS_METRICS, counts [5] int32 in the order of PAIR_LOSS_COUNTS); only
+    out[0] carries gradient.  Nothing the backward reads is overwritten: a second backward over the same graph gives the same."""
+
+    @staticmethod
+    def forward(ctx, logits, labels):
+        _dev_check(logits)
+        if not labels.is_cuda:
+            raise RuntimeError('gpe ops need tensors on the MI355X (got %s labels); there is no CPU path' % labels.device)
+        dev = logits.device
+        x = logits.reshape(-1).contiguous()
+        M = x.numel()
+        y, kind = _pair_labels(labels, M)
+        part = torch.empty(PAIR_LOSS_SLOTS * 4, device=dev, dtype=torch.int64)
+        out = torch.empty(4, device=dev, dtype=F32)
+        counts = torch.empty(5, device=dev, dtype=torch.int32)
+        L.call('gpe_pair_loss_fwd', x, y, kind, M, PAIR_LOSS_SLOTS, part, _ticket(dev), out, counts)
+        ctx.rows = (x, y, kind, M)
+        ctx.shape = logits.shape
+        ctx.mark_non_differentiable(counts)
+        return out, counts
+
+    @staticmethod
+    def backward(ctx, g, _g_counts):
+        x, y, kind, M = ctx.rows
+        gx = torch.empty(M, device=x.device, dtype=F32)
+        # g[0] is the upstream gradient of the loss (a device scalar: no host sync); the ratios carry none
+        L.call('gpe_pair_loss_bwd', x, y, kind, M, g.contiguous(), gx)
+        return gx.view(ctx.shape), None
+
+
+def pair_class_loss(logits, labels, return_counts=False):
+    """-> out [4] = (edge_pair_class_loss, edge_pair_class_acc, stitch_precision, stitch_recall) of fp32 device logits against
+    labels of the same number of elements (bool / uint8 / fp32 read in place, other types cast once on the device); a ratio with
+    an empty denominator is 0.  return_counts: -> (out, counts [5] int32 = rows, correct, true positives, predicted positives,
+    ground-truth positives)."""
+    out, counts = PairClassLossFn.apply(logits, labels)
+    return (out, counts) if return_counts else out
+
+
 def stitch_renumber(stitches, nums, P, Lp, perm=None, lead=None, num_edges=None):
     """composed_loss.py:592-620 (`perm`: the panel-order permutation) and :727-755 (`lead` / `num_edges`: the panel-origin
     shift) applied to the ground-truth stitches [B,2,S] int64 -> a new tensor."""

@@ -673,6 +673,27 @@ int gpe_stitch_eval_finalize(const double* loss_slab, long slots, int group, con
                              const int32_t* stitches, const int32_t* num_stitches, int B, int P, int L, double* loss_sum,
                              int32_t* counts, float* metrics, void* stream);
 
+/* ---- the training loss of the same classifier on a batch of sampled pair rows (nn/metrics/composed_loss.py:83-126 ComposedLoss as
+ * StitchOnEdge3DPairs calls it in training) ------------------------------------------------------------------------------------------
+ * Added without a version bump (gpe_abi_version() stays 7): two compute entry points, nothing else changes.
+ * x fp32 [M] dense logits; y the labels, kind 0 = bytes (uint8 / bool), kind 1 = fp32; 0 <= M < 2^31.  All memory is the caller's.
+ * gpe_pair_loss_fwd, one launch of `slots` workgroups (1 .. 256): BCEWithLogitsLoss (mean) with the terms max(x, 0) - x y +
+ *   log1p(exp(-|x|)) in fp32 (for y in {0, 1}: relu(-x if y else x) + log1p(exp(-|x|)), as the evaluating kernels above) summed in
+ *   fp64, and the counters of the class sigmoid(x) > 0.5 (fp32, as the selection above): correct = class == y, positive label =
+ *   y == 1.  Slot s owns the rows [s * ceil(M / slots), (s + 1) * ceil(M / slots)): the result depends on `slots`, not on the device.
+ *   Inside a workgroup the sums run in a fixed order (a thread's rows in order, xor butterfly in a wave, then the waves in order
+ *   through LDS); the workgroup that draws the last ticket adds the slots in slot order.  Nobody waits, no float atomics:
+ *   bit-reproducible.  part: slots * 32 bytes, 8-B aligned, need not be cleared; ticket: one ZEROED uint32, left zero (the word of
+ *   gpe_pack_fold may be shared by calls on one stream).
+ *   out fp32 [4] = edge_pair_class_loss, edge_pair_class_acc, stitch_precision, stitch_recall, the ratios as float32 quotients of
+ *   the counts; a ratio whose denominator is 0 is 0 (composed_loss.py:123-124), M = 0 gives a NaN loss (the mean of nothing).
+ *   counts int32 [5] = rows, correct, true positives, predicted positives, ground-truth positives.
+ * gpe_pair_loss_bwd, one launch: gx[i] = gscale[0] * (sigmoid(x[i]) - y[i]) / M, gscale a DEVICE scalar (the upstream gradient of
+ *   the loss); gx fp32 [M].  M = 0 launches nothing. */
+int gpe_pair_loss_fwd(const float* x, const void* y, int kind, long M, int slots, void* part, uint32_t* ticket, float* out,
+                      int32_t* counts, void* stream);
+int gpe_pair_loss_bwd(const float* x, const void* y, int kind, long M, const float* gscale, float* gx, void* stream);
+
 
 /* ---- optimizer / input side (nn/trainer.py:162-185; nn/data/transforms.py:35-50) ----------------------------------- */
 /* one torch.optim.Adam step (amsgrad off) over a flat arena of n floats (16-B aligned p, g, m, v); `step` counts from 1;
