@@ -1699,12 +1699,7 @@ def _stitch_eval_ws(gt_stitches, gt_num_stitches, B, P, Lm, dev):
     ev = {'mask': torch.zeros(B, E, (E + 31) // 32, device=dev, dtype=torch.int32),
           'counters': torch.zeros(B, 2, device=dev, dtype=torch.int64)}
     # the kernel ignores ids outside 0 .. E - 1 and clamps the counts itself; wider integers are brought into int32's range first
-    st, nums = gt_stitches.detach(), gt_num_stitches.detach()
-    if st.dtype != torch.int32:
-        st = st.to(torch.int64).clamp(-1, E).to(torch.int32)
-    if nums.dtype != torch.int32:
-        nums = nums.to(torch.int64).clamp(0, S).to(torch.int32)
-    st, nums = st.contiguous(), nums.contiguous()
+    st, nums = _int32(gt_stitches, -1, E), _int32(gt_num_stitches, 0, S)
     L.call('gpe_stitch_pairs_labels', st if S else None, nums, B, P, Lm, S, ev['mask'])
     return ev
 
@@ -2016,6 +2011,92 @@ def pair_class_loss(logits, labels, return_counts=False):
     ground-truth positives)."""
     out, counts = PairClassLossFn.apply(logits, labels)
     return (out, counts) if return_counts else out
+
+
+STITCH_SAMPLE_MAX_EDGES, STITCH_SAMPLE_MAX_ROWS = 512, 4096     # P * L and rows per garment of csrc/gpe_stitch_sample.hip
+
+
+def _int_tensor(t, shape, name, dev):
+    if (not torch.is_tensor(t) or tuple(t.shape) != shape or t.is_floating_point() or t.is_complex() or t.dtype == torch.bool
+            or t.device != dev):
+        raise ValueError('%s must be an integer %s tensor on the device of edges3d' % (name, list(shape)))
+
+
+def _int32(t, lo, hi):
+    """an integer tensor as the kernels read it: int32 as it is (they clamp themselves), wider ones brought into range first"""
+    t = t.detach()
+    if t.dtype != torch.int32:
+        t = t.to(torch.int64).clamp(lo, hi).to(torch.int32)
+    return t.contiguous()
+
+
+def stitch_sample_resident(edges3d, num_edges, gt_stitches, gt_num_stitches):
+    """the resident set of stitch_pairs_sample, checked, with wider integer tensors brought into int32 once:
+    edges3d [G, P, L, Fe] fp32, num_edges [G, P], gt_stitches [G, 2, S] (edge ids panel * L + edge), gt_num_stitches [G]"""
+    if not torch.is_tensor(edges3d) or edges3d.dim() != 4:
+        raise ValueError('edges3d must be [G, P, L, Fe] (got %s)' % (tuple(getattr(edges3d, 'shape', ())),))
+    G, P, Lm, Fe = edges3d.shape
+    if G < 1 or P < 1 or Lm < 1 or P * Lm > STITCH_SAMPLE_MAX_EDGES or not 1 <= Fe <= 16:
+        raise ValueError('stitch_pairs_sample handles garments of 1 .. %d edge slots of 1 .. 16 features (got G = %d, P = %d, L = %d, '
+                         'Fe = %d)' % (STITCH_SAMPLE_MAX_EDGES, G, P, Lm, Fe))
+    dev = edges3d.device
+    _int_tensor(num_edges, (G, P), 'num_edges', dev)
+    if not torch.is_tensor(gt_stitches) or gt_stitches.dim() != 3:
+        raise ValueError('gt_stitches must be an integer [G, 2, S] tensor of edge ids panel * L + edge on the device of edges3d')
+    S = gt_stitches.shape[2]
+    _int_tensor(gt_stitches, (G, 2, S), 'gt_stitches', dev)
+    _int_tensor(gt_num_stitches, (G,), 'gt_num_stitches', dev)
+    _dev_check(edges3d)
+    return (edges3d.detach().contiguous(), _int32(num_edges, 0, Lm), _int32(gt_stitches, -1, P * Lm), _int32(gt_num_stitches, 0, S))
+
+
+def stitch_sample_state(seed, draw, device):
+    """{seed, draw} of stitch_pairs_sample as an int64 [2] device tensor (the bit patterns of two unsigned 64-bit numbers)"""
+    signed = [v - (1 << 64) if v >= 1 << 63 else v for v in (int(seed) % (1 << 64), int(draw) % (1 << 64))]
+    return torch.tensor(signed, dtype=torch.int64).to(device)
+
+
+def stitch_pairs_sample(edges3d, num_edges, gt_stitches, gt_num_stitches, index, n_stitched, n_non_stitched, f_shift, f_scale,
+                        state, ticket, shuffle_pairs=True, shuffle_pairs_order=True):
+    """Training pair rows of B garments drawn on the device: what NNSewingPattern.stitches_as_3D_pairs(n_stitched, n_non_stitched,
+    shuffle_pairs, shuffle_pairs_order) (nn/data/pattern_converter.py:321-409) followed by FeatureStandartization gives per garment,
+    in one launch of csrc/gpe_stitch_sample.hip and with no host read (semantics and random numbers: include/gpe_hip.h).
+
+    The resident set as stitch_sample_resident takes it; index integer [B]: the garment of every batch slot; f_shift / f_scale: 2 Fe
+    numbers; state int64 [2] = {seed, draw} on the device (stitch_sample_state), advanced by the launch; ticket: one zeroed int32 of
+    the caller's, left zero.  -> rows fp32 [B, R, 2 Fe] (R = n_stitched + n_non_stitched), labels bool [B, R] (a view of the bytes
+    ops.pair_class_loss reads in place), status int32 [B] (>= 0 rows that gave up, -1 more valid stitches than n_stitched, -2 index
+    outside 0 .. G - 1; such a slot is all zeros)."""
+    edges, ne, gt, nums = stitch_sample_resident(edges3d, num_edges, gt_stitches, gt_num_stitches)
+    G, P, Lm, Fe = edges.shape
+    dev = edges.device
+    n_stitched, n_non_stitched = int(n_stitched), int(n_non_stitched)
+    R = n_stitched + n_non_stitched
+    if n_stitched < 0 or n_non_stitched < 0 or not 1 <= R <= STITCH_SAMPLE_MAX_ROWS:
+        raise ValueError('stitch_pairs_sample draws 1 .. %d rows per garment (got %d + %d)' % (STITCH_SAMPLE_MAX_ROWS, n_stitched, n_non_stitched))
+    if len(f_shift) != 2 * Fe or len(f_scale) != 2 * Fe:
+        raise ValueError('the statistics have %d / %d numbers, the pair rows %d features' % (len(f_shift), len(f_scale), 2 * Fe))
+    if shuffle_pairs and Fe != 8:
+        raise ValueError('shuffle_pairs reverses edges of the layout [start xyz | end xyz | cx cy]: Fe must be 8 (got %d)' % Fe)
+    if not torch.is_tensor(index) or index.dim() != 1 or index.numel() < 1:
+        raise ValueError('index must be an integer [B] tensor, B >= 1')
+    B = index.numel()
+    _int_tensor(index, (B,), 'index', dev)
+    if (not torch.is_tensor(state) or state.dtype != torch.int64 or tuple(state.shape) != (2,) or state.device != dev
+            or not state.is_contiguous()):
+        raise ValueError('state must be a contiguous int64 [2] tensor {seed, draw} on the device of edges3d')
+    if not torch.is_tensor(ticket) or ticket.dtype != torch.int32 or ticket.numel() != 1 or ticket.device != dev:
+        raise ValueError('ticket must be one zeroed int32 on the device of edges3d')
+    import ctypes
+    sh = (ctypes.c_float * (2 * Fe))(*[float(v) for v in f_shift])
+    sc = (ctypes.c_float * (2 * Fe))(*[float(v) for v in f_scale])
+    rows = torch.empty(B, R, 2 * Fe, device=dev, dtype=F32)
+    labels = torch.empty(B, R, device=dev, dtype=torch.uint8)
+    status = torch.empty(B, device=dev, dtype=torch.int32)
+    L.call('gpe_stitch_sample', edges, ne, gt if gt.numel() else None, nums, G, P, Lm, Fe, gt.shape[2], _int32(index, -1, G), B,
+           n_stitched, n_non_stitched, (1 if shuffle_pairs else 0) | (2 if shuffle_pairs_order else 0), sh, sc, state, ticket, rows,
+           labels, status)
+    return rows, labels.view(torch.bool), status
 
 
 def stitch_renumber(stitches, nums, P, Lp, perm=None, lead=None, num_edges=None):

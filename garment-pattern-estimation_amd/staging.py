@@ -3,7 +3,10 @@ memory, after nn/data/transforms.py:35-50 standardised every sample on the CPU).
 
 BatchStager keeps two pinned host buffers and a copy stream per device: batch i+1 is copied while step i computes, the
 compute stream only waits on the copy's event, and the per-axis standardisation `(x - shift) / scale` runs as one kernel
-on the device instead of per sample on the host."""
+on the device instead of per sample on the host.
+
+StitchPairSampler is the input side of the edge-pair classifier's training (GarmentStitchPairsDataset with random_pairs_mode,
+nn/data/datasets.py:985-1132): the data set's 3D edges and stitches stay in HBM and every step's pair rows are drawn there."""
 import torch
 
 from . import ops
@@ -27,3 +30,55 @@ class BatchStager:
         if self.shift is not None:
             out = ops.standardize(out.view(-1, out.shape[-1]), self.shift, self.scale).view(out.shape)
         return out
+
+
+class StitchPairSampler:
+    """Fresh training pairs of the stitch classifier for every step, drawn on the device from a resident data set: what
+    GarmentStitchPairsDataset._get_sample_info (nn/data/datasets.py:1119-1122: NNSewingPattern.stitches_as_3D_pairs, then
+    FeatureStandartization) gives per garment, for a whole batch in one launch (ops.stitch_pairs_sample) and without host work.  The
+    keyword names and defaults are those of the data set's config.
+
+    edges3d [G, P, L, Fe] fp32, num_edges [G, P], gt_stitches [G, 2, S] (edge ids panel * L + edge), gt_num_stitches [G]: the layout
+    StitchOnEdge3DPairs.evaluate_stitches takes; data_stats: {'f_shift', 'f_scale'} of the pair rows.
+
+        sampler = StitchPairSampler(edges3d, num_edges, gt_stitches, gt_num_stitches, stats)
+        sg = graph.StepGraph(lambda idx: (lambda r, y: model.loss(model(r), y)[:2])(*sampler.sample(idx)), opt)
+        loss = sg.step(index)               # index: the garments of the batch, an integer [B] tensor
+
+    The sampler owns the resident tensors, the generator state {seed, draw} (`.state`, int64 [2] on the device: every call of
+    sample() advances draw by one on the device, so a captured call draws new pairs on every replay) and the kernel's ticket word.
+    `.status` is the int32 [B] status of the last call (>= 0 rows that gave up, -1 more stitches than stitched_edge_pairs_num, -2 an
+    index outside the set).  reseed(seed, draw) restarts the sequence: the draws are a function of (seed, draw, batch slot, data)."""
+
+    def __init__(self, edges3d, num_edges, gt_stitches, gt_num_stitches, data_stats, stitched_edge_pairs_num=200,
+                 non_stitched_edge_pairs_num=200, shuffle_pairs=True, shuffle_pairs_order=True, seed=0):
+        self.edges3d, self.num_edges, self.gt_stitches, self.gt_num_stitches = ops.stitch_sample_resident(
+            edges3d, num_edges, gt_stitches, gt_num_stitches)
+        self.f_shift = [float(v) for v in data_stats['f_shift']]
+        self.f_scale = [float(v) for v in data_stats['f_scale']]
+        self.stitched_edge_pairs_num = int(stitched_edge_pairs_num)
+        self.non_stitched_edge_pairs_num = int(non_stitched_edge_pairs_num)
+        self.shuffle_pairs, self.shuffle_pairs_order = bool(shuffle_pairs), bool(shuffle_pairs_order)
+        self.device = self.edges3d.device
+        self.state = ops.stitch_sample_state(seed, 0, self.device)
+        self.ticket = torch.zeros(1, device=self.device, dtype=torch.int32)
+        self.status = None
+
+    @classmethod
+    def from_config(cls, edges3d, num_edges, gt_stitches, gt_num_stitches, dataset_config, seed=0):
+        """dataset_config: the 'dataset' dict of a stitch-model experiment (its 'standardize' statistics are required)"""
+        keys = ('stitched_edge_pairs_num', 'non_stitched_edge_pairs_num', 'shuffle_pairs', 'shuffle_pairs_order')
+        return cls(edges3d, num_edges, gt_stitches, gt_num_stitches, dataset_config['standardize'], seed=seed,
+                   **{k: dataset_config[k] for k in keys if k in dataset_config})
+
+    def reseed(self, seed, draw=0):
+        """the next call draws with (seed, draw); a copy queued on the current stream, no device read"""
+        self.state.copy_(ops.stitch_sample_state(seed, draw, 'cpu'), non_blocking=False)
+
+    def sample(self, index):
+        """index: integer [B] tensor on the device -> (rows fp32 [B, R, 2 Fe], labels bool [B, R])"""
+        rows, labels, self.status = ops.stitch_pairs_sample(
+            self.edges3d, self.num_edges, self.gt_stitches, self.gt_num_stitches, index, self.stitched_edge_pairs_num,
+            self.non_stitched_edge_pairs_num, self.f_shift, self.f_scale, self.state, self.ticket, self.shuffle_pairs,
+            self.shuffle_pairs_order)
+        return rows, labels

@@ -694,6 +694,42 @@ int gpe_pair_loss_fwd(const float* x, const void* y, int kind, long M, int slots
                       int32_t* counts, void* stream);
 int gpe_pair_loss_bwd(const float* x, const void* y, int kind, long M, const float* gscale, float* gx, void* stream);
 
+/* ---- the sampled pair rows of that training, drawn on the device (NNSewingPattern.stitches_as_3D_pairs,
+ * nn/data/pattern_converter.py:321-409, then FeatureStandartization) ----------------------------------------------------------------
+ * Added without a version bump (gpe_abi_version() stays 7): one compute entry point, nothing else changes.  All memory is the
+ * caller's; the library keeps no state.
+ * The resident set: edges3d fp32 [G][P][L][Fe] (Fe <= 16, E = P * L <= 512), num_edges int32 [G][P] (clamped to 0 .. L; 0 = panel
+ * absent), gt_stitches int32 [G][2][S] of edge ids panel * L + edge and gt_num_stitches int32 [G] (clamped to 0 .. S), the operands
+ * of gpe_stitch_pairs_labels; gt_stitches may be NULL when S == 0.  index int32 [B]: the garment of every batch slot, 1 <= B <= 2^24.
+ * One launch of B workgroups writes, with R = n_stitched + n_non_stitched (1 .. 4096; both >= 0):
+ *   rows   fp32 [B][R][2 Fe] = ([e_a | e_b] - shift) / scale, fp32 subtract then divide as gpe_stitch_pairs_rows (shift_host /
+ *          scale_host: HOST arrays of 2 Fe floats); 16-byte stores when Fe is even and rows is 16-byte aligned;
+ *   labels uint8 [B][R], 0 / 1 (kind 0 of gpe_pair_loss_fwd);
+ *   status int32 [B]: >= 0 the rows that gave up; -1 more valid stitches than n_stitched; -2 index[b] outside 0 .. G - 1 (all rows
+ *          and labels of such a slot are zero).
+ * Per slot, before the shuffle: rows [0, S_v) are the valid stitches in order (both ids in 0 .. E - 1 and present), label 1; rows
+ * [S_v, n_stitched) copy a uniformly chosen row below S_v as stored, label 1; the remaining rows (all R when S_v == 0) are
+ * non-stitched, label 0: an attempt draws a present panel, an edge of it, and the same again, and is rejected when both sides are
+ * the same edge or the pair is a valid stitch in either orientation; after 64 rejected attempts the row gives up (zeros, label 0).
+ * flags bit 0 (shuffle_pairs; needs Fe == 8, the [start xyz | end xyz | cx cy] layout): every present edge is reversed with
+ * probability 1/2 once per slot (endpoints swapped, cx' = cx ? 1 - cx : 0, cy' = -cy) and every valid stitch row has its halves
+ * swapped with probability 1/2.  flags bit 1 (shuffle_pairs_order): row r moves to the rank of (key_r, r), key_r a 32-bit draw.
+ * Random numbers: Philox4x32-10, key = (seed lo, seed hi), counter = (item | kind << 28, attempt | b << 8, draw lo, draw hi); an
+ * integer in [0, n) is (uint64(word) * n) >> 32.
+ *   kind 0 flip: item = edge id, bit 31 of word 0          kind 1 stitch swap: item = rank of the valid stitch, bit 31 of word 0
+ *   kind 2 duplicate choice: item = row, word 0            kind 3 non-stitched attempt: item = index among the non-stitched rows,
+ *   kind 4 order key: item = pre-shuffle row, word 0         attempt = 0 .. 63, words 0 - 3 = panel, edge, panel, edge
+ * The result is a function of (seed, draw, b, inputs) only.  state uint64 [2] = {seed, draw} in DEVICE memory, 8-byte aligned: the
+ * launch stores draw + 1 after every workgroup has read it (the last-arriver ticket of gpe_pack_fold, nobody waits), so a captured
+ * launch draws anew on every replay.  ticket: one ZEROED uint32 of its own, left zero.
+ * -EINVAL before any launch: a NULL pointer, Fe > 16, Fe != 8 with bit 0 set, unknown flag bits, P * L > 512, R outside 1 .. 4096,
+ * B < 1. */
+int gpe_stitch_sample(const float* edges3d, const int32_t* num_edges, const int32_t* gt_stitches, const int32_t* gt_num_stitches,
+                      int G, int P, int L, int Fe, int S, const int32_t* index, int B, int n_stitched, int n_non_stitched,
+                      int flags /* bit 0 shuffle_pairs, bit 1 shuffle_pairs_order */, const float* shift_host, const float* scale_host,
+                      uint64_t* state /* device: {seed, draw} */, uint32_t* ticket, float* rows, uint8_t* labels, int32_t* status,
+                      void* stream);
+
 
 /* ---- optimizer / input side (nn/trainer.py:162-185; nn/data/transforms.py:35-50) ----------------------------------- */
 /* one torch.optim.Adam step (amsgrad off) over a flat arena of n floats (16-B aligned p, g, m, v); `step` counts from 1;
