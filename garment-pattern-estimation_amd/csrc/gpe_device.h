@@ -1,6 +1,6 @@
 // Device-side primitives shared by the gfx950 kernels of libgpe_hip.so (not part of the C ABI): vector typedefs, the split of an
-// fp32 pair into 16-bit terms, the inter-workgroup hand-off, the recurrent state scale and the LSTM cell.  A new persistent kernel
-// starts from these instead of growing its own copies.
+// fp32 pair into 16-bit terms, the samplers' counter-based random numbers, the inter-workgroup hand-off, the recurrent state scale
+// and the LSTM cell.  A new persistent kernel starts from these instead of growing its own copies.
 #pragma once
 #include "gpe_common.h"
 #include <math.h>
@@ -48,6 +48,29 @@ __device__ __forceinline__ void gpe_split2_bf16(float a, float b, unsigned& h, u
 // normal (smaller ones keep an absolute error < 1.5e-8).  Callers of the f16x3 recurrences guarantee |h0| < 16.
 #define GPE_STATE_SA 4096.f
 #define GPE_STATE_INV_SA (1.f / 4096.f)
+
+// ---- counter-based random numbers --------------------------------------------------------------------------------------------
+// Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11)
+__device__ __forceinline__ gpe_u32x4 gpe_philox4x32(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1)
+{
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+        const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    return gpe_u32x4{c0, c1, c2, c3};
+}
+// the samplers' block of one decision: key = the seed, counter = (item | kind << 28, attempt | b << 8, draw lo, draw hi), b the batch
+// slot (b8 = b << 8).  The kinds in use: 0 .. 4 gpe_stitch_sample.hip, 8 and 9 gpe_mesh_sample.hip
+struct gpe_rng {
+    unsigned k0, k1, d0, d1, b8;
+    __device__ __forceinline__ gpe_u32x4 operator()(int kind, unsigned item, unsigned attempt = 0) const
+    {
+        return gpe_philox4x32(item | ((unsigned)kind << 28), attempt | b8, d0, d1, k0, k1);
+    }
+};
 
 // ---- inter-workgroup hand-off inside one launch ---------------------------------------------------------------------------
 // Recipe R1 (MI355X_MICROARCH.md "Workgroup dispatch, XCD placement & inter-workgroup visibility"; cdna_hip_programming.md

@@ -38,27 +38,6 @@ struct SsParams {
     float shift[2 * SS_MAXF], scale[2 * SS_MAXF];
 };
 
-// Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11)
-__device__ __forceinline__ gpe_u32x4 ss_philox(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1)
-{
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    return gpe_u32x4{c0, c1, c2, c3};
-}
-
-struct SsRng {
-    unsigned k0, k1, d0, d1, b8;
-    __device__ __forceinline__ gpe_u32x4 operator()(int kind, unsigned item, unsigned attempt = 0) const
-    {
-        return ss_philox(item | ((unsigned)kind << 28), attempt | b8, d0, d1, k0, k1);
-    }
-};
-
 // an integer in [0, n)
 __device__ __forceinline__ unsigned ss_below(unsigned word, unsigned n) { return __umulhi(word, n); }
 
@@ -128,8 +107,8 @@ __global__ __launch_bounds__(SS_TPB) void gpe_stitch_sample_kernel(SsParams p)
     const int g = p.index[b];
     if (g < 0 || g >= p.G) { ss_zero_slot(p, b, -2); return; }            // block-uniform
     __syncthreads();
-    const SsRng rng = {(unsigned)s_state[0], (unsigned)(s_state[0] >> 32), (unsigned)s_state[1], (unsigned)(s_state[1] >> 32),
-                       (unsigned)b << 8};
+    const gpe_rng rng = {(unsigned)s_state[0], (unsigned)(s_state[0] >> 32), (unsigned)s_state[1], (unsigned)(s_state[1] >> 32),
+                         (unsigned)b << 8};
     const bool flips = p.flags & 1, shuffle = p.flags & 2;
 
     // ---- present panels ----

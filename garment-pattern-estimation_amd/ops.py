@@ -2099,6 +2099,142 @@ def stitch_pairs_sample(edges3d, num_edges, gt_stitches, gt_num_stitches, index,
     return rows, labels.view(torch.bool), status
 
 
+class MeshResident:
+    """the meshes of a data set as mesh_points_sample reads them (built by mesh_resident), ragged over G garments: verts4 fp32
+    [sum V, 4] = {x, y, z, the bits of the int32 class id}, faces int32 [sum F, 3] (indices local to the garment), vert_off / face_off
+    int32 [G + 1], face_cdf int32 [sum F] holding the uint32 thresholds of the face choice; has_unlabelled: some vertex carries -1"""
+
+    def __init__(self, verts4, faces, vert_off, face_off, face_cdf, has_unlabelled):
+        self.verts4, self.faces, self.vert_off, self.face_off, self.face_cdf = verts4, faces, vert_off, face_off, face_cdf
+        self.G = vert_off.numel() - 1
+        self.has_unlabelled = bool(has_unlabelled)
+        self.device = verts4.device
+
+    @property
+    def verts(self):
+        return self.verts4[:, :3]
+
+    @property
+    def vert_label(self):
+        return self.verts4.view(torch.int32)[:, 3]
+
+
+def mesh_face_thresholds(verts, faces):
+    """the integer thresholds of the area-proportional face choice of one garment (verts fp32 [V, 3], faces int [F, 3]) -> uint32
+    [F]: T[f] = floor(2^31 C_f / C_total), C the sequential float64 cumulative sum of area = 0.5 |(B - A) x (C - A)| from the fp32
+    vertices, and T[f] = 2^31 exactly from the last face of positive area onwards; all zeros for a garment without such a face"""
+    v = np.asarray(verts, dtype=np.float32).astype(np.float64)
+    f = np.asarray(faces, dtype=np.int64)
+    a, e1, e2 = v[f[:, 0]], v[f[:, 1]] - v[f[:, 0]], v[f[:, 2]] - v[f[:, 0]]
+    cx = e1[:, 1] * e2[:, 2] - e1[:, 2] * e2[:, 1]
+    cy = e1[:, 2] * e2[:, 0] - e1[:, 0] * e2[:, 2]
+    cz = e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0]
+    area = 0.5 * np.sqrt(cx * cx + cy * cy + cz * cz)
+    cum = np.cumsum(area)
+    out = np.zeros(len(f), dtype=np.uint32)
+    positive = np.nonzero(area > 0)[0]
+    if len(positive):
+        out[:] = np.floor(2.0 ** 31 * (cum / cum[-1])).astype(np.uint32)
+        out[positive[-1]:] = 1 << 31
+    return out
+
+
+def mesh_resident(meshes, device='cuda'):
+    """Packs the meshes of a data set for mesh_points_sample (setup, not per step): meshes is a list of (verts [V, 3] float, faces
+    [F, 3] integer with indices into that garment's vertices, labels [V] integer: the class id of every vertex as the caller's
+    PanelClasses map gives it, -1 for a `stitch` / `None` vertex) as arrays or CPU tensors -> MeshResident on `device`.  A face index
+    outside 0 .. V - 1, a label below -1 and a coordinate that is not finite are ValueErrors."""
+    if isinstance(meshes, MeshResident):
+        return meshes
+    meshes = list(meshes)
+    if not meshes:
+        raise ValueError('mesh_resident needs at least one mesh')
+    v4, fs, cdf, voff, foff = [], [], [], [0], [0]
+    for g, mesh in enumerate(meshes):
+        if len(mesh) != 3:
+            raise ValueError('mesh %d must be (verts, faces, labels)' % g)
+        as_np = lambda t: t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+        verts, faces, labels = [as_np(t) for t in mesh]
+        if verts.ndim != 2 or verts.shape[1] != 3 or verts.dtype.kind != 'f':
+            raise ValueError('mesh %d: verts must be a float [V, 3] array (got %s %s)' % (g, verts.dtype, verts.shape))
+        V = verts.shape[0]
+        if faces.ndim != 2 or faces.shape[1] != 3 or faces.dtype.kind not in 'iu':
+            raise ValueError('mesh %d: faces must be an integer [F, 3] array (got %s %s)' % (g, faces.dtype, faces.shape))
+        if labels.shape != (V,) or labels.dtype.kind not in 'iu':
+            raise ValueError('mesh %d: labels must be an integer [%d] array (got %s %s)' % (g, V, labels.dtype, labels.shape))
+        verts = verts.astype(np.float32)
+        if not np.isfinite(verts).all():
+            raise ValueError('mesh %d has a vertex coordinate that is not finite' % g)
+        faces, labels = faces.astype(np.int64), labels.astype(np.int64)
+        if faces.size and (faces.min() < 0 or faces.max() >= V):
+            raise ValueError('mesh %d: a face names vertex %d, outside 0 .. %d' % (g, faces.min() if faces.min() < 0 else faces.max(), V - 1))
+        if labels.size and (labels.min() < -1 or labels.max() >= 1 << 31):
+            raise ValueError('mesh %d: labels are class ids >= 0, or -1 for a stitch / None vertex' % g)
+        packed = np.empty((V, 4), dtype=np.float32)
+        packed[:, :3] = verts
+        packed.view(np.int32)[:, 3] = labels
+        v4.append(packed)
+        fs.append(faces.astype(np.int32))
+        cdf.append(mesh_face_thresholds(verts, faces))
+        voff.append(voff[-1] + V)
+        foff.append(foff[-1] + faces.shape[0])
+    if voff[-1] >= 1 << 31 or foff[-1] >= 1 << 31:
+        raise ValueError('the resident set holds %d vertices and %d faces: the offsets are int32' % (voff[-1], foff[-1]))
+    v4 = np.concatenate(v4)
+    to = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
+    return MeshResident(to(v4), to(np.concatenate(fs).reshape(-1, 3)), to(np.asarray(voff, dtype=np.int32)),
+                        to(np.asarray(foff, dtype=np.int32)), to(np.concatenate(cdf).view(np.int32)),
+                        bool((v4[:, 3].view(np.int32) < 0).any()))
+
+
+MESH_SAMPLE_MAX_POINTS, MESH_SAMPLE_MAX_BATCH = (1 << 28) - 1, (1 << 24) - 1    # the counter fields of csrc/gpe_mesh_sample.hip
+
+
+def mesh_points_sample(resident, index, mesh_samples, state, ticket, point_noise_w=0.0, f_shift=None, f_scale=None):
+    """The input point clouds of B garments and their segmentation labels drawn on the device: what
+    Garment3DPatternFullDataset._get_sample_info (nn/data/datasets.py: _sample_points, _point_classes_from_mesh,
+    FeatureStandartization) gives per garment, in at most two launches of csrc/gpe_mesh_sample.hip and with no host read (semantics
+    and random numbers: include/gpe_hip.h).
+
+    resident: mesh_resident(...) on the device; index integer [B]: the garment of every batch slot; f_shift / f_scale: 3 numbers
+    each or both None; state int64 [2] = {seed, draw} on the device (stitch_sample_state), advanced by the call; ticket: one zeroed
+    int32 of the caller's, left zero.  -> features fp32 [B, N, 3] (N = mesh_samples), segmentation int64 [B, N], status int32 [B]
+    (>= 0 points that fell back to label 0 for want of a labelled point in their cloud, -1 a garment without a face of positive
+    area, -2 index outside 0 .. G - 1; such a slot is all zeros)."""
+    if not isinstance(resident, MeshResident):
+        raise ValueError('resident must come from ops.mesh_resident (got %s)' % type(resident).__name__)
+    dev = resident.device
+    N = int(mesh_samples)
+    if not 1 <= N <= MESH_SAMPLE_MAX_POINTS:
+        raise ValueError('mesh_points_sample draws 1 .. 2^28 - 1 points per garment (got %d)' % N)
+    if (f_shift is None) != (f_scale is None) or (f_shift is not None and (len(f_shift) != 3 or len(f_scale) != 3)):
+        raise ValueError('the statistics are 3 shifts and 3 scales, or neither')
+    if not torch.is_tensor(index) or index.dim() != 1 or not 1 <= index.numel() <= MESH_SAMPLE_MAX_BATCH:
+        raise ValueError('index must be an integer [B] tensor, 1 <= B < 2^24')
+    B = index.numel()
+    if B * ((N + 511) // 512) >= 1 << 31:
+        raise ValueError('B * ceil(N / 512) must stay below 2^31 (got B = %d, N = %d)' % (B, N))
+    if index.is_floating_point() or index.is_complex() or index.dtype == torch.bool or index.device != dev:
+        raise ValueError('index must be an integer [%d] tensor on the device of the resident set' % B)
+    if (not torch.is_tensor(state) or state.dtype != torch.int64 or tuple(state.shape) != (2,) or state.device != dev
+            or not state.is_contiguous()):
+        raise ValueError('state must be a contiguous int64 [2] tensor {seed, draw} on the device of the resident set')
+    if not torch.is_tensor(ticket) or ticket.dtype != torch.int32 or ticket.numel() != 1 or ticket.device != dev:
+        raise ValueError('ticket must be one zeroed int32 on the device of the resident set')
+    _dev_check(resident.verts4)
+    import ctypes
+    sh = (ctypes.c_float * 3)(*[float(v) for v in f_shift]) if f_shift is not None else None
+    sc = (ctypes.c_float * 3)(*[float(v) for v in f_scale]) if f_scale is not None else None
+    features = torch.empty(B, N, 3, device=dev, dtype=F32)
+    seg = torch.empty(B, N, device=dev, dtype=torch.int64)
+    status = torch.empty(B, device=dev, dtype=torch.int32)
+    ws = torch.empty(B, N, 4, device=dev, dtype=F32) if resident.has_unlabelled else None
+    L.call('gpe_mesh_points_sample', resident.verts4, resident.faces, resident.vert_off, resident.face_off, resident.face_cdf,
+           resident.G, _int32(index, -1, resident.G), B, N, float(point_noise_w), sh, sc, 1 if resident.has_unlabelled else 0, ws,
+           state, ticket, features, seg, status)
+    return features, seg, status
+
+
 def stitch_renumber(stitches, nums, P, Lp, perm=None, lead=None, num_edges=None):
     """composed_loss.py:592-620 (`perm`: the panel-order permutation) and :727-755 (`lead` / `num_edges`: the panel-origin
     shift) applied to the ground-truth stitches [B,2,S] int64 -> a new tensor."""

@@ -731,6 +731,44 @@ int gpe_stitch_sample(const float* edges3d, const int32_t* num_edges, const int3
                       void* stream);
 
 
+/* ---- the encoder's input point clouds drawn on the device from resident meshes (Garment3DPatternFullDataset._get_sample_info,
+ * nn/data/datasets.py: igl.random_points_on_mesh, the barycentric -> world loop, the Gaussian noise, igl.snap_points twice,
+ * FeatureStandartization) -----------------------------------------------------------------------------------------------------------
+ * Added without a version bump (gpe_abi_version() stays 7): one compute entry point, nothing else changes.  All memory is the
+ * caller's; the library keeps no state.
+ * The resident set, ragged over G garments: verts4 fp32 [sum V][4] = {x, y, z, the bits of the int32 class id; -1 = a stitch / None
+ * vertex}, 16-byte aligned; faces int32 [sum F][3], indices local to the garment (the caller has checked them against 0 .. V - 1;
+ * the kernel holds them inside the garment all the same); vert_off, face_off int32 [G + 1]; face_cdf uint32 [sum F]: per garment
+ * T[f] = floor(2^31 C_f / C_total), C the inclusive cumulative sum of the face areas, and T[f] = 2^31 exactly from the last face of
+ * positive area onwards (a garment without one has no 2^31 at its end).  index int32 [B]: the garment of every batch slot.
+ * Slot b, point n < N (one launch of B * ceil(N / 512) workgroups; a second one of the same grid when relabel != 0):
+ *   face         w = word 0 >> 1 of kind 8: the first face f of the garment with T[f] > w (binary search)
+ *   barycentric  iu = word 1 >> 8, iv = word 2 >> 8; iu + iv > 2^24 reflects both (i <- 2^24 - i); b1 = iu 2^-24, b2 = iv 2^-24,
+ *                b0 = (2^24 - iu - iv) 2^-24; p = (b0 A + b1 B) + b2 C per axis, every product and sum rounded on its own
+ *   noise        point_noise_w != 0 only, kind 9: Box-Muller with u1 = ((word >> 8) + 1) 2^-24, u2 = (word >> 8) 2^-24,
+ *                r = sqrtf(-2 logf(u1)): words 0, 1 -> x += w (r cospif(2 u2)), y += w (r sinpif(2 u2)); words 2, 3 -> z += w (r
+ *                cospif(2 u2)); the multiply and the add each rounded
+ *   label        that of the vertex nearest to the noisy p: the lexicographic minimum of (d, vertex), d = (dx dx + dy dy) + dz dz,
+ *                every operation rounded on its own
+ *   re-label     relabel != 0 (needed exactly when the resident set has a -1 vertex; without it a -1 stays in the output): a point
+ *                labelled -1 takes the label of the nearest point of its own cloud whose label is >= 0, the lower point winning a
+ *                tie; no such point: label 0, counted in status[b].  ws: fp32 [B][N][4] of the caller's, 16-byte aligned (may be
+ *                NULL when relabel == 0)
+ * features fp32 [B][N][3] = (p - shift) / scale, the fp32 subtract-then-divide of gpe_standardize (shift_host / scale_host: HOST
+ * arrays of 3 floats; both NULL: p itself); segmentation int64 [B][N]; status int32 [B]: >= 0 the points that fell back to label 0;
+ * -1 a garment without a face of positive area; -2 index[b] outside 0 .. G - 1 (features and segmentation of such a slot are zero).
+ * Random numbers: the Philox4x32-10 blocks of gpe_stitch_sample, key = (seed lo, seed hi), counter = (n | kind << 28, b << 8, draw
+ * lo, draw hi), kinds 8 and 9.  The result is a function of (seed, draw, b, inputs) only.  state uint64 [2] = {seed, draw} in DEVICE
+ * memory, 8-byte aligned: the first launch stores draw + 1 after every workgroup has read it (last-arriver ticket, nobody waits);
+ * ticket: one ZEROED uint32 of its own, left zero.
+ * -EINVAL before any launch: a NULL pointer (ws with relabel; one of shift_host / scale_host alone), a misaligned verts4 / ws /
+ * state, G < 1, B < 1, B >= 2^24, N < 1, N >= 2^28, B * ceil(N / 512) >= 2^31. */
+int gpe_mesh_points_sample(const float* verts4, const int32_t* faces, const int32_t* vert_off, const int32_t* face_off,
+                           const uint32_t* face_cdf, int G, const int32_t* index, int B, int N, float point_noise_w,
+                           const float* shift_host, const float* scale_host, int relabel, float* ws,
+                           uint64_t* state /* device: {seed, draw} */, uint32_t* ticket, float* features, int64_t* segmentation,
+                           int32_t* status, void* stream);
+
 /* ---- optimizer / input side (nn/trainer.py:162-185; nn/data/transforms.py:35-50) ----------------------------------- */
 /* one torch.optim.Adam step (amsgrad off) over a flat arena of n floats (16-B aligned p, g, m, v); `step` counts from 1;
  * the gradient is read as g*gscale; zero_grad != 0 clears g afterwards.  The OneCycleLR value is passed in as lr. */
