@@ -20,12 +20,11 @@
 //             512-byte per-wave LDS strip.  No per-lane sorted arrays, no scratch memory.
 // Ordering rule: ascending (dist, candidate index); an equal-distance candidate never displaces an earlier one.
 #include "gpe_device.h"
+#include "gpe_knn_plan.h"
 #include <math.h>
 #include <stdint.h>
 #include <stdlib.h>
 
-#define KNN_TQ 64
-#define KNN_TC 64
 #define KNN_CCH 32          // channels staged per step
 #define KNN_LD 36           // row stride (floats) of the point-major operand tiles
 #define KNN_LDD 68          // row stride of a wave's 16 x 64 distance strip
@@ -350,88 +349,34 @@ __global__ __launch_bounds__(256) void gpe_knn_merge_kernel(const unsigned long 
     }
 }
 
-template <int VEC>
-static void knn_launch(long nblocks, size_t lds, hipStream_t s, int probe, const float* x, int N, int C, int ldx, int k,
-                       int32_t* idx, int32_t* idx_glob, int B, int tiles, int pin, int nsplit, unsigned long long* part)
-{
-    if (probe)
-        hipLaunchKernelGGL((gpe_knn_kernel<VEC, 1>), dim3((unsigned)nblocks), dim3(256), lds, s, x, N, C, ldx, k, idx, idx_glob, B,
-                           tiles, pin, probe, nsplit, part);
-    else if (VEC == 1 && C <= 4)
-        hipLaunchKernelGGL((gpe_knn_kernel<1, 0, true>), dim3((unsigned)nblocks), dim3(256), lds, s, x, N, C, ldx, k, idx, idx_glob,
-                           B, tiles, pin, 0, nsplit, part);
-    else
-        hipLaunchKernelGGL((gpe_knn_kernel<VEC, 0>), dim3((unsigned)nblocks), dim3(256), lds, s, x, N, C, ldx, k, idx, idx_glob, B,
-                           tiles, pin, 0, nsplit, part);
-}
-
-// C == 3 on a spatially sorted cloud with tile pruning (gpe_knn3.hip): 1 launched, 0 not on its menu
-int gpe_knn3_try(const float* x, int B, int N, int ldx, int k, int32_t* idx, int32_t* idx_glob, int32_t* order_out, void* ws, long ws_bytes,
-                 hipStream_t s);
-
-// all-exact path: every distance by the defined chain (C < 16, k > 48, or GPE_KNN_EXACT=1)
+// the order of a search that has none of its own (every path but the sorted cloud's): the identity is a valid, locality-free answer
 __global__ void gpe_knn_identity_order_kernel(int* __restrict__ order, long nq, int N)
 {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < nq) order[i] = (int)(i % N);
 }
 
-static int knn_exact(const float* x, int B, int N, int C, int ldx, int k, int32_t* idx, int32_t* idx_glob, void* ws,
-                     long ws_bytes, void* stream, int32_t* order_out = nullptr)
+// all-pairs kernel: the staging width, the probe and the C <= 4 instance as template arguments; the merge of the pieces
+int gpe_knn_launch_allpairs(const GpeKnnCall& c, const GpeKnnPlan& p)
 {
-    if (C == 3) {
-        const int rc = gpe_knn3_try(x, B, N, ldx, k, idx, idx_glob, order_out, ws, ws_bytes, (hipStream_t)stream);
-        if (rc != 0) return rc < 0 ? rc : GPE_OK;
-    }
-    if (order_out) {                                   // no curve order on this path: the identity is a valid (locality-free) answer
-        hipLaunchKernelGGL(gpe_knn_identity_order_kernel, dim3((unsigned)gpe_cdiv((long)B * N, 256)), dim3(256), 0, (hipStream_t)stream,
-                           order_out, (long)B * N, N);
-        GPE_CHECK_LAUNCH();
-    }
     const size_t lds = ((size_t)2 * KNN_TQ * KNN_LD + 4 * 16 * KNN_LDD) * sizeof(float) + 4 * 64 * sizeof(unsigned long long);
-    static const int probe = gpe_dbg_env("GPE_KNN_PROBE", 0);
-    const int tiles = gpe_cdiv(N, KNN_TQ);
-    static const int dbg_pin = gpe_dbg_env("GPE_KNN_PIN", -1);      // measurement overrides
-    static const int dbg_vec = gpe_dbg_env("GPE_KNN_VEC", 0);
-    const int pin = (dbg_pin >= 0) ? (dbg_pin && B >= GPE_NXCD) : (gpe_pin_clouds(B) ? 1 : 0);
-    // Candidate split.  With every workgroup resident (4 per CU) an XCD works on 128 items at a time = 128 / (tiles * nsplit)
-    // clouds, whose tables (N x ldx floats each) are streamed once per item: they must fit the XCD's 4 MiB L2 together or the
-    // cyclic stream evicts every line before its next use (measured at cfg 2, layer 2: 4 x 1.25 MB -> 396-475 MB fetched for
-    // 39 MB; 3 tables -> 36 MB).  nsplit pieces per query tile put nsplit x fewer clouds in flight.
-    static const int dbg_split = gpe_dbg_env("GPE_KNN_SPLIT", 0);
-    int nsplit = 1;
-    if (pin) {
-        const double table = (double)N * ldx * sizeof(float), l2_budget = 3.2 * 1024 * 1024;
-        const int resident = 4 * gpe_num_cus() / GPE_NXCD;                 // items in flight per XCD
-        for (;;) {
-            const double clouds = (double)resident / ((double)tiles * nsplit);
-            if (table * (clouds > 1.0 ? clouds : 1.0) <= l2_budget) break;  // the tables in flight fit
-            if (clouds <= 1.0) break;                                      // one table alone is too big: no split helps
-            if (nsplit >= 4 || 2 * nsplit * k > 64 || 2 * nsplit > tiles) break;
-            nsplit *= 2;
-        }
-    }
-    if (dbg_split > 0 && dbg_split * k <= 64 && dbg_split <= tiles) nsplit = dbg_split;
-    unsigned long long* part = nullptr;
-    if (nsplit > 1) {
-        const size_t need = (size_t)B * N * nsplit * k * sizeof(unsigned long long);
-        part = (ws && !(((uintptr_t)ws) & 15) && (size_t)ws_bytes >= need) ? (unsigned long long*)ws : nullptr;
-        if (!part) nsplit = 1;                                             // no workspace: one piece, more HBM traffic
-    }
-    const long nblocks = (pin ? (long)GPE_NXCD * gpe_cdiv(B, GPE_NXCD) * tiles : (long)B * tiles) * nsplit;
-    if (nblocks >= (1L << 31)) return GPE_EINVAL;
-    // widest staging copy the rows allow (a C < 32 chunk is staged ((C + 3) & ~3) floats wide, so it must divide too)
-    const uintptr_t xa = (uintptr_t)x;
-    int vec = (C % 4 == 0 && ldx % 4 == 0 && xa % 16 == 0) ? 4 : (C % 2 == 0 && ldx % 2 == 0 && xa % 8 == 0) ? 2 : 1;
-    if (dbg_vec > 0 && dbg_vec < vec) vec = dbg_vec;
-    hipStream_t s = (hipStream_t)stream;
-    if (vec == 4) knn_launch<4>(nblocks, lds, s, probe, x, N, C, ldx, k, idx, idx_glob, B, tiles, pin, nsplit, part);
-    else if (vec == 2) knn_launch<2>(nblocks, lds, s, probe, x, N, C, ldx, k, idx, idx_glob, B, tiles, pin, nsplit, part);
-    else knn_launch<1>(nblocks, lds, s, probe, x, N, C, ldx, k, idx, idx_glob, B, tiles, pin, nsplit, part);
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)p.nblocks), dim3(256), lds, c.stream, c.x, c.N, c.C, c.ldx, c.k, c.idx, c.idx_glob, c.B,
+                           p.tiles, p.pin, p.probe, p.nsplit, p.part);
+    };
+    auto staged = [&](auto vec) {                    // vec: the staging width as a type (the instances are emitted in the order named here)
+        constexpr int VEC = decltype(vec)::value;
+        if (p.probe) go(gpe_knn_kernel<VEC, 1>);
+        else if (p.smallc) go(gpe_knn_kernel<1, 0, true>);
+        else go(gpe_knn_kernel<VEC, 0>);
+    };
+    if (p.vec == 4) staged(std::integral_constant<int, 4>{});
+    else if (p.vec == 2) staged(std::integral_constant<int, 2>{});
+    else staged(std::integral_constant<int, 1>{});
     GPE_CHECK_LAUNCH();
-    if (nsplit > 1) {
-        hipLaunchKernelGGL(gpe_knn_merge_kernel, dim3((unsigned)gpe_cdiv((long)B * N * nsplit * k, 256)), dim3(256), 0, s, part,
-                           (long)B * N, N, k, nsplit, idx, idx_glob);
+    if (p.nsplit > 1) {
+        hipLaunchKernelGGL(gpe_knn_merge_kernel, dim3((unsigned)gpe_cdiv((long)c.B * c.N * p.nsplit * c.k, 256)), dim3(256), 0, c.stream,
+                           p.part, (long)c.B * c.N, c.N, c.k, p.nsplit, c.idx, c.idx_glob);
         GPE_CHECK_LAUNCH();
     }
     return GPE_OK;
@@ -444,7 +389,8 @@ static int knn_exact(const float* x, int B, int N, int C, int ldx, int k, int32_
 // MFMA multiply-add (v_mfma_f32_16x16x4_f32: exact products, fp32 accumulation) — half the issue slots.  d~ is NOT the
 // defined distance (oracle/knn_ref.c: the fmaf chain of (q_c - p_c)^2), so it only FILTERS:
 //   1. gpe_knn_norms_kernel    |x|^2 per point, max per cloud;
-//   2. gpe_knn_mfma_kernel     per query the K2 = min(64, N, 2k + 8) best candidates by (d~, index), streamed like above;
+//   2. gpe_knn_mfma_kernel     per query the K2 best candidates by (d~, index), streamed like above (gpe_knn_k2:
+//                              K2 = max(min(2k, 32), k + 8), at most 64 and at most N);
 //                              a candidate is inserted only below min(K2-th best, k-th best + 2E): nothing further out can
 //                              be needed (the k-th best only decreases);
 //   3. gpe_knn_rerank_kernel   one wave per query: every candidate of the exact top-k has d~ <= T = d~[k-th] + 2E (proof
@@ -459,7 +405,6 @@ static int knn_exact(const float* x, int B, int N, int C, int ldx, int k, int32_
 // so E = (5 C + 8) u (|q|^2 + max_p |p|^2) suffices; the kernels use (6 C + 16) u and 1 % on top.
 // Why T suffices: let p be in the exact top-k with d~(p) > kth~ + 2E.  The k list entries r with d~(r) <= kth~ have
 // d_chain(r) <= d~(r) + E <= kth~ + E < d~(p) - E <= d_chain(p): k candidates strictly closer than p — contradiction.
-#define KNN_MF_MINC 16
 #ifndef KNN_MF_CCH
 #define KNN_MF_CCH 32          // channels staged per step by the matrix-pipe filter
 #endif
@@ -798,7 +743,6 @@ __global__ __launch_bounds__(256, KNN_MF_WGS) void gpe_knn_mfma_kernel(const flo
 #define KNN_H3_CCH 64                     // channels per staged step: two 32-k MFMA blocks
 #define KNN_H3_PITCH 160                  // bytes per plane row in LDS: 8 data chunks of 16 B + 2 pad (chunk count = 2 mod 4:
                                           // the ds_read_b128 that walks down a column is conflict-free, gpe_edgegemm_split_kernel.h)
-#define KNN_H3_MAXC 256
 
 // planes of the feature table: pl[row] = [h plane: CP halves | l plane: CP halves] (CP = C rounded up to 32, zero pad),
 // isc[row] = 2^-sh.  Wave = KNN_NORM_ROWS rows; pass 1 the rows' largest magnitudes, pass 2 the split (the rows come from L2).
@@ -1091,13 +1035,6 @@ __global__ __launch_bounds__(256, 2) void gpe_knn_h3_kernel(const _Float16* __re
     }
 }
 
-// The threshold-scan filter (round 6) lives in gpe_knn_ft.hip; what gpe_knn needs of it:
-#define KNN_FT_NBMAX 5                    // 32-channel blocks: C <= 160
-#define KNN_FT_MAXK 32
-int gpe_knn_ft_launch(int wide, long nblocks, hipStream_t s, const _Float16* planes, const float* iscale, int N, int CP, int k,
-                      const float* norms, const int* cmax, float ce, int B, int qtiles, int pin, unsigned long long* part,
-                      const int* rot, int probe);
-
 // exact chain distance of one (query row, candidate row) pair per lane — oracle/knn_ref.c's arithmetic
 // (16-byte loads when both rows allow it: a lane walks its own row, so the loads of the next channels must be in flight under
 // the dependent fma chain — one dword load per step was a full L2 round trip per channel, 12 us per re-evaluated candidate)
@@ -1346,143 +1283,72 @@ __global__ __launch_bounds__(256) void gpe_knn_rerank2_kernel(const float* __res
     }
 }
 
-// what the filter path keeps per query: the K2 best candidates by the matrix-pipe distance
-static int knn_k2(int k, int N)
+// ---- launchers (gpe_knn_plan.h): what the plan names, nothing decided here ---------------------------------------------------
+// identity order, norms + per-cloud maxima, planes: whichever of them the plan asks for, in this order
+int gpe_knn_launch_prologue(const GpeKnnCall& c, const GpeKnnPlan& p)
 {
-    int K2 = (2 * k < 32) ? 2 * k : 32;
-    if (K2 < k + 8) K2 = k + 8;
-    if (K2 > 64) K2 = 64;
-    if (K2 > N) K2 = N;
-    return K2;
-}
-// bytes of the caller's workspace: partial k-lists of up to 4 candidate pieces (all-exact path: k entries each; filter path:
-// K2 entries), the squared norms and the per-cloud maxima
-extern "C" long gpe_knn_ws_bytes(int B, int N, int C, int k)
-{
-    if (B < 0 || N <= 0 || C <= 0 || k <= 0 || k > 64) return GPE_EINVAL;
-    const size_t nq = (size_t)B * N;
-    const size_t lists = nq * 64 * sizeof(unsigned long long) + 256;      // nsplit * K2 <= 64 and nsplit * k <= 64 by construction
-    const size_t norm_bytes = (nq * sizeof(float) + 255) & ~(size_t)255;
-    // fp16-pipe filter (16 <= C <= 256): two fp16 planes of the table (C rounded up to 32) + one inverse scale per row
-    const size_t CP = ((size_t)C + 31) & ~(size_t)31;
-    const size_t plane_bytes = (C >= KNN_MF_MINC && C <= KNN_H3_MAXC) ? ((nq * 2 * CP * sizeof(_Float16) + 255) & ~(size_t)255) + norm_bytes : 0;
-    return (long)(lists + norm_bytes + ((size_t)B * sizeof(int) + 255 & ~(size_t)255) + plane_bytes + 256);
-}
-
-extern "C" int gpe_knn(const float* x, int B, int N, int C, int ldx, int k, int32_t* idx, int32_t* idx_glob, const int32_t* order_in,
-                       int32_t* order_out, void* ws, long ws_bytes, void* stream)
-{
-    if (!x || !idx || B < 0 || N <= 0 || C <= 0 || ldx < C || k <= 0 || k > 64 || k > N || (long)B * N * k >= (1L << 31)) return GPE_EINVAL;
-    if (B == 0) return GPE_OK;
-    static const int force_exact = gpe_dbg_env("GPE_KNN_EXACT", 0);
-    if (C < KNN_MF_MINC || k > 48 || force_exact) return knn_exact(x, B, N, C, ldx, k, idx, idx_glob, ws, ws_bytes, stream, order_out);
-    if (order_out) {                                   // (only the xyz search produces an order; a filter-path caller gets the identity)
-        hipLaunchKernelGGL(gpe_knn_identity_order_kernel, dim3((unsigned)gpe_cdiv((long)B * N, 256)), dim3(256), 0, (hipStream_t)stream,
-                           order_out, (long)B * N, N);
+    const long nq = (long)c.B * c.N;
+    if (p.identity) {
+        hipLaunchKernelGGL(gpe_knn_identity_order_kernel, dim3((unsigned)gpe_cdiv(nq, 256)), dim3(256), 0, c.stream, c.order_out, nq, c.N);
         GPE_CHECK_LAUNCH();
     }
-    // ---- matrix-pipe filter + exact recheck ----
-    const int K2 = knn_k2(k, N);
-    const int tiles = gpe_cdiv(N, KNN_TQ);
-    static const int dbg_pin = gpe_dbg_env("GPE_KNN_PIN", -1);
-    static const int dbg_vec = gpe_dbg_env("GPE_KNN_VEC", 0);
-    static const int dbg_split = gpe_dbg_env("GPE_KNN_SPLIT", 0);
-    static const int mprobe = gpe_dbg_env("GPE_KNN_PROBE", 0);   // timing aid (wrong results)
-    const int pin = (dbg_pin >= 0) ? (dbg_pin && B >= GPE_NXCD) : (gpe_pin_clouds(B) ? 1 : 0);
-    // No candidate split here.  knn_exact cuts the candidate range in pieces so that the tables in flight fit an L2; for this
-    // path every piece would pay its own first-tile ranking and its own list build-up (selection work x 1.7 at two pieces) plus
-    // a 64-key merge per query in the rerank: measured at cfg 2, layer 2: 0.99 ms with two pieces, 0.86 ms with one (the extra
-    // ~360 MB of L2 misses per launch are 0.5 TB/s of HBM traffic under a kernel that is not memory-bound).  GPE_KNN_SPLIT
-    // still forces pieces (the merge code stays tested).
-    int nsplit = 1;
-    if (dbg_split > 0 && dbg_split * K2 <= 64 && dbg_split <= tiles) nsplit = dbg_split;
-    const size_t nq = (size_t)B * N;
-    const size_t part_bytes = (nq * 64 * sizeof(unsigned long long) + 255) & ~(size_t)255;   // nsplit * K2 <= 64; the threshold scan: 64 keys per query
-    const size_t norm_bytes = (nq * sizeof(float) + 255) & ~(size_t)255;
-    const size_t cmax_bytes = ((size_t)B * sizeof(int) + 255) & ~(size_t)255;
-    // the fp16-pipe filter (default for C <= 256; GPE_KNN_F32FILTER=1 keeps the exact-product filter for A/B measurements)
-    static const int f32filter = gpe_dbg_env("GPE_KNN_F32FILTER", 0);
-    const int CP = (C + 31) & ~31;
-    const size_t pl_bytes = (nq * 2 * (size_t)CP * sizeof(_Float16) + 255) & ~(size_t)255;
-    bool h3 = !f32filter && C <= KNN_H3_MAXC;
-    size_t need = part_bytes + norm_bytes + cmax_bytes + 256;
-    if (h3 && (!ws || (size_t)ws_bytes < need + pl_bytes + norm_bytes)) h3 = false;      // workspace sized by an older query
-    if (h3) need += pl_bytes + norm_bytes;
-    char* scratch = (ws && !(((uintptr_t)ws) & 15) && (size_t)ws_bytes >= need) ? (char*)ws : nullptr;
-    if (!scratch) return knn_exact(x, B, N, C, ldx, k, idx, idx_glob, nullptr, 0, stream);   // no workspace: the all-exact kernel
-    unsigned long long* part = (unsigned long long*)scratch;
-    float* norms = (float*)(scratch + part_bytes);
-    int* cmax = (int*)(scratch + part_bytes + norm_bytes);
-    _Float16* planes = (_Float16*)(scratch + part_bytes + norm_bytes + cmax_bytes);
-    float* iscale = (float*)(scratch + part_bytes + norm_bytes + cmax_bytes + pl_bytes);
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(gpe_knn_norms_kernel, dim3((unsigned)gpe_cdiv((long)nq, 4 * KNN_NORM_ROWS)), dim3(256), 0, s, x, (long)nq, N, C, ldx, norms,
-                       cmax);
+    if (p.norms) {
+        hipLaunchKernelGGL(gpe_knn_norms_kernel, dim3((unsigned)gpe_cdiv(nq, 4 * KNN_NORM_ROWS)), dim3(256), 0, c.stream, c.x, nq, c.N, c.C,
+                           c.ldx, p.norms, p.cmax);
+        GPE_CHECK_LAUNCH();
+        hipLaunchKernelGGL(gpe_knn_cmax_kernel, dim3(c.B), dim3(256), 0, c.stream, p.norms, c.N, p.cmax);
+        GPE_CHECK_LAUNCH();
+    }
+    if (p.planes) {
+        hipLaunchKernelGGL(gpe_knn_planes_kernel, dim3((unsigned)gpe_cdiv(nq, 4 * KNN_NORM_ROWS)), dim3(256), 0, c.stream, c.x, nq, c.C,
+                           c.ldx, p.CP, p.planes, p.iscale, p.order, c.N);
+        GPE_CHECK_LAUNCH();
+    }
+    return GPE_OK;
+}
+
+// fp16-pipe ordered-list filter: the instance that holds NB 32-channel blocks
+int gpe_knn_launch_lists(const GpeKnnCall& c, const GpeKnnPlan& p)
+{
+    const size_t lds = (size_t)2 * 2 * KNN_TC * KNN_H3_PITCH + (size_t)4 * 16 * KNN_LDD * sizeof(float) +
+                       4 * 64 * sizeof(unsigned long long) + 4 * KNN_TC * sizeof(float);
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)p.nblocks), dim3(256), lds, c.stream, p.planes, p.iscale, c.N, p.CP, c.k, p.K2, p.norms,
+                           p.cmax, p.ce, c.B, p.tiles, p.pin, p.nsplit, p.part, p.probe, p.order);
+    };
+    if (p.NB <= 2) go(gpe_knn_h3_kernel<2>);
+    else if (p.NB <= 5) go(gpe_knn_h3_kernel<5>);
+    else go(gpe_knn_h3_kernel<8>);
     GPE_CHECK_LAUNCH();
-    hipLaunchKernelGGL(gpe_knn_cmax_kernel, dim3(B), dim3(256), 0, s, norms, N, cmax);
-    GPE_CHECK_LAUNCH();
-    // (6C + 16) * 2^-24, see the bound above; + 16 * 2^-24 for the two-term fp16 products of the fp16-pipe filter
-    const float ce = (6.f * C + (h3 ? 32.f : 16.f)) * 5.9604645e-8f;
+    return GPE_OK;
+}
+
+// fp32 matrix-pipe filter
+int gpe_knn_launch_f32filter(const GpeKnnCall& c, const GpeKnnPlan& p)
+{
     const size_t lds = ((size_t)2 * KNN_TQ * KNN_MF_LD + 4 * 16 * KNN_LDD) * sizeof(float) + 4 * 64 * sizeof(unsigned long long) +
                        KNN_TC * sizeof(float);
-    const long nblocks = (pin ? (long)GPE_NXCD * gpe_cdiv(B, GPE_NXCD) * tiles : (long)B * tiles) * nsplit;
-    if (nblocks >= (1L << 31)) return GPE_EINVAL;
-    const uintptr_t xa = (uintptr_t)x;
-    // widest staging copy: a vector may run into the row's pad columns (their contents are replaced by zeros), so only the
-    // pitch and the base address have to allow it
-    int vec = (ldx % 4 == 0 && xa % 16 == 0 && ((C + 3) & ~3) <= ldx) ? 4
-            : (ldx % 2 == 0 && xa % 8 == 0 && ((C + 1) & ~1) <= ldx) ? 2 : 1;
-    if (dbg_vec > 0 && dbg_vec < vec) vec = dbg_vec;
-    if (h3) {
-        hipLaunchKernelGGL(gpe_knn_planes_kernel, dim3((unsigned)gpe_cdiv((long)nq, 4 * KNN_NORM_ROWS)), dim3(256), 0, s, x, (long)nq, C,
-                           ldx, CP, planes, iscale, gpe_dbg_env("GPE_KNN_NOORDER", 0) ? nullptr : order_in, N);
-        GPE_CHECK_LAUNCH();
-        const size_t lds3 = (size_t)2 * 2 * KNN_TC * KNN_H3_PITCH + (size_t)4 * 16 * KNN_LDD * sizeof(float) +
-                            4 * 64 * sizeof(unsigned long long) + 4 * KNN_TC * sizeof(float);
-        const int NB = CP >> 5;
-        static const int no_order = gpe_dbg_env("GPE_KNN_NOORDER", 0);     // A/B: ignore the caller's order (planes built above with it: keep both off)
-        const int32_t* rot = no_order ? nullptr : order_in;
-        static const int ft_on = gpe_dbg_env("GPE_KNN_FT", 1);              // A/B: 0 = the ordered-list filter (gpe_knn_h3_kernel)
-        if (ft_on && NB <= KNN_FT_NBMAX && k <= KNN_FT_MAXK && nsplit == 1) {
-            // the threshold scan: 128 queries per workgroup when that still fills the chip, 64 otherwise
-            const int cus = gpe_num_cus();
-            const bool wide = ft_on == 8 || (ft_on != 4 && (long)B * gpe_cdiv(N, 128) >= cus);
-            const int tq = wide ? 128 : 64;
-            const int qtiles = gpe_cdiv(N, tq);
-            const long nb = pin ? (long)GPE_NXCD * gpe_cdiv(B, GPE_NXCD) * qtiles : (long)B * qtiles;
-            const int rc = gpe_knn_ft_launch(wide ? 1 : 0, nb, s, planes, iscale, N, CP, k, norms, cmax, ce, B, qtiles, pin, part, rot, mprobe);
-            if (rc != GPE_OK) return rc;
-            static const int rr2 = gpe_dbg_env("GPE_KNN_RR2", 1);                // A/B: 0 = one query per wave
-            if (rr2)
-                hipLaunchKernelGGL(gpe_knn_rerank2_kernel, dim3((unsigned)gpe_cdiv((long)nq, 8)), dim3(256), 0, s, x, (long)nq, N, C, ldx, k,
-                                   part, norms, cmax, ce, idx, idx_glob);
-            else
-                hipLaunchKernelGGL(gpe_knn_rerank_kernel, dim3((unsigned)gpe_cdiv((long)nq, 4)), dim3(256), 0, s, x, (long)nq, N, C, ldx, k, K2,
-                                   nsplit, part, norms, cmax, ce, idx, idx_glob, 1);
-            GPE_CHECK_LAUNCH();
-            return GPE_OK;
-        }
-        if (NB <= 2)
-            hipLaunchKernelGGL((gpe_knn_h3_kernel<2>), dim3((unsigned)nblocks), dim3(256), lds3, s, planes, iscale, N, CP, k, K2, norms,
-                               cmax, ce, B, tiles, pin, nsplit, part, mprobe, rot);
-        else if (NB <= 5)
-            hipLaunchKernelGGL((gpe_knn_h3_kernel<5>), dim3((unsigned)nblocks), dim3(256), lds3, s, planes, iscale, N, CP, k, K2, norms,
-                               cmax, ce, B, tiles, pin, nsplit, part, mprobe, rot);
-        else
-            hipLaunchKernelGGL((gpe_knn_h3_kernel<8>), dim3((unsigned)nblocks), dim3(256), lds3, s, planes, iscale, N, CP, k, K2, norms,
-                               cmax, ce, B, tiles, pin, nsplit, part, mprobe, rot);
-    } else if (vec == 4)
-        hipLaunchKernelGGL((gpe_knn_mfma_kernel<4>), dim3((unsigned)nblocks), dim3(256), lds, s, x, N, C, ldx, k, K2, norms, cmax, ce,
-                           B, tiles, pin, nsplit, part, mprobe);
-    else if (vec == 2)
-        hipLaunchKernelGGL((gpe_knn_mfma_kernel<2>), dim3((unsigned)nblocks), dim3(256), lds, s, x, N, C, ldx, k, K2, norms, cmax, ce,
-                           B, tiles, pin, nsplit, part, mprobe);
-    else
-        hipLaunchKernelGGL((gpe_knn_mfma_kernel<1>), dim3((unsigned)nblocks), dim3(256), lds, s, x, N, C, ldx, k, K2, norms, cmax, ce,
-                           B, tiles, pin, nsplit, part, mprobe);
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)p.nblocks), dim3(256), lds, c.stream, c.x, c.N, c.C, c.ldx, c.k, p.K2, p.norms, p.cmax,
+                           p.ce, c.B, p.tiles, p.pin, p.nsplit, p.part, p.probe);
+    };
+    if (p.vec == 4) go(gpe_knn_mfma_kernel<4>);
+    else if (p.vec == 2) go(gpe_knn_mfma_kernel<2>);
+    else go(gpe_knn_mfma_kernel<1>);
     GPE_CHECK_LAUNCH();
-    hipLaunchKernelGGL(gpe_knn_rerank_kernel, dim3((unsigned)gpe_cdiv((long)nq, 4)), dim3(256), 0, s, x, (long)nq, N, C, ldx, k, K2,
-                       nsplit, part, norms, cmax, ce, idx, idx_glob, 0);
+    return GPE_OK;
+}
+
+// the exact recheck of a filter's lists
+int gpe_knn_launch_recheck(const GpeKnnCall& c, const GpeKnnPlan& p)
+{
+    const long nq = (long)c.B * c.N;
+    if (p.rerank2)
+        hipLaunchKernelGGL(gpe_knn_rerank2_kernel, dim3((unsigned)gpe_cdiv(nq, 8)), dim3(256), 0, c.stream, c.x, nq, c.N, c.C, c.ldx, c.k,
+                           p.part, p.norms, p.cmax, p.ce, c.idx, c.idx_glob);
+    else
+        hipLaunchKernelGGL(gpe_knn_rerank_kernel, dim3((unsigned)gpe_cdiv(nq, 4)), dim3(256), 0, c.stream, c.x, nq, c.N, c.C, c.ldx, c.k,
+                           p.K2, p.nsplit, p.part, p.norms, p.cmax, p.ce, c.idx, c.idx_glob, p.unsorted);
     GPE_CHECK_LAUNCH();
     return GPE_OK;
 }

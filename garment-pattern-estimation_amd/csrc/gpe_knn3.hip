@@ -22,13 +22,11 @@
 // Selection: the first tile (the wave's own: it holds the queries themselves) is sorted by a 64-lane bitonic network per query;
 // later tiles are merged survivor by survivor exactly like gpe_knn.hip's knn_select, with 64-bit keys.
 // Measured / motivation: DESIGN.md 5.9 and 9(c) — the all-pairs kernel spends 322 us on 0.4 GFLOP at cfg 2 and 5.7 ms at N = 8192.
-#include "gpe_common.h"
+#include "gpe_knn_plan.h"
 #include <math.h>
 #include <stdint.h>
 #include <stdlib.h>
 
-#define K3_MAXN 8192
-#define K3_MINN 128
 #define K3_CELLS 4096
 
 __device__ __forceinline__ float k3_sub_sv(float a_uniform, float b)
@@ -222,9 +220,6 @@ __device__ __forceinline__ void k3_select(unsigned long long key, int lane, int 
 // neighbours prunes more tiles.  Measured at cfg 2 (32 x 2048 Gaussian points, k = 16; whole gpe_knn family, ms per step, the
 // layer-2 search is 0.80 of it): 16 queries 1.058, 8: 1.007, 4: 0.938, 2: 0.931, 1: 0.921 (all-pairs kernel: 1.10); at N = 8192 x 64
 // clouds 14.6 - 14.9 for all of them (all-pairs: 18.1).
-#ifndef K3_QW
-#define K3_QW 4
-#endif
 static_assert(64 % K3_QW == 0 && K3_QW <= 16, "a wave's queries must lie in ONE tile of 64 sorted points (the pruning argument), in registers");
 __global__ __launch_bounds__(256) void gpe_knn3_query_kernel(const float4* __restrict__ xs, const float* __restrict__ tb, int N, int k,
                                                              int tiles, int wgs, int32_t* __restrict__ idx, int32_t* __restrict__ idx_glob)
@@ -342,25 +337,15 @@ __global__ __launch_bounds__(256) void gpe_knn3_query_kernel(const float4* __res
     }
 }
 
-// 1 = launched, 0 = not on this path's menu (the caller runs the all-pairs kernel), < 0 error.  ws: >= B*N*16 + B*tiles*32 bytes.
-// GPE_KNN_SORTED=0 keeps the all-pairs kernel (A/B measurements, tests of the old path).
-int gpe_knn3_try(const float* x, int B, int N, int ldx, int k, int32_t* idx, int32_t* idx_glob, int32_t* order_out, void* ws,
-                 long ws_bytes, hipStream_t s)
+// sort, then query (gpe_knn_plan.h: xs / tb alias the workspace's list region)
+int gpe_knn_launch_sorted(const GpeKnnCall& c, const GpeKnnPlan& p)
 {
-    static const int off = gpe_dbg_env("GPE_KNN_SORTED", 1) == 0;
-    if (off || N < K3_MINN || N > K3_MAXN || k > 64 || k > N) return 0;
-    const int tiles = gpe_cdiv(N, 64);
-    const size_t xs_bytes = (size_t)B * N * sizeof(float4), tb_bytes = (size_t)B * tiles * 8 * sizeof(float);
-    if (!ws || (((uintptr_t)ws) & 15) || (size_t)ws_bytes < xs_bytes + tb_bytes) return 0;
-    if ((long)B * gpe_cdiv(N, 4 * K3_QW) >= (1L << 31)) return 0;
-    float4* xs = reinterpret_cast<float4*>(ws);
-    float* tb = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + xs_bytes);
-    const size_t lds = (size_t)N * sizeof(float4) + K3_CELLS * sizeof(unsigned) + 96 * sizeof(float) + 16 * sizeof(unsigned);
+    const size_t lds = (size_t)c.N * sizeof(float4) + K3_CELLS * sizeof(unsigned) + 96 * sizeof(float) + 16 * sizeof(unsigned);
     GPE_ENSURE_MAX_LDS(gpe_knn3_sort_kernel);
-    hipLaunchKernelGGL(gpe_knn3_sort_kernel, dim3(B), dim3(1024), lds, s, x, N, ldx, order_out, xs, tb, tiles);
+    hipLaunchKernelGGL(gpe_knn3_sort_kernel, dim3(c.B), dim3(1024), lds, c.stream, c.x, c.N, c.ldx, c.order_out, p.xs, p.tb, p.tiles);
     GPE_CHECK_LAUNCH();
-    const int wgs = gpe_cdiv(N, 4 * K3_QW);
-    hipLaunchKernelGGL(gpe_knn3_query_kernel, dim3((unsigned)((long)B * wgs)), dim3(256), 0, s, xs, tb, N, k, tiles, wgs, idx, idx_glob);
+    hipLaunchKernelGGL(gpe_knn3_query_kernel, dim3((unsigned)p.nblocks), dim3(256), 0, c.stream, p.xs, p.tb, c.N, c.k, p.tiles, p.qtiles,
+                       c.idx, c.idx_glob);
     GPE_CHECK_LAUNCH();
-    return 1;
+    return GPE_OK;
 }

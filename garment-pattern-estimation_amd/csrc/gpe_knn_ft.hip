@@ -1,11 +1,10 @@
-// The layer-2 (wide-feature) graph search's filter as a threshold scan — the kernel behind gpe_knn (gpe_knn.hip) for 16 <= C <= 160,
+// The layer-2 (wide-feature) graph search's filter as a threshold scan — the kernel behind gpe_knn (step 2b of gpe_knn_plan.h) for 16 <= C <= 160,
 // k <= 32 (replaces torch_cluster.knn as reached from /root/reference/nn/net_blocks.py:127-135,174 through PyG's DynamicEdgeConv).
 // Its own translation unit: gpe_knn.hip is compiled under the max-ILP scheduling strategy its ordered-list kernels were tuned with.
 #include "gpe_device.h"
+#include "gpe_knn_plan.h"
 #include <math.h>
 #include <stdint.h>
-
-#define KNN_TC 64
 
 // =====================================================================================================================
 // Round 6: the fp16-pipe filter as a THRESHOLD scan (gpe_knn_ft_kernel; C <= 160, k <= 32).  What gpe_knn_h3_kernel spends its time
@@ -26,10 +25,7 @@
 // within 2E of its k-th: duplicates, lattices) is marked and re-done exactly by the recheck, like an overflowing h3 list.
 // Output: 64 keys per query, unordered, ~0 = empty; 64 valid keys = "redo exactly".
 // =====================================================================================================================
-#define KNN_FT_CAP 64
 #define KNN_FT_LSTR 65                    // keys per list row in LDS (odd: the 16 queries of a wave spread over the banks)
-#define KNN_FT_NBMAX 5                    // 32-channel blocks: C <= 160
-#define KNN_FT_MAXK 32
 
 __device__ __forceinline__ void knn_ft_append(int* cnt, unsigned long long* list, unsigned long long key)
 {
@@ -329,22 +325,22 @@ __global__ __launch_bounds__(64 * NW) void gpe_knn_ft_kernel(const _Float16* __r
 }
 
 
-// host side (called by gpe_knn): wide = 128 queries per workgroup (8 waves), else 64 (4 waves)
-int gpe_knn_ft_launch(int wide, long nblocks, hipStream_t s, const _Float16* planes, const float* iscale, int N, int CP, int k,
-                      const float* norms, const int* cmax, float ce, int B, int qtiles, int pin, unsigned long long* part,
-                      const int* rot, int probe)
+// wide = 128 queries per workgroup (8 waves), else 64 (4 waves)
+int gpe_knn_launch_scan(const GpeKnnCall& c, const GpeKnnPlan& p)
 {
-    const int tq = wide ? 128 : 64;
-    const size_t ldsf = (size_t)2 * KNN_TC * (4 * CP + 32) + (size_t)(tq / 16) * 16 * KNN_FT_LSTR * sizeof(unsigned long long) +
-                        (size_t)tq * sizeof(int) + 4 * KNN_TC * sizeof(float);
-    if (wide) {
+    const int tq = p.wide ? 128 : 64;
+    const size_t lds = (size_t)2 * KNN_TC * (4 * p.CP + 32) + (size_t)(tq / 16) * 16 * KNN_FT_LSTR * sizeof(unsigned long long) +
+                       (size_t)tq * sizeof(int) + 4 * KNN_TC * sizeof(float);
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)p.nblocks), dim3(4 * tq), lds, c.stream, p.planes, p.iscale, c.N, p.CP, c.k, p.norms,
+                           p.cmax, p.ce, c.B, p.qtiles, p.pin, p.part, p.order, p.probe);
+    };
+    if (p.wide) {
         GPE_ENSURE_MAX_LDS(gpe_knn_ft_kernel<8>);
-        hipLaunchKernelGGL((gpe_knn_ft_kernel<8>), dim3((unsigned)nblocks), dim3(512), ldsf, s, planes, iscale, N, CP, k, norms, cmax, ce, B,
-                           qtiles, pin, part, rot, probe);
+        go(gpe_knn_ft_kernel<8>);
     } else {
         GPE_ENSURE_MAX_LDS(gpe_knn_ft_kernel<4>);
-        hipLaunchKernelGGL((gpe_knn_ft_kernel<4>), dim3((unsigned)nblocks), dim3(256), ldsf, s, planes, iscale, N, CP, k, norms, cmax, ce, B,
-                           qtiles, pin, part, rot, probe);
+        go(gpe_knn_ft_kernel<4>);
     }
     GPE_CHECK_LAUNCH();
     return GPE_OK;

@@ -114,11 +114,19 @@ def test_knn_xyz_sorted_cloud_bit_exact(gpe, B, N, k, data):
     assert torch.equal(got, ref)
 
 
-# C -> fp16-pipe filter instance (blocks of 32 channels, NB = ceil(C / 32)): <2> 32, 33, 64; <5> 100 (two full steps), 150;
-# <8> 200 (seven blocks: an odd last step), 256; C = 300 > 256 keeps the exact-product fp32 filter
+# Which path a case reaches (csrc/gpe_knn_plan.h; NB = ceil(C / 32) blocks of 32 channels):
+#   threshold scan (C <= 160, k <= 32): C = 32, 33, 64, 100, 150 with k = 5 .. 20; k = 32 is its last k
+#   ordered-list kernel <2> / <5> (C <= 160, 32 < k <= 48): C = 32 (one block of queries, a ragged tile), 33 (two blocks);
+#     C = 150 with k = 48 (the largest filtered k, K2 = 56), C = 160 (NB = 5)
+#   ordered-list kernel <8> (160 < C <= 256): C = 161 (NB = 6, the first width the scan refuses), 200 (seven blocks: an odd last
+#     step), 256 with k <= 48
+#   fp32 matrix-pipe filter: C = 300 > 256
+#   all-pairs kernel on wide rows (k > 48): (2, 513, 256, 256, 64), and k = 49, the first k that leaves the filters
 MF_CASES = [(2, 300, 150, 152, 16), (1, 1000, 64, 64, 20), (3, 97, 32, 32, 5), (2, 513, 256, 256, 64), (1, 2048, 33, 36, 16),
             (2, 200, 100, 100, 10), (1, 700, 200, 200, 16), (1, 300, 300, 300, 8),
-            (2, 130, 150, 152, 9)]
+            (2, 130, 150, 152, 9),
+            (3, 97, 32, 32, 33), (2, 130, 33, 36, 40), (1, 200, 150, 152, 48), (1, 200, 160, 160, 33), (1, 200, 161, 164, 16),
+            (2, 130, 64, 64, 32), (1, 200, 40, 40, 49)]
 
 
 @pytest.mark.parametrize('B,N,C,ld,k', MF_CASES)
@@ -172,12 +180,15 @@ print('alt path ok')
 
 @pytest.mark.parametrize('env', [{'GPE_KNN_EXACT': '1'}, {'GPE_KNN_SPLIT': '2'}, {'GPE_KNN_EXACT': '1', 'GPE_KNN_SPLIT': '2'},
                                  {'GPE_KNN_F32FILTER': '1'}, {'GPE_KNN_F32FILTER': '1', 'GPE_KNN_SPLIT': '2'},
-                                 {'GPE_KNN_SORTED': '0'}, {'GPE_KNN_SORTED': '0', 'GPE_KNN_SPLIT': '2'}])
+                                 {'GPE_KNN_SORTED': '0'}, {'GPE_KNN_SORTED': '0', 'GPE_KNN_SPLIT': '2'},
+                                 {'GPE_KNN_FT': '0'}, {'GPE_KNN_FT': '4'}, {'GPE_KNN_FT': '8'}, {'GPE_KNN_RR2': '0'}])
 def test_knn_alternative_paths(gpe, env, tmp_path):
     """The paths the dispatcher no longer takes by default on wide rows — the all-exact kernel's float4 / float2 staging
     (C >= 16 goes through a matrix-pipe filter), the exact-product fp32 filter (16 <= C <= 256 now runs the fp16-pipe filter)
     and the candidate split with its list merge (forced: B >= 8 pins clouds to XCDs, which is what enables pieces), the all-pairs
-    kernel on an xyz cloud (GPE_KNN_SORTED=0: 128 .. 8192 points otherwise take the sorted-cloud kernel) — stay bit-exact.  The overrides are read once per process, hence the subprocess."""
+    kernel on an xyz cloud (GPE_KNN_SORTED=0: 128 .. 8192 points otherwise take the sorted-cloud kernel), the ordered-list kernels
+    on the shapes the threshold scan serves (GPE_KNN_FT=0), the scan's 64- and 128-query workgroups whatever the batch (4 / 8)
+    and its one-query recheck (GPE_KNN_RR2=0) — stay bit-exact.  The overrides are read once per process, hence the subprocess."""
     import os, subprocess, sys
     script = tmp_path / 'w.py'
     script.write_text(_KNN_ALT_WORKER % os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -216,7 +227,9 @@ def test_knn_candidate_split_full_size(gpe):
 
 
 @pytest.mark.parametrize('B,N,C,k,kind', [(32, 2048, 150, 16, 'random'), (32, 2048, 150, 16, 'curve'), (3, 700, 150, 16, 'reverse'),
-                                          (9, 1000, 40, 20, 'random'), (2, 192, 64, 9, 'lattice')])
+                                          (9, 1000, 40, 20, 'random'), (2, 192, 64, 9, 'lattice'),
+                                          # the hint on the ordered-list kernels: <8> (C > 160) and <2> (k > 32)
+                                          (2, 300, 200, 16, 'random'), (2, 200, 64, 40, 'reverse')])
 def test_knn_with_a_locality_order_is_still_exact(gpe, B, N, C, k, kind):
     """gpe_knn's order_in (round 6) is a SPEED hint of the wide-feature search: plane rows laid out in the caller's order, every query
     tile's scan started one tile before its own tile.  The answer must not depend on it: bit-exact against the C oracle and equal to
@@ -250,6 +263,32 @@ def test_knn_with_a_locality_order_is_still_exact(gpe, B, N, C, k, kind):
     for b in sorted({0, B // 2, B - 1}):
         ref = O.knn_local(x[b * N:(b + 1) * N].contiguous(), 1, k).to(torch.int32).view(N, k)
         assert torch.equal(hinted[b].cpu(), ref), b
+
+
+@pytest.mark.parametrize('B,N,C,k,short', [(2, 130, 24, 5, None), (2, 300, 3, 8, None), (2, 130, 24, 5, 1)])
+def test_knn_without_a_workspace_falls_back_to_the_all_pairs_kernel(gpe, B, N, C, k, short):
+    """gpe_knn with ws = NULL (not reachable through ops.knn, which always passes the queried size): wide rows leave the filter group
+    for the all-pairs kernel in one piece, an xyz cloud cannot be sorted and takes the all-pairs kernel too; both report the
+    identity order.  short = 1: a workspace one byte short of gpe_knn_ws_bytes (the query's 256 bytes of slack still hold every
+    region, so this one filters).  The oracle's graph in every case."""
+    from oracle import ref_path as O
+    from gpe_amd import _lib as L
+    g = torch.Generator().manual_seed(B * 100 + N + C)
+    x = torch.randn(B * N, C, generator=g)
+    ref = O.knn_local(x, B, k).to(torch.int32).view(B, N, k)
+    xd = x.cuda()
+    idx = torch.full((B, N, k), -7, device='cuda', dtype=torch.int32)
+    jg = torch.full((B, N, k), -7, device='cuda', dtype=torch.int32)
+    oo = torch.full((B, N), -7, device='cuda', dtype=torch.int32)
+    ws, nws = None, 0
+    if short:
+        nws = L.query('gpe_knn_ws_bytes', B, N, C, k) - short
+        ws = torch.empty(nws, device='cuda', dtype=torch.uint8)
+    L.call('gpe_knn', xd, B, N, C, xd.stride(0), k, idx, jg, None, oo, ws, nws)
+    bad = (idx.cpu() != ref).any(-1).sum().item()
+    assert bad == 0, '%d / %d queries differ' % (bad, B * N)
+    assert torch.equal(jg.cpu(), ref + (torch.arange(B, dtype=torch.int32) * N)[:, None, None])
+    assert torch.equal(oo.cpu(), torch.arange(N, dtype=torch.int32).expand(B, N))
 
 
 def test_knn_strided_rows(gpe):
