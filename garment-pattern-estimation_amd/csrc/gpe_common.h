@@ -28,7 +28,8 @@ static inline bool gpe_overlap(const void* p, size_t n, const void* q, size_t m)
 
 // Measurement switches of the library (A/B runs inside one GPU session: scripts/gpu_session.sh ab): environment variables that are
 // ONLY consulted when GPE_DEBUG=1 is set — a production process cannot be steered off the product path by a stray variable.
-//   GPE_W8 GPE_REV GPE_LAZY_DZ3 GPE_H3_LEFT          edge kernels        GPE_RD_DEEP GPE_RD_NOPC        reduce-GEMM paths
+//   GPE_W8 GPE_REV GPE_LAZY_DZ3 GPE_H3_LEFT          edge kernels
+//   GPE_RD_DEEP GPE_RD_NOPC                          reduce-GEMM paths (GpeRdSwitches, gpe_redgemm_plan.h)
 //   GPE_WV_KS GPE_WV_BJ GPE_RNN_F32                  recurrences
 //   GPE_KNN_PROBE _PIN _VEC _SPLIT _EXACT _F32FILTER _SORTED _NOORDER _FT _RR2      kNN (GpeKnnSwitches, gpe_knn_plan.h)
 static inline const char* gpe_dbg_env_str(const char* name)

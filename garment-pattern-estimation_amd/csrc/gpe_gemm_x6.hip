@@ -30,8 +30,8 @@
 // TN splits the rows over gridDim.x workgroups per output block; partial blocks go to the caller's `part` image
 // [split][MgPad][NgPad] (+ fp64 column sums) and gpe_redgemm_finish adds them in fp64 (gpe_redgemm.hip: same image as the exact path).
 #include "gpe_edgegemm_split_kernel.h"
+#include "gpe_redgemm_plan.h"        // GX_B (block edge: rows of A / columns of W; columns of U / of V), the TN launcher's plan
 
-#define GX_B 128                      // block edge (rows of A / columns of W; columns of U / of V)
 #define GX_PLANE (GX_B * 64)          // bytes: 128 rows x 32 k x 2
 #define GX_OP (3 * GX_PLANE)
 #define GX_BUF (2 * GX_OP)            // one step: both operands, 49152 bytes
@@ -380,20 +380,13 @@ __global__ __launch_bounds__(768) void gpe_gemm_x6_tn_kernel(GxRedParams p)
 // =====================================================================================================================
 // host side (called by gpe_linear / gpe_redgemm when the arithmetic mode allows it)
 // =====================================================================================================================
-static bool gx_rows16(const GpeRows& r, int cols)
-{
-    if (!r.base || (((uintptr_t)r.base) & 15) || (r.stride_outer & 3)) return false;
-    if (r.inner > 0) return !(r.stride_inner & 3) && r.stride_inner >= ((cols + 3) & ~3);
-    return r.stride_outer >= ((cols + 3) & ~3);
-}
-
 // 1 = launched, 0 = not on this kernel's menu
 int gpe_gemm_x6_linear(const GpeRows& a, const float* wp, int Npad, int Kq, const float* bias, const GpeRows& addend, float* y,
                        long y_so, long y_si, int y_inner, long M, int N, int K, int act, hipStream_t s)
 {
     // worth it from ~0.25 GFLOP with at least one full wave of blocks' worth of rows; A rows 16-byte loadable up to round4(K)
     if (M < 2048 || N < 48 || K < 32 || 2.0 * M * N * K < 2.5e8) return 0;
-    if (!gx_rows16(a, K) || (((uintptr_t)wp) & 15)) return 0;
+    if (!gpe_rd_rows_x6(a, K) || (((uintptr_t)wp) & 15)) return 0;
     GxLinParams p = {};
     p.a = a; p.wp = wp; p.Npad = Npad; p.Kq = Kq; p.bias = bias; p.addend = addend;
     p.y = y; p.y_so = y_so; p.y_si = y_si; p.y_inner = y_inner; p.act = act; p.M = M; p.N = N; p.K = K;
@@ -405,43 +398,22 @@ int gpe_gemm_x6_linear(const GpeRows& a, const float* wp, int Npad, int Kq, cons
     return 1;
 }
 
-// workspace floats this path needs for an Mg x Ng product (gpe_redgemm_ws takes the maximum over the paths)
-long gpe_gemm_x6_red_ws(int Mg, int Ng)
+// the TN kernel's launcher (gpe_redgemm_plan.h): the plan found the product on the menu (gpe_rd_x6_menu), cut the rows (gpe_rd_x6_split)
+// and laid out the partial image; gpe_redgemm_finish follows in the caller
+int gpe_gemm_x6_launch_redgemm(const RdParams& c, const GpeRdPlan& plan, hipStream_t s)
 {
-    const long MgPad = gpe_round_up(Mg, GX_B), NgPad = gpe_round_up(Ng, GX_B);
-    return 32L * MgPad * NgPad + 2L * 32 * MgPad + 8 + 1024;      // (+ 4 KB: the step timeline of gpe_debug_set(32768))
-}
-
-long gpe_gemm_x6_red_ws(int Mg, int Ng);
-// 1 = partial blocks written (the caller runs gpe_redgemm_finish over *nsplit partials of MgPad x NgPad), 0 = not on the menu
-int gpe_gemm_x6_redgemm(const GpeRows& u, const GpeRows& v, const float* v_shift, long rows, int Mg, int Ng, float* part, bool want_cs,
-                        int* nsplit, int* MgPad, int* NgPad, double** part_cs, hipStream_t s)
-{
-    // also the row-poor products (32 .. 736 rows: the exact kernels run those on ONE workgroup per column block — 39 - 53 us for
-    // 2 - 90 MFLOP): here they are a handful of 128 x 128 blocks of one to six steps
-    if (rows < 32 || rows >= (1L << 31) || Mg < 48 || Ng < 48 || 2.0 * rows * Mg * Ng < 2.0e6) return 0;
-    if (!gx_rows16(u, Mg) || !gx_rows16(v, Ng)) return 0;
-    const int mb = gpe_cdiv(Mg, GX_B), nb = gpe_cdiv(Ng, GX_B);
-    int S = gpe_num_cus() / (mb * nb);
-    if (S > 32) S = 32;
-    if (S > rows / 128) S = (int)(rows / 128);             // >= 4 steps per workgroup
-    if (S < 1) S = 1;
     GxRedParams p = {};
-    p.u = u; p.v = v; p.v_shift = v_shift; p.rows = rows;
-    p.rows_per_split = ((rows + S - 1) / S + 31) & ~31L;
-    S = (int)((rows + p.rows_per_split - 1) / p.rows_per_split);
-    p.Mg = Mg; p.Ng = Ng; p.MgPad = mb * GX_B; p.NgPad = nb * GX_B;
-    p.part = part;
-    size_t off = (size_t)S * p.MgPad * p.NgPad;
-    off = (off + 1) & ~(size_t)1;
-    p.part_cs = want_cs ? reinterpret_cast<double*>(part + off) : nullptr;
-    if (gpe_debug_get() & 32768) {
-        p.trace = reinterpret_cast<unsigned long long*>(part + gpe_gemm_x6_red_ws(Mg, Ng) - 1024);
+    p.u = c.u; p.v = c.v; p.v_shift = c.v_shift; p.rows = c.rows;
+    p.rows_per_split = plan.rows_per_split;
+    p.Mg = c.Mg; p.Ng = c.Ng; p.MgPad = plan.MgPad; p.NgPad = plan.NgPad;
+    p.part = c.part;
+    p.part_cs = c.part_cs;
+    if (plan.trace_off >= 0) {
+        p.trace = reinterpret_cast<unsigned long long*>(c.part + plan.trace_off);
         if (hipMemsetAsync(p.trace, 0, 4096, s) != hipSuccess) return GPE_ELAUNCH;
     }
     GPE_ENSURE_MAX_LDS(gpe_gemm_x6_tn_kernel);
-    hipLaunchKernelGGL(gpe_gemm_x6_tn_kernel, dim3(S, mb, nb), dim3(768), GX_LDS, s, p);
+    hipLaunchKernelGGL(gpe_gemm_x6_tn_kernel, dim3(plan.gx, plan.gy, plan.gz), dim3(768), GX_LDS, s, p);
     GPE_CHECK_LAUNCH();
-    *nsplit = S; *MgPad = p.MgPad; *NgPad = p.NgPad; *part_cs = p.part_cs;
-    return 1;
+    return GPE_OK;
 }

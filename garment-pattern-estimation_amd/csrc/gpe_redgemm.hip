@@ -1,59 +1,34 @@
 // Reduce-GEMM family for gfx950:  G[Mg, Ng] = sum over rows r of U[r, :]^T V[r, :]   (+ colsum of U)
 //
-// This is the weight-gradient half of every Linear on the path (nn.Linear backward under
-// /root/reference/nn/trainer.py:97 `loss.backward()`).  V rows are either dense or the EdgeConv gather
-// relu(P_i + Q_j) rebuilt on the fly.  Because BatchNorm's backward reductions are linear in the same products,
-// G and colsum(U) are also all that the BN backward of the previous block needs (gpe_bn_bwd_from_G) — no extra
+// This is the weight-gradient half of every Linear on the path (nn.Linear backward under the trainer's `loss.backward()`).  V rows
+// are either dense or the EdgeConv gather relu(P_i + Q_j) rebuilt on the fly.  Because BatchNorm's backward reductions are linear in
+// the same products, G and colsum(U) are also all that the BN backward of the previous block needs (gpe_bn_bwd_from_G) — no extra
 // pass over the E edges.
 //
-// Structure: ONE persistent 256-thread workgroup per CU (grid = #CUs), 512-VGPR budget per wave.
-//   * 32-row operand tiles are fetched global -> registers one tile AHEAD (the dependent idx -> Q-row gather
-//     included), written to a double-buffered LDS image after the current tile's MFMAs: one barrier per tile, HBM/L2
-//     latency fully under the matrix pipe;
-//   * the 4 waves tile G 2x2: wave (wm, wn) keeps the accumulators of M-tiles [wm*MH, ..) x N-tiles [wn*NH, ..)
-//     in registers across ALL its row tiles (v_mfma_f32_16x16x4_f32, reduction dim = rows); 13 x 13 tiles split
-//     7/6 x 7/6 instead of 4/3/3/3 rows of 13 (86 % vs 81 % balance, half the operand reads);
-//   * one partial per workgroup at the end; a second kernel sums the partials in a fixed order (fp64), so results
-//     are run-to-run deterministic.
+// Every kernel writes one partial G (and partial column sums) per workgroup along x into the caller's `part` image
+// (gpe_rd_layout); gpe_redgemm_finish sums the partials in a fixed order in fp64, so results are run-to-run deterministic.
+// Which kernel runs is decided in gpe_redgemm_plan.h, not here.  Map of this file, five kernel families:
+//   1  gpe_redgemm_kernel<MH, NH, VMODE>         big-block: ONE persistent 256-thread workgroup per CU, 512-VGPR budget per wave.
+//        32-row operand tiles are fetched global -> registers one tile AHEAD (the dependent idx -> Q-row gather included), written
+//        to a double-buffered LDS image after the current tile's MFMAs: one barrier per tile.  The 4 waves tile G 2x2: wave (wm, wn)
+//        keeps M-tiles [wm*MH, ..) x N-tiles [wn*NH, ..) in registers across ALL its row tiles (v_mfma_f32_16x16x4_f32, reduction
+//        dim = rows); 13 x 13 tiles split 7/6 x 7/6 instead of 4/3/3/3 rows of 13 (86 % vs 81 % balance, half the operand reads).
+//        The general kernel: any Mg, Ng <= 256, dense or gathered V, any row descriptor
+//   2  gpe_redgemm_pc_kernel<MT, NT, VMODE>      producer/consumer, exact fp32: the edge weight-gradient shapes (13 x {13, 10} tiles)
+//   3  gpe_redgemm_b3_kernel<MT, NT, VMODE, F16, LAZY>   the same shapes on the 16-bit matrix pipe: bf16x3, f16x3 (amax words), and
+//        f16x3 LAZY, which forms U = dz3 from the stored activation
+//   4  gpe_redgemm_deep_kernel<VVEC>             row-poor dense products: 64 x 64 output blocks, row split <= RDD_MAX_GX
+//   5  gpe_redgemm_thin_kernel<QL>               Ng <= 4: streams U once, no matrix pipe
+// then gpe_redgemm_finish, one launcher per plan outcome (the bf16-pipe TN kernel and its launcher are in gpe_gemm_x6.hip), rd_run
+// and the entry points.
 #include "gpe_device.h"
+#include "gpe_redgemm_plan.h"
 #include <stdlib.h>
 
-long gpe_gemm_x6_red_ws(int Mg, int Ng);                                                 // gpe_gemm_x6.hip
-int gpe_gemm_x6_redgemm(const GpeRows& u, const GpeRows& v, const float* v_shift, long rows, int Mg, int Ng, float* part, bool want_cs,
-                        int* nsplit, int* MgPad, int* NgPad, double** part_cs, hipStream_t s);
 extern "C" int gpe_debug_get(void);
 static int g_rd_math = 0;            // 0: exact fp32 MFMA, 1: bf16x3, 2: f16x3 where the operand scales are known (gpe_math_set)
 void gpe_redgemm_set_math(int m) { g_rd_math = m; }
 
-#define RD_RT 32
-
-enum { V_GATHER = 0, V_DENSE = 1 };
-
-struct RdParams {
-    long rows;
-    int Mg, Ng, MgPad, NgPad;
-    int num_tiles;
-    GpeRows u;
-    GpeRows v;                                   // V_DENSE
-    const float* pq; int ldpq; int H; const int32_t* jg; int k; double rcp_k;   // V_GATHER (global neighbour rows)
-    unsigned kmagic;                             // ceil(2^32 / k): row / k == umulhi(row, kmagic) while row * k < 2^32 (pc kernel)
-    unsigned umagic, vmagic;                     // the same for u.inner / v.inner (2-level rows of the deep kernel)
-    int pin_clouds;                              // B when the rows are B equal clouds (gpe_edge_redgemm), else 0
-    const float* v_shift;                        // optional [Ng]: V := V - shift on valid rows (BN centring)
-    int vec;                                     // rows aligned to 16 B and padded to 4 columns: plain 16-B loads
-    int pin_tpc;                                 // gather variants of the pc/b3 kernels: tiles per cloud when pinned (gpe_common.h)
-    int rev;                                     // walk the tile sequence from the far end (gpe_common.h GpeTileSeq)
-    float* part;                                 // [gridDim.x][MgPad][NgPad]
-    double* part_cs;                             // [gridDim.x][MgPad]
-    // f16x3 variant of the b3 kernel: bit patterns of the largest magnitudes of U and of V - shift (device memory)
-    const unsigned* amax_u;
-    const unsigned* amax_v;
-    // LAZY dz3 (f16x3, k = 16, dense V): U is the stored activation a3 of the aggregated block and the producers form dz3 from it
-    // (gpe_edge_dz3's arithmetic; RgParams::lz_* of the edge kernels has the same fields).  NULL = off.
-    const float* lz_g; int lz_ldg;
-    const uint8_t* lz_amx; const uint8_t* lz_amn; int lz_ldagg;
-    const float* lz_coef;                        // [4][Mg] = {s, c1, k2, mean}
-};
 // b3 kernel, compile-time switches (A/B builds through scripts/ab_build.sh; run-time flags cost this kernel registers it does not
 // have: a run-time `pipe` flag spilled 120 of them in the gathered 13 x 13 instance):
 //   RD_B3_PIPE  producers' order: 0 (default) = fetch tile t + 1 ... left-over MFMAs ... commit it (round 4); 1 = the two operands
@@ -990,9 +965,7 @@ __global__ __launch_bounds__(512, 2) void gpe_redgemm_b3_kernel(RdParams p)
 // split stays <= 32 and a workgroup still runs tens of row tiles.  Rows are addressed through the
 // 2-level descriptor with plain 16-B loads (aligned pitches, rows padded to 4 columns: every internal sequence buffer).
 // ---------------------------------------------------------------------------------------------------------
-#define RDD_B 64
 #define RDD_LD 80                     // == 16 (mod 32): conflict-free b32 operand reads
-#define RDD_MAX_GX 32
 
 // 2-level row offset with the division as one v_mul_hi_u32 (host: r * inner < 2^32)
 __device__ __forceinline__ long rd_row_off_magic(const GpeRows& a, unsigned r, unsigned magic)
@@ -1158,15 +1131,6 @@ __global__ __launch_bounds__(256, 3) void gpe_redgemm_deep_kernel(RdParams p)
     }
 }
 
-// rows a 16-B loader can take through the 2-level descriptor: aligned base and pitches, rows padded to 4 columns
-static bool rd_rows_vec2(const GpeRows& r, int cols)
-{
-    const long pitch = r.inner > 0 ? r.stride_inner : r.stride_outer;
-    if ((((uintptr_t)r.base) & 15) || (r.stride_outer & 3)) return false;
-    if (r.inner > 0 && (r.stride_inner & 3)) return false;
-    return pitch >= ((cols + 3) & ~3) || (cols & 3) == 0;
-}
-
 // ---------------------------------------------------------------------------------------------------------
 // Thin products (Ng <= 4: the weight gradient of a Linear on raw xyz positions, 65 536 x 400 against 65 536 x 3): nothing for
 // the matrix pipe, the job is to stream U once.  Workgroup = a contiguous row range, wave w takes its rows w, w+4, ...,
@@ -1174,7 +1138,6 @@ static bool rd_rows_vec2(const GpeRows& r, int cols)
 // rows per wave, then the four waves are added in fp64 and one partial per workgroup goes to gpe_redgemm_finish.
 // HBM-bound (rows * Mg * 4 bytes): 80 -> ~25 us on the shape above, against the 224 x 256 big-block kernel.
 // ---------------------------------------------------------------------------------------------------------
-#define RDT_GX 512
 #define RDT_RB 4
 template <int QL>
 __global__ __launch_bounds__(256) void gpe_redgemm_thin_kernel(RdParams p)
@@ -1263,23 +1226,7 @@ __global__ __launch_bounds__(256) void gpe_redgemm_thin_kernel(RdParams p)
     }
 }
 
-// row split of the deep kernel: ~3 workgroups per CU, but enough of them for at most RDD_MAX_TPW row tiles each as far as the
-// RDD_MAX_GX partial images allow (every workgroup sums its tiles in one fp32 accumulator chain, whose rounding grows with its length:
-// sized by the CU count alone, 64 usable CUs put 8 k rows into one chain just below the deep-kernel switch, 3.1e-6 of max|G| against
-// fp64), and at least 4 row tiles each
-#define RDD_MAX_TPW 64                // = the big-block kernel's tiles per workgroup at the switch (num_tiles < 64 gx)
-static int rdd_gx(int Mg, int Ng, long num_tiles, int cus)
-{
-    const long blocks = (long)gpe_cdiv(Mg, RDD_B) * gpe_cdiv(Ng, RDD_B);
-    long gx = gpe_cdiv(3L * cus, blocks);
-    if (num_tiles >= 0 && gx < gpe_cdiv(num_tiles, (long)RDD_MAX_TPW)) gx = gpe_cdiv(num_tiles, (long)RDD_MAX_TPW);
-    if (gx > RDD_MAX_GX) gx = RDD_MAX_GX;
-    if (num_tiles >= 0 && gx > num_tiles / 4) gx = num_tiles / 4;
-    return gx < 1 ? 1 : (int)gx;
-}
-
-#define RD_FIN_E 32
-#define RD_FIN_Q 8
+// the finish: every path's nblk partials summed per output element in fp64, in one fixed order (RD_FIN_Q partials side by side)
 __global__ __launch_bounds__(RD_FIN_E * RD_FIN_Q) void gpe_redgemm_finish(
     const float* __restrict__ part, const double* __restrict__ part_cs, int nblk, int Mg, int Ng, int MgPad, int NgPad,
     float* G, int ldg, float* colsum, int accumulate)
@@ -1329,62 +1276,43 @@ __global__ __launch_bounds__(RD_FIN_E * RD_FIN_Q) void gpe_redgemm_finish(
 }
 
 // ---------------------------------------------------------------------------------------------------------
-static int rd_pick(int need, const int* opts, int n)
+// Host side.  gpe_redgemm_plan (gpe_redgemm_plan.h) decides; below: the workspace query, one launcher per outcome — each sizes its
+// LDS beside its launch and decides nothing —, the one finish launch, rd_run and the entry points.
+// ---------------------------------------------------------------------------------------------------------
+const GpeRdSwitches& gpe_rd_switches()
 {
-    for (int i = 0; i < n; ++i) if (opts[i] >= need) return opts[i];
-    return -1;
-}
-static const int RD_MH_OPTS[3] = {2, 5, 7};
-static const int RD_NH_OPTS[4] = {1, 5, 7, 8};
-
-static int rd_num_cus() { return gpe_num_cus(); }
-
-// geometry shared by the workspace query and the launcher (no device query here: the ws size must be computable on a
-// CPU-only box, so it is sized for the largest grid we ever launch)
-#define RD_MAX_GX 256
-// rows < 0: workspace query -> the largest M block (an upper bound of every geometry below: gx * MgPad grows with MH).
-static void rd_geometry(int Mg, int Ng, long rows, int* MH, int* NH, int* gy, int* MgPad, int* NgPad)
-{
-    // (64-row output blocks for the row-poor LSTM weight gradients were tried and measured slower: 2.43 vs 1.95 ms per
-    // step — only 16 of 64 staging lanes carry U columns)
-    const int mt = gpe_cdiv(Mg, 16), nt = gpe_cdiv(Ng, 16);
-    const int mtb = mt < 14 ? mt : 14;
-    int mh = rd_pick(gpe_cdiv(mtb, 2), RD_MH_OPTS, 3);
-    // (r02: for the row-poor LSTM weight gradients — 10 k rows against a 1000 x 250 output — a narrower M block with fewer
-    // row splits was tried: partials 52 -> 16 MB, but the reduce-GEMM time went UP, 1.85 -> 2.56 ms per step: with 2 M-tiles
-    // per wave the V operand is re-read 3.5x as often from LDS and the MFMA stream is too short to hide it.  `rows` stays in
-    // the signature for the next attempt.)
-    (void)rows;
-    *MH = mh;
-    *NH = rd_pick(gpe_cdiv(nt, 2), RD_NH_OPTS, 4);
-    *gy = gpe_cdiv(mt, 2 * (*MH));
-    *MgPad = (*gy) * 32 * (*MH);
-    *NgPad = gpe_round_up(Ng, 16);
+    static const GpeRdSwitches sw = {gpe_dbg_env("GPE_RD_DEEP", -1), gpe_dbg_env("GPE_RD_NOPC", 0)};
+    return sw;
 }
 
-extern "C" long gpe_redgemm_ws(int Mg, int Ng)
+extern "C" long gpe_redgemm_ws(int Mg, int Ng) { return gpe_rd_ws_floats(Mg, Ng); }
+
+static int rd_launch_thin(const RdParams& p, const GpeRdPlan& plan, hipStream_t s)
 {
-    int MH, NH, gy, MgPad, NgPad;
-    rd_geometry(Mg, Ng, -1, &MH, &NH, &gy, &MgPad, &NgPad);
-    if (NH < 0) return -1;
-    const long gx = RD_MAX_GX / gy > 0 ? RD_MAX_GX / gy : 1;
-    const long big = gx * MgPad * NgPad + 2L * gx * MgPad + 8;
-    const long dM = gpe_round_up(Mg, RDD_B), dN = gpe_round_up(Ng, RDD_B);
-    const long deep = RDD_MAX_GX * dM * dN + 2L * RDD_MAX_GX * dM + 8;
-    const long mr = gpe_round_up(Mg, 4);
-    const long thin = Ng <= 4 ? (long)RDT_GX * mr * 4 + 2L * RDT_GX * mr + 8 : 0;      // gpe_redgemm_thin_kernel
-    const long m2 = big > deep ? big : deep;
-    const long m3 = m2 > thin ? m2 : thin;
-    const long x6 = gpe_gemm_x6_red_ws(Mg, Ng);
-    return m3 > x6 ? m3 : x6;
+    const size_t lds = (size_t)4 * p.MgPad * 5 * sizeof(float);
+    if (plan.ql <= 1) { GPE_ENSURE_MAX_LDS((gpe_redgemm_thin_kernel<1>)); hipLaunchKernelGGL(gpe_redgemm_thin_kernel<1>, dim3(plan.gx), dim3(256), lds, s, p); }
+    else if (plan.ql == 2) { GPE_ENSURE_MAX_LDS((gpe_redgemm_thin_kernel<2>)); hipLaunchKernelGGL(gpe_redgemm_thin_kernel<2>, dim3(plan.gx), dim3(256), lds, s, p); }
+    else { GPE_ENSURE_MAX_LDS((gpe_redgemm_thin_kernel<4>)); hipLaunchKernelGGL(gpe_redgemm_thin_kernel<4>, dim3(plan.gx), dim3(256), lds, s, p); }
+    GPE_CHECK_LAUNCH();
+    return GPE_OK;
 }
 
-template <int MH, int NH, int VMODE>
-static int rd_launch(const RdParams& p, dim3 grid, hipStream_t s)
+static int rd_launch_deep(const RdParams& p, const GpeRdPlan& plan, hipStream_t s)
 {
-    const size_t lds = (size_t)2 * RD_RT * ((32 * MH + 16) + (32 * NH + 16)) * sizeof(float);
-    GPE_ENSURE_MAX_LDS((gpe_redgemm_kernel<MH, NH, VMODE>));
-    hipLaunchKernelGGL((gpe_redgemm_kernel<MH, NH, VMODE>), grid, dim3(256), lds, s, p);
+    const size_t lds = (size_t)4 * RD_RT * RDD_LD * sizeof(float);
+    const dim3 grid(plan.gx, plan.gy, plan.gz);
+    if (plan.vvec) hipLaunchKernelGGL(gpe_redgemm_deep_kernel<true>, grid, dim3(256), lds, s, p);
+    else hipLaunchKernelGGL(gpe_redgemm_deep_kernel<false>, grid, dim3(256), lds, s, p);
+    GPE_CHECK_LAUNCH();
+    return GPE_OK;
+}
+
+template <int MT, int NT, int VMODE, bool F16 = false, bool LAZY = false>
+static int rd_b3_launch(const RdParams& p, int gx, hipStream_t s)
+{
+    const size_t lds = (size_t)2 * (RdB3Layout<MT>::BYTES + RdB3Layout<NT>::BYTES);
+    GPE_ENSURE_MAX_LDS((gpe_redgemm_b3_kernel<MT, NT, VMODE, F16, LAZY>));
+    hipLaunchKernelGGL((gpe_redgemm_b3_kernel<MT, NT, VMODE, F16, LAZY>), dim3(gx), dim3(512), lds, s, p);
     GPE_CHECK_LAUNCH();
     return GPE_OK;
 }
@@ -1402,159 +1330,94 @@ static int rd_pc_launch(const RdParams& p, int gx, hipStream_t s)
     return GPE_OK;
 }
 
-template <int MT, int NT, int VMODE, bool F16 = false, bool LAZY = false>
-static int rd_b3_launch(const RdParams& p, int gx, hipStream_t s)
+template <int MH, int NH, int VMODE>
+static int rd_big_launch(const RdParams& p, dim3 grid, hipStream_t s)
 {
-    const size_t lds = (size_t)2 * (RdB3Layout<MT>::BYTES + RdB3Layout<NT>::BYTES);
-    GPE_ENSURE_MAX_LDS((gpe_redgemm_b3_kernel<MT, NT, VMODE, F16, LAZY>));
-    hipLaunchKernelGGL((gpe_redgemm_b3_kernel<MT, NT, VMODE, F16, LAZY>), dim3(gx), dim3(512), lds, s, p);
+    const size_t lds = (size_t)2 * RD_RT * ((32 * MH + 16) + (32 * NH + 16)) * sizeof(float);
+    GPE_ENSURE_MAX_LDS((gpe_redgemm_kernel<MH, NH, VMODE>));
+    hipLaunchKernelGGL((gpe_redgemm_kernel<MH, NH, VMODE>), grid, dim3(256), lds, s, p);
     GPE_CHECK_LAUNCH();
     return GPE_OK;
 }
 
-template <int VMODE>
-static int rd_dispatch(int MH, int NH, const RdParams& p, dim3 grid, hipStream_t s)
+// (the launchers below name their instances in this order: the order of first use is the order the kernels are emitted in)
+static int rd_launch_b3_lazy(const RdParams& p, const GpeRdPlan& plan, hipStream_t s)
 {
-#define RD_CASE(M_, N_) if (MH == M_ && NH == N_) return rd_launch<M_, N_, VMODE>(p, grid, s)
+    return (plan.MT == 13) ? rd_b3_launch<13, 13, V_DENSE, true, true>(p, plan.gx, s) : rd_b3_launch<10, 13, V_DENSE, true, true>(p, plan.gx, s);
+}
+
+static int rd_launch_b3_f16(const RdParams& p, const GpeRdPlan& plan, hipStream_t s)
+{
+    if (plan.MT == 13 && plan.vmode == V_DENSE) return rd_b3_launch<13, 13, V_DENSE, true>(p, plan.gx, s);
+    if (plan.MT == 13) return rd_b3_launch<13, 13, V_GATHER, true>(p, plan.gx, s);
+    if (plan.vmode == V_DENSE) return rd_b3_launch<10, 13, V_DENSE, true>(p, plan.gx, s);
+    return rd_b3_launch<10, 13, V_GATHER, true>(p, plan.gx, s);
+}
+static int rd_launch_b3_bf16(const RdParams& p, const GpeRdPlan& plan, hipStream_t s)
+{
+    if (plan.MT == 13 && plan.vmode == V_DENSE) return rd_b3_launch<13, 13, V_DENSE>(p, plan.gx, s);
+    if (plan.MT == 13) return rd_b3_launch<13, 13, V_GATHER>(p, plan.gx, s);
+    if (plan.vmode == V_DENSE) return rd_b3_launch<10, 13, V_DENSE>(p, plan.gx, s);
+    return rd_b3_launch<10, 13, V_GATHER>(p, plan.gx, s);
+}
+static int rd_launch_pc(const RdParams& p, const GpeRdPlan& plan, hipStream_t s)
+{
+    if (plan.MT == 13 && plan.vmode == V_DENSE) return rd_pc_launch<13, 13, V_DENSE>(p, plan.gx, s);
+    if (plan.MT == 13) return rd_pc_launch<13, 13, V_GATHER>(p, plan.gx, s);
+    if (plan.vmode == V_DENSE) return rd_pc_launch<10, 13, V_DENSE>(p, plan.gx, s);
+    return rd_pc_launch<10, 13, V_GATHER>(p, plan.gx, s);
+}
+
+template <int VMODE>
+static int rd_big_menu(const RdParams& p, const GpeRdPlan& plan, hipStream_t s)
+{
+    const dim3 grid(plan.gx, plan.gy);
+#define RD_CASE(M_, N_) if (plan.MH == M_ && plan.NH == N_) return rd_big_launch<M_, N_, VMODE>(p, grid, s)
     RD_CASE(2, 1); RD_CASE(2, 5); RD_CASE(2, 7); RD_CASE(2, 8);
     RD_CASE(5, 1); RD_CASE(5, 5); RD_CASE(5, 7); RD_CASE(5, 8);
     RD_CASE(7, 1); RD_CASE(7, 5); RD_CASE(7, 7); RD_CASE(7, 8);
 #undef RD_CASE
     return GPE_EINVAL;
 }
-
-static bool rd_rows_vec(const GpeRows& r, int cols)
+static int rd_launch_big(const RdParams& p, const GpeRdPlan& plan, hipStream_t s)
 {
-    return r.inner <= 0 && !(r.stride_outer & 3) && r.stride_outer >= ((cols + 3) & ~3) && !(((uintptr_t)r.base) & 15);
+    return (plan.vmode == V_DENSE) ? rd_big_menu<V_DENSE>(p, plan, s) : rd_big_menu<V_GATHER>(p, plan, s);
 }
 
-static int rd_run(RdParams& p, int vmode, float* G, int ldG, float* colsum, float* part, int accumulate,
-                  hipStream_t s)
+// the one finish launch, after whichever path wrote its plan.nblk partials: ceil(Mg Ng / RD_FIN_E) workgroups reduce G, the
+// ceil(Mg / RD_FIN_E) after them the column sums (if the caller wants them)
+static int rd_finish(const RdParams& p, const GpeRdPlan& plan, float* G, int ldG, float* colsum, int accumulate, hipStream_t s)
 {
-    // aligned, 4-padded rows take the plain unconditional 16-B loader (all RQ loads in flight); anything else the
-    // guarded scalar-tail loader
-    p.vec = rd_rows_vec(p.u, p.Mg) && (vmode == V_GATHER || rd_rows_vec(p.v, p.Ng));
-    int MH, NH, gy, MgPad, NgPad;
-    rd_geometry(p.Mg, p.Ng, p.rows, &MH, &NH, &gy, &MgPad, &NgPad);
-    if (MH < 0 || NH < 0) return GPE_EINVAL;
-    p.MgPad = MgPad; p.NgPad = NgPad;
-    p.num_tiles = gpe_cdiv(p.rows, RD_RT);
-    int cus = rd_num_cus();
-    if (cus > RD_MAX_GX) cus = RD_MAX_GX;
-    int gx = cus / gy;
-    if (gx < 1) gx = 1;
-    if (gx > p.num_tiles) gx = p.num_tiles > 0 ? p.num_tiles : 1;
-    p.part = part;
-    // row-poor dense products (fewer than 64 row tiles per workgroup of the big-block grid) with a 16-B loadable U
-    // thin products: stream U once (Ng <= 4, plain 16-B loadable U rows, single-level rows on both sides)
-    if (vmode == V_DENSE && !p.lz_g && p.Ng <= 4 && p.Mg <= 1024 && p.rows >= 4096 && p.u.inner <= 0 && p.v.inner <= 0 &&
-        rd_rows_vec(p.u, p.Mg)) {
-        const int gxt = (int)(p.rows / 64 < RDT_GX ? p.rows / 64 : RDT_GX);
-        p.MgPad = gpe_round_up(p.Mg, 4); p.NgPad = 4;
-        size_t toff = (size_t)gxt * p.MgPad * 4;
-        toff = (toff + 1) & ~(size_t)1;
-        p.part_cs = colsum ? reinterpret_cast<double*>(part + toff) : nullptr;
-        const size_t lds = (size_t)4 * p.MgPad * 5 * sizeof(float);
-        const int ql = gpe_cdiv(p.MgPad, 256);
-        if (ql <= 1) { GPE_ENSURE_MAX_LDS((gpe_redgemm_thin_kernel<1>)); hipLaunchKernelGGL(gpe_redgemm_thin_kernel<1>, dim3(gxt), dim3(256), lds, s, p); }
-        else if (ql == 2) { GPE_ENSURE_MAX_LDS((gpe_redgemm_thin_kernel<2>)); hipLaunchKernelGGL(gpe_redgemm_thin_kernel<2>, dim3(gxt), dim3(256), lds, s, p); }
-        else { GPE_ENSURE_MAX_LDS((gpe_redgemm_thin_kernel<4>)); hipLaunchKernelGGL(gpe_redgemm_thin_kernel<4>, dim3(gxt), dim3(256), lds, s, p); }
-        GPE_CHECK_LAUNCH();
-        const long fin_t = gpe_cdiv((long)p.Mg * p.Ng, RD_FIN_E) + (colsum ? gpe_cdiv(p.Mg, RD_FIN_E) : 0);
-        hipLaunchKernelGGL(gpe_redgemm_finish, dim3(fin_t), dim3(RD_FIN_E * RD_FIN_Q), 0, s, p.part, p.part_cs, gxt, p.Mg,
-                           p.Ng, p.MgPad, p.NgPad, G, ldG, colsum, accumulate);
-        GPE_CHECK_LAUNCH();
-        return GPE_OK;
-    }
-    // f16x3 mode: row-rich dense products off the edge kernels' menu (the decoders' weight gradients, 10304 rows x 1000 x 250; the
-    // [P|Q] projection's, 65536 x 400 x 150) on the bf16 pipe, three-term splits (gpe_gemm_x6.hip): same partial image, same finish
-    if (vmode == V_DENSE && g_rd_math == 2 && !p.lz_g && !(gpe_debug_get() & 16384) &&
-        !(gpe_cdiv(p.Ng, 16) == 13 && (gpe_cdiv(p.Mg, 16) == 13 || gpe_cdiv(p.Mg, 16) == 10) && gy == 1 && p.amax_u && p.amax_v)) {
-        int ns = 0, mp = 0, np = 0;
-        double* pcs = nullptr;
-        const int rc = gpe_gemm_x6_redgemm(p.u, p.v, p.v_shift, p.rows, p.Mg, p.Ng, part, colsum != nullptr, &ns, &mp, &np, &pcs, s);
-        if (rc < 0) return rc;
-        if (rc == 1) {
-            const long fin_x = gpe_cdiv((long)p.Mg * p.Ng, RD_FIN_E) + (colsum ? gpe_cdiv(p.Mg, RD_FIN_E) : 0);
-            hipLaunchKernelGGL(gpe_redgemm_finish, dim3(fin_x), dim3(RD_FIN_E * RD_FIN_Q), 0, s, part, pcs, ns, p.Mg, p.Ng, mp, np, G, ldG,
-                               colsum, accumulate);
-            GPE_CHECK_LAUNCH();
-            return GPE_OK;
-        }
-    }
-    const long in_max = (p.u.inner > p.v.inner ? p.u.inner : p.v.inner) > 1 ? (p.u.inner > p.v.inner ? p.u.inner : p.v.inner) : 1;
-    static const int dbg_deep = gpe_dbg_env("GPE_RD_DEEP", -1);   // measurement override: 0 = never the deep kernel
-    // the edge weight-gradient shapes (<= 208 x 208 outputs, plain 16-B rows, >= 4 row tiles per workgroup) stay on the
-    // producer/consumer kernels below at every size: measured (profiles/r04_h_rd_paths.md, dense V, 150 x 200) 48 / 64 / 106 / 206 us
-    // against the deep kernel's 70 / 107 / 204 / 403 us at E = 41 k / 66 k / 131 k / 262 k rows (f16x3: 46 / 53 / 70 / 127 us); the deep
-    // kernel keeps the row-poor decoder products it was built for (10 k rows x 1000 x 250: 79 against 154 us)
-    const bool edge_shape = gpe_cdiv(p.Ng, 16) == 13 && (gpe_cdiv(p.Mg, 16) == 13 || gpe_cdiv(p.Mg, 16) == 10) && gy == 1 &&
-                            rd_rows_vec(p.u, p.Mg) && rd_rows_vec(p.v, p.Ng) && p.num_tiles >= 4L * gx;
-    if (vmode == V_DENSE && g_rd_math != 1 && !p.lz_g && !edge_shape && dbg_deep != 0 && p.num_tiles > 0 && p.num_tiles < 64L * gx && p.rows * in_max < (1L << 32) &&
-        p.rows < (1L << 31) && rd_rows_vec2(p.u, p.Mg)) {
-        p.umagic = p.u.inner > 1 ? (unsigned)(((1ull << 32) + p.u.inner - 1) / p.u.inner) : 0;
-        p.vmagic = p.v.inner > 1 ? (unsigned)(((1ull << 32) + p.v.inner - 1) / p.v.inner) : 0;
-        const int dgx = rdd_gx(p.Mg, p.Ng, p.num_tiles, cus);
-        const int dgy = gpe_cdiv(p.Mg, RDD_B), dgz = gpe_cdiv(p.Ng, RDD_B);
-        p.MgPad = dgy * RDD_B; p.NgPad = dgz * RDD_B;
-        size_t doff = (size_t)dgx * p.MgPad * p.NgPad;
-        doff = (doff + 1) & ~(size_t)1;
-        p.part_cs = colsum ? reinterpret_cast<double*>(part + doff) : nullptr;
-        const size_t lds = (size_t)4 * RD_RT * RDD_LD * sizeof(float);
-        if (rd_rows_vec2(p.v, p.Ng)) hipLaunchKernelGGL(gpe_redgemm_deep_kernel<true>, dim3(dgx, dgy, dgz), dim3(256), lds, s, p);
-        else hipLaunchKernelGGL(gpe_redgemm_deep_kernel<false>, dim3(dgx, dgy, dgz), dim3(256), lds, s, p);
-        GPE_CHECK_LAUNCH();
-        const long total_d = (long)p.Mg * p.Ng;
-        const long fin_d = gpe_cdiv(total_d, RD_FIN_E) + (colsum ? gpe_cdiv(p.Mg, RD_FIN_E) : 0);
-        hipLaunchKernelGGL(gpe_redgemm_finish, dim3(fin_d), dim3(RD_FIN_E * RD_FIN_Q), 0, s, p.part, p.part_cs, dgx, p.Mg,
-                           p.Ng, p.MgPad, p.NgPad, G, ldG, colsum, accumulate);
-        GPE_CHECK_LAUNCH();
-        return GPE_OK;
-    }
-    size_t off = (size_t)gx * MgPad * NgPad;
-    off = (off + 1) & ~(size_t)1;                                  // 8-B align the fp64 section
-    p.part_cs = reinterpret_cast<double*>(part + off);
-    dim3 grid(gx, gy);
-    int rc = GPE_EINVAL;
-    const int mt_all = gpe_cdiv(p.Mg, 16), nt_all = gpe_cdiv(p.Ng, 16);
-    static const int dbg_nopc = gpe_dbg_env("GPE_RD_NOPC", 0);     // measurement override
-    const bool pc_ok = !dbg_nopc && gy == 1 && nt_all == 13 && (mt_all == 13 || mt_all == 10) && rd_rows_vec(p.u, p.Mg) &&
-                       (vmode == V_GATHER || rd_rows_vec(p.v, p.Ng)) && p.num_tiles >= 4 * gx &&
-                       (vmode != V_GATHER || (p.k > 1 && p.rows * p.k < (1L << 32)));   // umulhi row / k (kmagic)
-    p.pin_tpc = 0;
-    if (pc_ok && vmode == V_GATHER && p.pin_clouds > 0 && gpe_pin_clouds(p.pin_clouds) && p.pin_clouds % GPE_NXCD == 0) {
-        const long rows_per_cloud = p.rows / p.pin_clouds;
-        if (rows_per_cloud % RD_RT == 0 && gx % GPE_NXCD == 0 && rows_per_cloud / RD_RT >= gx / GPE_NXCD)
-            p.pin_tpc = (int)(rows_per_cloud / RD_RT);
-    }
-    if (p.lz_g) {
-        // lazy dz3: only the f16x3 dense-V kernel forms U on the fly; the caller asked gpe_edge_lazy_dz3_ok first
-        if (!(pc_ok && g_rd_math == 2 && p.amax_u && p.amax_v && vmode == V_DENSE && p.k == 16 && (p.rows & 15) == 0)) return GPE_EINVAL;
-        rc = (mt_all == 13) ? rd_b3_launch<13, 13, V_DENSE, true, true>(p, gx, s) : rd_b3_launch<10, 13, V_DENSE, true, true>(p, gx, s);
-    } else if (pc_ok && g_rd_math == 2 && p.amax_u && p.amax_v) {
-        if (mt_all == 13 && vmode == V_DENSE) rc = rd_b3_launch<13, 13, V_DENSE, true>(p, gx, s);
-        else if (mt_all == 13) rc = rd_b3_launch<13, 13, V_GATHER, true>(p, gx, s);
-        else if (vmode == V_DENSE) rc = rd_b3_launch<10, 13, V_DENSE, true>(p, gx, s);
-        else rc = rd_b3_launch<10, 13, V_GATHER, true>(p, gx, s);
-    } else if (pc_ok && g_rd_math == 1) {
-        if (mt_all == 13 && vmode == V_DENSE) rc = rd_b3_launch<13, 13, V_DENSE>(p, gx, s);
-        else if (mt_all == 13) rc = rd_b3_launch<13, 13, V_GATHER>(p, gx, s);
-        else if (vmode == V_DENSE) rc = rd_b3_launch<10, 13, V_DENSE>(p, gx, s);
-        else rc = rd_b3_launch<10, 13, V_GATHER>(p, gx, s);
-    } else if (pc_ok) {
-        if (mt_all == 13 && vmode == V_DENSE) rc = rd_pc_launch<13, 13, V_DENSE>(p, gx, s);
-        else if (mt_all == 13) rc = rd_pc_launch<13, 13, V_GATHER>(p, gx, s);
-        else if (vmode == V_DENSE) rc = rd_pc_launch<10, 13, V_DENSE>(p, gx, s);
-        else rc = rd_pc_launch<10, 13, V_GATHER>(p, gx, s);
-    } else
-        rc = (vmode == V_DENSE) ? rd_dispatch<V_DENSE>(MH, NH, p, grid, s) : rd_dispatch<V_GATHER>(MH, NH, p, grid, s);
-    if (rc != GPE_OK) return rc;
-    const long total = (long)p.Mg * p.Ng;
-    const long fin_blocks = gpe_cdiv(total, RD_FIN_E) + (colsum ? gpe_cdiv(p.Mg, RD_FIN_E) : 0);
-    hipLaunchKernelGGL(gpe_redgemm_finish, dim3(fin_blocks), dim3(RD_FIN_E * RD_FIN_Q), 0, s, p.part, p.part_cs, gx,
-                       p.Mg, p.Ng, MgPad, NgPad, G, ldG, colsum, accumulate);
+    const long blocks = gpe_cdiv((long)p.Mg * p.Ng, RD_FIN_E) + (colsum ? gpe_cdiv(p.Mg, RD_FIN_E) : 0);
+    hipLaunchKernelGGL(gpe_redgemm_finish, dim3(blocks), dim3(RD_FIN_E * RD_FIN_Q), 0, s, p.part, p.part_cs, plan.nblk, p.Mg, p.Ng,
+                       plan.MgPad, plan.NgPad, G, ldG, colsum, accumulate);
     GPE_CHECK_LAUNCH();
     return GPE_OK;
+}
+
+// fill the plan, switch on the path, finish
+static int rd_run(RdParams& p, int vmode, float* G, int ldG, float* colsum, float* part, int accumulate, hipStream_t s)
+{
+    const GpeRdPlan plan = gpe_redgemm_plan(p, vmode, colsum != nullptr, g_rd_math, gpe_debug_get(), gpe_rd_switches(), gpe_num_cus());
+    if (plan.path == GPE_RD_NOTHING) return plan.rc;
+    p.vec = plan.vec; p.MgPad = plan.MgPad; p.NgPad = plan.NgPad; p.num_tiles = plan.num_tiles;
+    p.umagic = plan.umagic; p.vmagic = plan.vmagic; p.pin_tpc = plan.pin_tpc;
+    p.part = part;
+    p.part_cs = plan.cs ? reinterpret_cast<double*>(part + plan.cs_off) : nullptr;
+    int rc = GPE_EINVAL;
+    switch (plan.path) {
+    case GPE_RD_THIN: rc = rd_launch_thin(p, plan, s); break;
+    case GPE_RD_X6_TN: rc = gpe_gemm_x6_launch_redgemm(p, plan, s); break;
+    case GPE_RD_DEEP: rc = rd_launch_deep(p, plan, s); break;
+    case GPE_RD_B3_LAZY: rc = rd_launch_b3_lazy(p, plan, s); break;
+    case GPE_RD_B3_F16: rc = rd_launch_b3_f16(p, plan, s); break;
+    case GPE_RD_B3_BF16: rc = rd_launch_b3_bf16(p, plan, s); break;
+    case GPE_RD_PC: rc = rd_launch_pc(p, plan, s); break;
+    case GPE_RD_BIG: rc = rd_launch_big(p, plan, s); break;
+    default: break;
+    }
+    if (rc != GPE_OK) return rc;
+    return rd_finish(p, plan, G, ldG, colsum, accumulate, s);
 }
 
 extern "C" int gpe_redgemm(const float* u, long u_so, long u_si, int u_inner, const float* v, long v_so,

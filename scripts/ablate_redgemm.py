@@ -1,6 +1,10 @@
-"""Profiling aid: the f16x3 edge reduce-GEMM (gpe_redgemm_b3_kernel) at the BASELINE cfg-2 size under the timing-only switches of
-GPE_RD_DBG (1 = no commit, 2 = no row loads, 4 = no consumer MFMAs, 8 = no left-over MFMAs; results are wrong).  One process per
-setting (the switch is read once):  for d in 0 1 2 3 4 8 15; do GPE_RD_DBG=$d python scripts/ablate_redgemm.py; done"""
+"""Profiling aid: the f16x3 edge reduce-GEMM (gpe_redgemm_b3_kernel) at the BASELINE cfg-2 size under the timing-only ablation
+RD_B3_DBG (1 = no commit, 2 = no row loads, 4 = no consumer MFMAs, 8 = no left-over MFMAs; results are wrong).  The ablation is
+compile-time (csrc/gpe_redgemm.hip), so every setting is a library of its own, built through scripts/ab_build.sh with the file's
+own extra flags, and one process per library:
+  scripts/ab_build.sh gpe_redgemm.hip d0 "-mllvm -amdgpu-sched-strategy=max-memory-clause" \
+      d4 "-mllvm -amdgpu-sched-strategy=max-memory-clause -DRD_B3_DBG=4" ...
+  for d in d0 d4; do GPE_HIP_LIB=build/ab/lib_$d.so python scripts/ablate_redgemm.py; done"""
 import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -50,4 +54,4 @@ def rd():   # dense V: G2 = dz3^T a2
            None, 0, None, None, 0, None)
 
 
-print('GPE_RD_DBG=%s  gathered 13x13: %.0f us   dense 10x13: %.0f us' % (os.environ.get('GPE_RD_DBG', '0'), timeit(rg), timeit(rd)))
+print('%s  gathered 13x13: %.0f us   dense 10x13: %.0f us' % (os.environ.get('GPE_HIP_LIB', 'the in-tree library (RD_B3_DBG=0)'), timeit(rg), timeit(rd)))

@@ -376,7 +376,10 @@ def test_linear_strided_addend_act(gpe):
 
 
 @pytest.mark.parametrize('rows,Mg,Ng', [(1000, 150, 200), (77, 8, 250), (5000, 1000, 250), (4096, 400, 3),
-                                        (300, 23, 153), (65536, 400, 152), (10304, 1000, 252), (40000, 200, 7)])
+                                        (300, 23, 153), (65536, 400, 152), (10304, 1000, 252), (40000, 200, 7),
+                                        # the neighbours of the thin rung (csrc/gpe_redgemm_plan.h: Ng <= 4, Mg <= 1024, rows >= 4096):
+                                        # a row short and a column over, which go on down the ladder; its <2> and <4> instances
+                                        (4095, 400, 3), (4096, 1025, 4), (4096, 300, 4), (4096, 1000, 4)])
 def test_redgemm(gpe, rows, Mg, Ng):
     ops = gpe.ops
     g = torch.Generator().manual_seed(rows + Mg)
@@ -435,6 +438,20 @@ def test_redgemm_thin(gpe, rows, Mg, Ng, pitch):
     G, cs = ops.redgemm_raw(ops._rows2d(u), ops._rows2d(v), rows, Mg, Ng, v_shift=shift)
     assert relerr(G, u.double().t() @ (v.double() - shift.double())) < 3e-6
     assert relerr(cs, u.double().sum(0)) < 3e-6
+
+
+def test_redgemm_thin_without_colsum(gpe):
+    """the streaming kernel when the caller wants no column sum: it gets no fp64 section of the partial image and writes none."""
+    ops = gpe.ops
+    rows, Mg, Ng = 4099, 37, 2
+    g = torch.Generator().manual_seed(rows + Mg + Ng)
+    ubuf = torch.full((rows, 40), float('nan')).cuda()
+    ubuf[:, :Mg] = torch.randn(rows, Mg, generator=g).cuda()
+    u = ubuf[:, :Mg]
+    v = torch.randn(rows, Ng, generator=g).cuda()
+    G, cs = ops.redgemm_raw(ops._rows2d(u), ops._rows2d(v), rows, Mg, Ng, want_colsum=False)
+    assert cs is None
+    assert relerr(G, u.double().t() @ v.double()) < 3e-6
 
 
 def test_redgemm_two_level_rows(gpe):
