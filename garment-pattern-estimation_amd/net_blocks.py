@@ -64,6 +64,38 @@ class DynamicEdgeConv(nn.Module):
         self.last_knn = idx
         return out
 
+    def predict(self, x, n_clouds, n_points, order=None, route='auto'):
+        """forward at prediction time (an addition to the reference's class surface): eval mode, nothing recorded for autograd, and
+        on route 'fused' no per-edge tensor (ops.edge_conv_predict; 'layers' = the kernels of forward, 'auto' chooses).  Sets
+        last_knn / last_order as forward does."""
+        if route not in ops.EDGE_PREDICT_ROUTES:
+            raise ValueError('unknown route %r (choose from %s)' % (route, ops.EDGE_PREDICT_ROUTES))
+        if self.training:
+            raise RuntimeError('DynamicEdgeConv.predict is a prediction path: call .eval() first (BatchNorm running statistics)')
+        nb = len(self.nn)
+        blocks = [self.nn[i] for i in range(nb)]
+        lin = [b[0] for b in blocks]
+        bn = [b[2] for b in blocks]
+        args = []
+        for l, b in zip(lin, bn):
+            args += [l.weight, l.bias, b.weight, b.bias]
+        for b in bn:
+            args += [b.running_mean, b.running_var, b.num_batches_tracked]
+        H0 = lin[0].weight.shape[0]
+        if H0 % 4 or H0 > 256:
+            # a first-block width off the P|Q menu: the general formulation, as in forward
+            if route == 'fused':
+                raise ValueError("route='fused' needs a first-block width <= 256 that is a multiple of 4 (got %d)" % H0)
+            with torch.no_grad():
+                out, idx = ops.edge_conv_general(x.detach(), n_clouds, n_points, self.k, False, bn[0].eps, bn[0].momentum, nb,
+                                                 self.aggr, args)
+            self.last_order = None
+        else:
+            out, idx, self.last_order = ops.edge_conv_predict(x, n_clouds, n_points, self.k, nb, self.aggr, args, order=order,
+                                                              route=route, eps=bn[0].eps)
+        self.last_knn = idx
+        return out
+
 
 class EdgeConvFeatures(nn.Module):
     """nn/net_blocks.py:93-191: defaults, 2x DynamicEdgeConv, optional skip concat, global pool, Linear.
@@ -120,6 +152,40 @@ class EdgeConvFeatures(nn.Module):
         for conv in self.conv_layers:
             conv.register_packs(plan)
         plan.add_linear(self.lin.weight)
+
+    def predict(self, positions, global_pool=True, want_batch=True, route='auto'):
+        """forward at prediction time (an addition to the reference's class surface): the same triple, computed in eval mode without
+        autograd records, every DynamicEdgeConv on its prediction path (route: DynamicEdgeConv.predict)."""
+        if route not in ops.EDGE_PREDICT_ROUTES:
+            raise ValueError('unknown route %r (choose from %s)' % (route, ops.EDGE_PREDICT_ROUTES))
+        if self.training:
+            raise RuntimeError('EdgeConvFeatures.predict is a prediction path: call .eval() first (BatchNorm running statistics)')
+        with torch.no_grad():
+            B, N = positions.size(0), positions.size(1)
+            pos_flat = positions.reshape(-1, positions.size(-1))
+            if pos_flat.dtype != torch.float32:
+                pos_flat = pos_flat.float()
+            pos_flat = pos_flat.contiguous()
+            batch = torch.arange(B, device=positions.device).repeat_interleave(N) if want_batch else None
+            out = pos_flat
+            order = None
+            if self.config['graph_pooling']:
+                for conv, pool in zip(self.conv_layers, self.gpool_layers):
+                    _check_cloud(conv.k, N)
+                    out = conv.predict(out, B, N, order=order, route=route)
+                    out, (_, N) = pool(out, (B, N), order=conv.last_order)      # (the pool's existing forward)
+                if want_batch:
+                    batch = torch.arange(B, device=positions.device).repeat_interleave(N)
+            else:
+                for conv in self.conv_layers:
+                    out = conv.predict(out, B, N, order=order, route=route)
+                    order = conv.last_order
+            if self.config['skip_connections']:
+                out = torch.cat([out, pos_flat], dim=-1)
+            if global_pool:
+                pooled = self.global_pool(out.contiguous() if out.stride(1) != 1 else out, B, N)
+                return ops.linear(pooled, self.lin.weight, self.lin.bias), out, batch
+            return None, out, batch
 
     def forward(self, positions, global_pool=True, want_batch=True):
         B, N = positions.size(0), positions.size(1)

@@ -51,6 +51,22 @@ class BaseModule(nn.Module):
             self.loss.eval()
         return self
 
+    def predict(self, positions_batch, route='auto', **kwargs):
+        """forward's output dict at prediction time (an addition to the reference's class surface; its users call model.eval() and
+        forward under no_grad: nn/evaluation_scripts/predict_per_example.py, on_test_set.py): nothing recorded for autograd, an
+        EdgeConvFeatures encoder on its prediction path (route 'fused' / 'layers' / 'auto': ops.edge_conv_predict), everything
+        behind the encoder on its existing forward kernels."""
+        if route not in ops.EDGE_PREDICT_ROUTES:
+            raise ValueError('unknown route %r (choose from %s)' % (route, ops.EDGE_PREDICT_ROUTES))
+        if self.training:
+            raise RuntimeError('%s.predict is a prediction path: call .eval() first (BatchNorm running statistics)'
+                               % self.__class__.__name__)
+        with torch.no_grad():
+            return self._predict(positions_batch, route, **kwargs)
+
+    def _predict(self, positions_batch, route, **kwargs):
+        return self.forward(positions_batch, **kwargs)
+
 
 # ---- GarmentFullPattern3D: what the reference's constructor fixes (nn/nets.py:49-130), as tables ------------------------------------
 # attribute <- data_config key (nn/nets.py:53-57)
@@ -104,8 +120,11 @@ class GarmentFullPattern3D(BaseModule):
                 n_layers=cfg[name + '_n_layers'], out_len=out_len, dropout=cfg['dropout'], custom_init=cfg['lstm_init']))
         self.placement_decoder = nn.Linear(cfg['panel_encoding_size'], self.rotation_size + self.translation_size)
 
-    def forward_encode(self, positions_batch):
+    def forward_encode(self, positions_batch, route=None):
+        """route (predict only): the EdgeConvFeatures encoder runs its prediction path"""
         if isinstance(self.feature_extractor, blocks.EdgeConvFeatures):
+            if route is not None:
+                return self.feature_extractor.predict(positions_batch, want_batch=False, route=route)[0]
             return self.feature_extractor(positions_batch, want_batch=False)[0]
         return self.feature_extractor(positions_batch)[0]
 
@@ -137,6 +156,10 @@ class GarmentFullPattern3D(BaseModule):
     def forward(self, positions_batch, **kwargs):
         self.refresh_packs()
         return self.forward_decode(self.forward_encode(positions_batch))
+
+    def _predict(self, positions_batch, route, **kwargs):
+        self.refresh_packs()
+        return self.forward_decode(self.forward_encode(positions_batch, route=route))
 
 
 class GarmentSegmentPattern3D(GarmentFullPattern3D):
@@ -170,10 +193,12 @@ class GarmentSegmentPattern3D(GarmentFullPattern3D):
         self.panel_dec_lin = nn.Linear(panel_att_out_size, self.feature_extractor.config['panel_encoding_size'])
         del self.pattern_decoder
 
-    def forward_panel_enc_from_3d(self, positions_batch):
+    def forward_panel_enc_from_3d(self, positions_batch, route=None):
+        """route (predict only): the encoder runs its prediction path"""
         batch_size = positions_batch.shape[0]
         init_pattern_encodings, point_features_flat, batch = self.feature_extractor(
-            positions_batch, not self.config['local_attention'])
+            positions_batch, not self.config['local_attention']) if route is None else self.feature_extractor.predict(
+            positions_batch, not self.config['local_attention'], route=route)
         num_points = point_features_flat.shape[0] // batch_size
         point_features_flat = point_features_flat.contiguous()
         if self.config['local_attention']:
@@ -205,6 +230,15 @@ class GarmentSegmentPattern3D(GarmentFullPattern3D):
         self.refresh_packs()
         batch_size = positions_batch.shape[0]
         panel_encodings, att_weights = self.forward_panel_enc_from_3d(positions_batch)
+        panels = self.forward_panel_decode(panel_encodings.view(-1, panel_encodings.shape[-1]), batch_size)
+        if len(att_weights) > 0:
+            panels.update(att_weights=att_weights)
+        return panels
+
+    def _predict(self, positions_batch, route, **kwargs):
+        self.refresh_packs()
+        batch_size = positions_batch.shape[0]
+        panel_encodings, att_weights = self.forward_panel_enc_from_3d(positions_batch, route=route)
         panels = self.forward_panel_decode(panel_encodings.view(-1, panel_encodings.shape[-1]), batch_size)
         if len(att_weights) > 0:
             panels.update(att_weights=att_weights)

@@ -1083,6 +1083,113 @@ def edge_conv_general(x, B, N, k, training, eps, momentum, nb, aggr, tensors):
 
 
 # -------------------------------------------------------------------------------------------------
+# DynamicEdgeConv at prediction time: one store-free launch per layer (csrc/gpe_edge_predict.hip)
+# -------------------------------------------------------------------------------------------------
+EDGE_PREDICT_ROUTES = ('auto', 'fused', 'layers')
+EDGE_PREDICT_MAX_K, EDGE_PREDICT_MAX_WIDTH, EDGE_PREDICT_MAX_HIDDEN, EDGE_PREDICT_H3_MAX_WIDTH = 64, 256, 3, 224
+_AGGR_CODE = {'max': 0, 'mean': 1, 'add': 2}
+
+
+def _edge_widths_on_menu(shapes, k):
+    """shapes: the (out, in) shapes of the edge MLP's Linears"""
+    nb = len(shapes)
+    if nb < 2 or nb - 2 > EDGE_PREDICT_MAX_HIDDEN or not 1 <= k <= EDGE_PREDICT_MAX_K:
+        return False
+    H, F = shapes[0][0], shapes[-1][0]
+    if H % 4 or not 0 < H <= EDGE_PREDICT_MAX_WIDTH or not 0 < F <= EDGE_PREDICT_MAX_WIDTH:
+        return False
+    return all(tuple(s) == (H, H) for s in shapes[1:-1]) and shapes[-1][1] == H
+
+
+def edge_predict_on_menu(mlp, k):
+    """can csrc/gpe_edge_predict.hip's fused kernel run this edge MLP (net_blocks.MLP([2C, H, .., H, F])) on k neighbours?  (1 <= k <= 64;
+    H <= 256 and a multiple of 4, F <= 256; at most 3 H x H Linears between the first block and the last.)  Pure host logic: the same answer
+    as the library's gpe_edge_predict_ok."""
+    return _edge_widths_on_menu([tuple(mlp[i][0].weight.shape) for i in range(len(mlp))], k)
+
+
+def _edge_predict_h3(H, F, E):
+    """will gpe_edge_predict_fwd run its fp16-pipe kernel?  (the f16x3 mode, widths its LDS budget takes, past the mode's size gate)"""
+    return (L.get_math() == 'f16x3' and H <= EDGE_PREDICT_H3_MAX_WIDTH and F <= EDGE_PREDICT_H3_MAX_WIDTH
+            and E >= L.query('gpe_f16x3_min_rows'))
+
+
+def _edge_predict_auto(H, F, E):
+    """the route 'auto' takes on the menu, per arithmetic (profiles/edge_predict.md): measured at BASELINE cfg 2 and 4
+    the fused kernel is slower than the layer kernels' eval forward in both arithmetics (f32 x 1.14 - 1.24, f16x3 x 1.27 - 1.76 per
+    layer), so 'auto' takes 'layers' in every mode; 'fused' is chosen by name, for its memory (no [E, .] tensor: 147 MB against
+    1649 MB per layer at cfg 2)"""
+    return 'layers'
+
+
+def edge_conv_predict(x, B, N, k, nb, aggr, tensors, order=None, route='auto', eps=1e-5):
+    """One DynamicEdgeConv layer at prediction time (nn/net_blocks.py:43-47,124-135,174 under eval() and no_grad()).
+    x [B*N, C] rows; tensors = the layer's (weight, bias, gamma, beta) x nb + (running_mean, running_var, num_batches_tracked) x nb,
+    as EdgeConvFn takes them.  -> (out [B*N, F], idx int32 [B, N, k], order_out) like EdgeConvFn; nothing is recorded for autograd.
+    route: 'fused' — kNN, the per-point [P|Q] projection, the BatchNorm folds, then ONE launch that forms, transforms and aggregates
+    the k messages of every point in LDS (no [E, .] tensor exists; ValueError off the kernel's menu, edge_predict_on_menu);
+    'layers' — EdgeConvFn.forward with training=False, unchanged; 'auto' — 'fused' on the menu where DESIGN.md 5.34 measured it no slower
+    than the eval forward, 'layers' otherwise: today 'layers' in every arithmetic mode (the fused route is chosen by name, for its
+    memory)."""
+    if route not in EDGE_PREDICT_ROUTES:
+        raise ValueError('unknown route %r (choose from %s)' % (route, EDGE_PREDICT_ROUTES))
+    if aggr not in _AGGR_CODE:
+        raise ValueError("unsupported aggregation '%s'" % aggr)
+    if len(tensors) != 7 * nb or nb < 2:
+        raise ValueError('an edge MLP of nb >= 2 blocks comes as 4 nb parameters + 3 nb buffers (got nb = %d, %d tensors)'
+                         % (nb, len(tensors)))
+    if x.dim() != 2 or x.shape[0] != B * N:
+        raise ValueError('x must be [B*N, C] rows (got %s for B = %d, N = %d)' % (tuple(x.shape), B, N))
+    params, bufs = tensors[:4 * nb], tensors[4 * nb:]
+    Ws = [params[4 * l] for l in range(nb)]
+    if Ws[0].shape[1] != 2 * x.shape[1]:
+        raise ValueError('the first Linear takes %d features per edge, the points have %d' % (Ws[0].shape[1], x.shape[1]))
+    on_menu = _edge_widths_on_menu([tuple(w.shape) for w in Ws], k)
+    H, Fo = Ws[0].shape[0], Ws[-1].shape[0]
+    E = B * N * k
+    if route == 'fused' and not on_menu:
+        raise ValueError("route='fused' needs k <= 64, widths <= 256, a hidden width that is a multiple of 4 and at most 3 equally wide hidden "
+                         "Linears; use 'auto' or 'layers'")
+    if route == 'auto':
+        route = _edge_predict_auto(H, Fo, E) if on_menu else 'layers'
+    _dev_check(x)
+    with torch.no_grad():
+        x = x.detach()
+        if route == 'layers':
+            return EdgeConvFn.apply(x, B, N, k, False, eps, 0.1, nb, aggr, None, order, *tensors)
+        dev = x.device
+        BN, C = x.shape
+        idx, jg, order_out = knn(x, B, N, k, want_global=True, order=order, want_order=True)
+        wpq_p, _, bpq = edge_first_operands(Ws[0], params[1])
+        PQ = torch.empty(BN, 2 * H, device=dev, dtype=F32)
+        linear_raw(_rows2d(x), wpq_p, bpq, BN, 2 * H, C, _rows2d(PQ))
+        # the folded packs of the remaining Linears (the layout of gpe_stitch_pairs_fwd's, include/gpe_hip.h): W^T diag(s) of the
+        # BatchNorm in front, then b + W t; f16x3: their two-term fp16 planes, one power of two per layer (its amax word)
+        nh = nb - 2
+        ldh, ldf = _stitch_ldw(H), _stitch_ldw(Fo)
+        h3 = _edge_predict_h3(H, Fo, E)
+        KP = round_up(H, 32)
+        wpk = torch.zeros(nh * (H + 1) * ldh + (H + 1) * ldf, device=dev, dtype=F32)
+        planes = torch.empty(nh * KP * ldh + KP * ldf, device=dev, dtype=F32) if h3 else None
+        words = torch.empty(nh + 1, device=dev, dtype=torch.int32) if h3 else None
+        st = bn_from_running(bufs[0], bufs[1], params[2], params[3], eps)
+        for l in range(1, nb):
+            W, b = Ws[l], params[4 * l + 1]
+            ld, n_out = (ldh, H) if l < nb - 1 else (ldf, Fo)
+            o = (l - 1) * (H + 1) * ldh
+            L.call('gpe_stitch_pairs_pack', W, W.stride(0), n_out, H, st[2], wpk[o:], ld)
+            L.call('gpe_fold_bias', W, W.stride(0), n_out, H, b, st[3], wpk[o + H * ld:])
+            if h3:
+                L.call('gpe_absmax', wpk[o:], ld, H, ld, words[l - 1:])
+                L.call('gpe_stitch_pairs_planes', wpk[o:], H, ld, words[l - 1:], planes[(l - 1) * KP * ldh:])
+            st = bn_from_running(bufs[3 * l], bufs[3 * l + 1], params[4 * l + 2], params[4 * l + 3], eps)
+        ldF = round_up(Fo, 4)
+        out = torch.empty(BN, ldF, device=dev, dtype=F32)[:, :Fo]
+        L.call('gpe_edge_predict_fwd', PQ, 2 * H, jg, BN, k, H, Fo, nh, wpk, planes, words, st, _AGGR_CODE[aggr], out, ldF)
+        return out, idx, order_out
+
+
+# -------------------------------------------------------------------------------------------------
 # graph pooling (DynamicASAPool)
 # -------------------------------------------------------------------------------------------------
 ASAP_K = 10                        # nn/net_blocks.py:204: DynamicASAPool builds its graph with k = 10 whatever it is given

@@ -674,6 +674,39 @@ int gpe_stitch_eval_finalize(const double* loss_slab, long slots, int group, con
                              const int32_t* stitches, const int32_t* num_stitches, int B, int P, int L, double* loss_sum,
                              int32_t* counts, float* metrics, void* stream);
 
+/* ---- one DynamicEdgeConv layer at prediction time, nothing stored per edge (nn/net_blocks.py:43-47,124-135,174 under eval():
+ * the edge MLP's [Linear -> ReLU -> BatchNorm] blocks on [x_i | x_j - x_i] of the kNN graph and the aggregation over the k messages) -
+ * Added without a version bump (gpe_abi_version() stays 7): one compute entry point and one host-only query, nothing else changes.
+ * The caller owns every byte; the library allocates nothing.
+ * Menu: 1 <= k <= 64; H (the width of every block but the last) <= 256 and a multiple of 4 (the [P|Q] rows are read in quads); F (the
+ * last block's width) 1 .. 256; n_hidden = H -> H Linears between the first block and the last, 0 .. 3 (the edge MLP has n_hidden + 2
+ * blocks).  Anything else returns -22 before any
+ * launch; gpe_edge_predict_ok answers the same question (1 / 0) on the host (its stream argument is ignored).
+ * gpe_edge_predict_fwd, one launch per layer:
+ *   pq [BN][ldpq] fp32 = [P | Q] of the first Linear (2 H columns, 16-B aligned rows, ldpq % 4 == 0; gpe_w1_split + gpe_linear write
+ *   it), message (i, j) starts as relu(P_i + Q_j); jg int32 [BN * k] = global neighbour rows (gpe_knn's idx_global; values are clamped
+ *   to 0 .. BN - 1); BN = B * N point rows, BN * k < 2^31.  A tile of points may span clouds: nothing depends on cloud boundaries.
+ *   wpk (16-B aligned), with nb(W) = the smallest of {4, 8, 13, 16} >= ceil(W / 16) and ldw(W) = 16 nb (+ 16 unless 16 nb % 32 == 16):
+ *     for each hidden layer: Wt [H][ldw(H)] = gpe_stitch_pairs_pack(w, .., col_scale = s of the BatchNorm in front, ldo = ldw(H)), then
+ *       the folded bias (gpe_fold_bias with t of that BatchNorm) in a zero-filled row of ldw(H) floats;
+ *     then the last layer alike: Wt [H][ldw(F)] and its bias row of ldw(F) floats
+ *   = n_hidden * (H + 1) * ldw(H) + (H + 1) * ldw(F) floats.  last_stats [4][F] = gpe_bn_from_running of the last block.
+ *   aggr 0 / 1 / 2 = max / mean / add; out [BN][ldo] fp32 (ldo >= F), with m = the message's last relu output:
+ *     max: s_c >= 0 ? s_c max_j m + t_c : s_c min_j m + t_c (gpe_edge_finish's rule);  mean: s_c (sum_j m / k) + t_c;
+ *     add: s_c sum_j m + k t_c.
+ *   Exact kernel: a workgroup owns floor(64 / k) consecutive point rows and their edge rows on v_mfma_f32_16x16x4_f32; dynamic LDS
+ *   4 * (64 * lda(max(H, F)) + 32 * max(ldw(H), ldw(F))) bytes, lda(W) = (ceil(W / 4) | 1) * 4.
+ *   f16x3 (gpe_math_set(4), H and F <= 224, BN * k >= gpe_f16x3_min_rows(), planes and w_amax given; otherwise the exact kernel): three
+ *   v_mfma_f32_16x16x32_f16 per product on two-term fp16 splits, fp32 accumulate, floor(128 / k) point rows per workgroup; w_amax uint32
+ *   [n_hidden + 1] = amax words of the layers' Wt (gpe_absmax over [H][ldw]), planes = per layer KP * ldw floats written by
+ *   gpe_stitch_pairs_planes (KP = H rounded up to 32), 16-B aligned; the activations are normalised per wave (32 edge rows) and layer by
+ *   the maximum found in the accumulators.  Dynamic LDS max(4 * (128 * (KP + 8) + 32 * max ldw), 4 * 128 * lda(F)) bytes.
+ *   Both may be NULL.  Other modes run the exact kernel.  No atomics, no workgroup waits on another: bit-reproducible. */
+int gpe_edge_predict_ok(int k, int H, int F, int n_hidden, void* stream);
+int gpe_edge_predict_fwd(const float* pq, int ldpq, const int32_t* jg, long BN, int k, int H, int F, int n_hidden, const float* wpk,
+                         const void* planes, const uint32_t* w_amax, const float* last_stats, int aggr, float* out, int ldo,
+                         void* stream);
+
 /* ---- the training loss of the same classifier on a batch of sampled pair rows (nn/metrics/composed_loss.py:83-126 ComposedLoss as
  * StitchOnEdge3DPairs calls it in training) ------------------------------------------------------------------------------------------
  * Added without a version bump (gpe_abi_version() stays 7): two compute entry points, nothing else changes.
