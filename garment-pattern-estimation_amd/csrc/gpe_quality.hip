@@ -8,17 +8,14 @@
 // caller-owned fp64 workspace (panel kernel, stitch kernel), and a single-thread finalise kernel combines them IN PATTERN ORDER,
 // with the reference's own number types per slot (fp32 sums where the reference sums fp32 tensors, fp64 where it sums Python
 // floats), so the result vector is bit-reproducible run to run.  At most three launches per call, no host reads.
-#include "gpe_device.h"
+#include "gpe_stitch_greedy.h"   // QM_TPB (one wave per pattern, both kernels), QM_MAXD, QM_MAXE and the pairing itself
 #include <math.h>
 
 // every product / sum below is rounded on its own, in the reference's order (no contraction into FMAs)
 #pragma clang fp contract(off)
 
-#define QM_TPB 64            // one wave per pattern (both kernels)
 #define QM_MAXP 64           // panels per pattern (shipped: 23)
 #define QM_MAXL 64           // edges per panel (shipped: 14)
-#define QM_MAXD 8            // rotation / translation / stitch-tag width
-#define QM_MAXE 1024         // edges per pattern P*L (shipped: 322)
 #define QM_PART 16           // doubles of workspace per pattern
 
 enum { QM_DISCRETE = 1, QM_SHAPE = 2, QM_ROT = 4, QM_TR = 8, QM_STITCH = 16, QM_FREE = 32, QM_TAG_STATS = 64 };
@@ -169,126 +166,37 @@ __global__ __launch_bounds__(QM_TPB) void gpe_quality_panel_kernel(QmPanelParams
 // stitch detection (greedy pairing of the non-free edges' tags) + precision / recall + free-edge accuracy: one wave per pattern
 // ---------------------------------------------------------------------------------------------------------------------
 struct QmStitchParams {
-    const float* tags; long t_sb, t_sp, t_sl; int D;    // predicted tags (b,p,l,d) at tags + b*t_sb + p*t_sp + l*t_sl + d
-    const float* logit; long m_sb, m_sp, m_sl;          // predicted free-edge logits (b,p,l)
+    QmEdgeViews v;                                      // predicted tags / free-edge logits (gpe_stitch_greedy.h)
     const int64_t* stitches; const int64_t* nums; int S; // ground truth [B][2][S] (after the matchings' re-numbering), [B]
     const float* gt_mask;                               // ground-truth free-edge mask [B,P,L] (1 = free)
     int B, P, L, flags;
 };
 
-__device__ __forceinline__ float qm_dist(const float* T, int i, int j, int D)
-{
-    float s = 0.f;
-    for (int d = 0; d < D; ++d) { const float v = T[i * QM_MAXD + d] - T[j * QM_MAXD + d]; s += v * v; }
-    return sqrtf(s);
-}
-
-// best remaining partner of row r: smallest distance over alive columns c > r, the smallest c on ties (-1: none)
-__device__ __forceinline__ void qm_row_best(const float* T, const unsigned char* alive, int r, int m, int D, float* bd, short* bj)
-{
-    float best = INFINITY;
-    int bc = -1;
-    for (int c = r + 1; c < m; ++c) {
-        if (!alive[c]) continue;
-        const float d = qm_dist(T, r, c, D);
-        if (d < best) { best = d; bc = c; }
-    }
-    bd[r] = best;
-    bj[r] = (short)bc;
-}
-
 __global__ __launch_bounds__(QM_TPB) void gpe_quality_stitch_kernel(QmStitchParams q, QmStats s, double* __restrict__ part)
 {
-    __shared__ float T[QM_MAXE * QM_MAXD];
-    __shared__ short ids[QM_MAXE];          // pattern-level edge id of non-free edge k (edge order)
-    __shared__ float bd[QM_MAXE];
-    __shared__ short bj[QM_MAXE];
-    __shared__ unsigned char alive[QM_MAXE];
-    __shared__ short pa[QM_MAXE / 2], pb[QM_MAXE / 2];
+    __shared__ QmGreedyLds g;
     const int b = blockIdx.x, lane = threadIdx.x;
     const int PL = q.P * q.L;
-    const unsigned long long below = (1ull << lane) - 1ull;
-    // pass 1: decisions, their count, the non-free edge with the largest logit (first on ties), free-edge accuracy
-    int m = 0, nfree_ok = 0;
-    float xmax = -INFINITY;
-    int emax = 0x7fffffff;
-    for (int e0 = 0; e0 < PL; e0 += QM_TPB) {
-        const int e = e0 + lane;
-        bool nonfree = false;
-        if (e < PL) {
-            const int pp = e / q.L, l = e - pp * q.L;
-            const float x = q.logit[b * q.m_sb + pp * q.m_sp + l * q.m_sl];
-            // torch.round(torch.sigmoid(x)) == 0 on the device: gpe_sigmoid (fp32 expf, IEEE division) and round half to even, so exactly
-            // 0.5 is a non-free edge.  NaN rounds to NaN, which is "free" (the reference casts it to True).
-            const float sg = gpe_sigmoid(x);
-            nonfree = sg <= 0.5f;
-            if (q.flags & QM_FREE) {
-                const float cls = sg != sg ? sg : (sg > 0.5f ? 1.f : 0.f);
-                nfree_ok += cls == q.gt_mask[(size_t)b * PL + e];
-            }
-            if (nonfree && (x > xmax || (x == xmax && e < emax))) { xmax = x; emax = e; }
+    // pass 1: decisions, their count, the edge an odd count drops, free-edge accuracy
+    int nfree_ok = 0, drop;
+    int m = qm_count_nonfree(q.v, b, PL, q.L, lane, &drop, [&](int e, float sg) {
+        if (q.flags & QM_FREE) {
+            const float cls = sg != sg ? sg : (sg > 0.5f ? 1.f : 0.f);
+            nfree_ok += cls == q.gt_mask[(size_t)b * PL + e];
         }
-        m += __builtin_popcountll(__ballot(nonfree));
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-        const float xo = __shfl_xor(xmax, o);
-        const int eo = __shfl_xor(emax, o);
-        if (xo > xmax || (xo == xmax && eo < emax)) { xmax = xo; emax = eo; }
-        nfree_ok += __shfl_xor(nfree_ok, o);
-    }
+    });
+    for (int o = 32; o > 0; o >>= 1) nfree_ok += __shfl_xor(nfree_ok, o);
     double* o = part + (size_t)b * QM_PART;
     if (!(q.flags & QM_STITCH) || m < 2) {                   // no stitches: the pattern adds 0 and joins no corr_ list
         if (lane == 0) { o[8] = 0.0; o[9] = 0.0; o[10] = 0.0; o[11] = (double)nfree_ok; }
         return;
     }
-    const int drop = (m & 1) ? emax : -1;                    // odd count: leave out the edge closest to "free"
-    // pass 2: compact the remaining non-free edges in edge order and stage their (un-standardised) tags
-    m = 0;
-    for (int e0 = 0; e0 < PL; e0 += QM_TPB) {
-        const int e = e0 + lane;
-        bool nonfree = false;
-        int pp = 0, l = 0;
-        if (e < PL && e != drop) {
-            pp = e / q.L; l = e - pp * q.L;
-            nonfree = gpe_sigmoid(q.logit[b * q.m_sb + pp * q.m_sp + l * q.m_sl]) <= 0.5f;
-        }
-        const unsigned long long bal = __ballot(nonfree);
-        if (nonfree) {
-            const int k = m + __builtin_popcountll(bal & below);
-            ids[k] = (short)e;
-            alive[k] = 1;
-            const float* t = q.tags + b * q.t_sb + pp * q.t_sp + l * q.t_sl;
-            for (int d = 0; d < q.D; ++d)
-                T[k * QM_MAXD + d] = (q.flags & QM_TAG_STATS) ? t[d] * s.v[QS_TAG_SCALE + d] + s.v[QS_TAG_SHIFT + d] : t[d];
-        }
-        m += __builtin_popcountll(bal);
-    }
-    __syncthreads();
-    for (int r = lane; r < m; r += QM_TPB) qm_row_best(T, alive, r, m, q.D, bd, bj);
-    __syncthreads();
-    // greedy rounds: the global minimum over (row, best column), ties to the smallest row (row-major argmin of the
-    // reference's upper-triangular matrix); then only the rows whose best partner was just taken are re-scanned
-    int npairs = 0;
-    for (int round = 0; round < m / 2; ++round) {
-        float dmin = INFINITY;
-        int rmin = 0x7fffffff;
-        for (int r = lane; r < m; r += QM_TPB)
-            if (alive[r] && bj[r] >= 0 && bd[r] < dmin) { dmin = bd[r]; rmin = r; }
-        for (int sh = 32; sh > 0; sh >>= 1) {
-            const float dq = __shfl_xor(dmin, sh);
-            const int rq = __shfl_xor(rmin, sh);
-            if (dq < dmin || (dq == dmin && rq < rmin)) { dmin = dq; rmin = rq; }
-        }
-        if (rmin == 0x7fffffff) break;                       // only non-finite distances left (NaN / inf tags)
-        const int cmin = bj[rmin];
-        __syncthreads();
-        if (lane == 0) { pa[npairs] = ids[rmin]; pb[npairs] = ids[cmin]; alive[rmin] = 0; alive[cmin] = 0; }
-        ++npairs;
-        __syncthreads();
-        for (int r = lane; r < m; r += QM_TPB)
-            if (alive[r] && (bj[r] == rmin || bj[r] == cmin)) qm_row_best(T, alive, r, m, q.D, bd, bj);
-        __syncthreads();
-    }
+    // pass 2 and the greedy rounds (gpe_stitch_greedy.h)
+    const bool ts = q.flags & QM_TAG_STATS;
+    m = qm_stage_tags(q.v, b, PL, q.L, lane, drop, ts ? s.v + QS_TAG_SHIFT : nullptr, ts ? s.v + QS_TAG_SCALE : nullptr, g);
+    const int npairs = qm_greedy_rounds(m, q.v.D, lane, g);
+    const short* pa = g.pa;
+    const short* pb = g.pb;
     // scoring: a detected pair is correct if it equals a ground-truth stitch in either order (each counted once)
     long n = q.nums[b];
     const int ncmp = (int)(n < 0 ? 0 : (n > q.S ? q.S : n));
@@ -399,7 +307,7 @@ extern "C" int gpe_quality_stitches(const float* tags, long t_sb, long t_sp, lon
     if ((flags & QM_FREE) && !gt_mask) return GPE_EINVAL;
     QmStats s;
     if (qm_stats(stats_host, &s) != GPE_OK) return GPE_EINVAL;
-    QmStitchParams q{tags, t_sb, t_sp, t_sl, D, logit, m_sb, m_sp, m_sl, stitches, nums, S, gt_mask, B, P, L, flags};
+    QmStitchParams q{{tags, t_sb, t_sp, t_sl, D, logit, m_sb, m_sp, m_sl}, stitches, nums, S, gt_mask, B, P, L, flags};
     hipLaunchKernelGGL(gpe_quality_stitch_kernel, dim3(B), dim3(QM_TPB), 0, (hipStream_t)stream, q, s, part);
     GPE_CHECK_LAUNCH();
     return GPE_OK;

@@ -7,6 +7,7 @@ import torch.nn as nn
 from . import net_blocks as blocks
 from . import ops
 from .metrics import ComposedLoss, ComposedPatternLoss
+from .patterns import DecodedPatterns
 
 
 class BaseModule(nn.Module):
@@ -67,6 +68,20 @@ class BaseModule(nn.Module):
     def _predict(self, positions_batch, route, **kwargs):
         return self.forward(positions_batch, **kwargs)
 
+    def predict_pattern(self, positions_batch, data_config, route='auto', stitches=None):
+        """predict, then the step the reference runs on every prediction (Garment3DPatternFullDataset._pred_to_pattern,
+        nn/data/datasets.py:731-767) on the device: ops.pattern_decode with data_config['standardize'] and
+        data_config['explicit_stitch_tags'].  `stitches` [B,2,S] replace the pairing of the predicted stitch tags ("if somehow
+        prediction already has an answer", :745).  -> patterns.DecodedPatterns; no host read before its as_spec / to_json."""
+        if not self._predicts_patterns:
+            raise NotImplementedError('%s.predict_pattern: the model predicts no panels (its stitches come from predict_stitches)'
+                                      % self.__class__.__name__)
+        preds = self.predict(positions_batch, route=route)
+        return DecodedPatterns(ops.pattern_decode(preds, data_config['standardize'],
+                                                  bool(data_config.get('explicit_stitch_tags', False)), stitches=stitches))
+
+    _predicts_patterns = False
+
 
 # ---- GarmentFullPattern3D: what the reference's constructor fixes (nn/nets.py:49-130), as tables ------------------------------------
 # attribute <- data_config key (nn/nets.py:53-57)
@@ -88,6 +103,7 @@ _LOSS_DEFAULTS = {'loss_components': ['shape', 'loop', 'rotation', 'translation'
 
 class GarmentFullPattern3D(BaseModule):
     """nn/nets.py:41-184: EdgeConv encoder -> pattern LSTM -> panel LSTM + placement Linear."""
+    _predicts_patterns = True
 
     def __init__(self, data_config, config={}, in_loss_config={}):
         super().__init__()

@@ -2465,6 +2465,109 @@ def quality_metrics(flags, stats, B, P, Lp, outlines=None, gt_outlines=None, num
     return out, counts
 
 
+# -------------------------------------------------------------------------------------------------
+# a prediction decoded to a sewing pattern (csrc/gpe_pattern_decode.hip)
+# -------------------------------------------------------------------------------------------------
+PATTERN_DECODE_KEYS = ('num_edges', 'edge_slot', 'num_verts', 'closed', 'new_panel_id', 'num_panels', 'vertices', 'curvature',
+                       'rotations', 'translations', 'curved', 'stitches', 'num_stitches', 'stitch_flags', 'first_invalid')
+PATTERN_MAX_EDGES, PATTERN_MAX_WIDTH = 1024, 8          # include/gpe_hip.h gpe_pattern_decode: P * L, and R / T / D
+
+
+def _pattern_decode_stats(data_stats, widths, explicit_stitch_tags):
+    """the 64-double host array `stats_host` of gpe_pattern_decode from data_config['standardize'] (Python floats are doubles: the
+    statistics reach the kernel as the reference's numpy sees them)"""
+    import ctypes
+    v = [0.0] * 64
+    for base, key in ((0, 'outlines'), (16, 'rotations'), (32, 'translations'), (48, 'stitch_tags')):
+        if key == 'stitch_tags' and not explicit_stitch_tags:
+            continue
+        sh = [float(x) for x in data_stats['gt_shift'][key]]
+        sc = [float(x) for x in data_stats['gt_scale'][key]]
+        if len(sh) != widths[key] or len(sc) != widths[key]:
+            raise ValueError('pattern_decode: %d statistics for %r of width %d' % (len(sh), key, widths[key]))
+        v[base:base + len(sh)], v[base + 8:base + 8 + len(sc)] = sh, sc
+    return (ctypes.c_double * 64)(*v)
+
+
+def _edge_views(stitch_tags, free_edges_mask, name):
+    """checks of the tag / logit views shared by pattern_decode and tags_to_stitches -> (B, P, L, D)"""
+    _dev_check(stitch_tags)
+    _dev_check(free_edges_mask)
+    if stitch_tags.dim() != 4 or free_edges_mask.shape != stitch_tags.shape[:3]:
+        raise ValueError('%s: stitch_tags [B,P,L,D] and free_edges_mask [B,P,L] expected (got %s, %s)'
+                         % (name, tuple(stitch_tags.shape), tuple(free_edges_mask.shape)))
+    B, P, Lp, D = stitch_tags.shape
+    if not (1 <= P * Lp <= PATTERN_MAX_EDGES) or not (1 <= D <= PATTERN_MAX_WIDTH) or B < 1:
+        raise ValueError('%s: 1 <= P * L <= %d edge slots and a tag width of 1 .. %d are supported (got P = %d, L = %d, D = %d)'
+                         % (name, PATTERN_MAX_EDGES, PATTERN_MAX_WIDTH, P, Lp, D))
+    return B, P, Lp, D
+
+
+def tags_to_stitches(stitch_tags, free_edges_mask):
+    """Garment3DPatternFullDataset.tags_to_stitches (nn/data/datasets.py:917-968) for a batch, one launch, no host read:
+    stitch_tags [B,P,L,D] and the free-edge logits [B,P,L] (strided views are fine) -> (stitches int32 [B,2,S] of pattern-level
+    edge ids in the order the reference appends them, zero tails; num_stitches int32 [B]) with S = P * L // 2."""
+    B, P, Lp, D = _edge_views(stitch_tags, free_edges_mask, 'tags_to_stitches')
+    tags, lg = stitch_tags.detach(), free_edges_mask.detach()
+    dev = tags.device
+    S = P * Lp // 2
+    stitches = torch.empty(B, 2, S, device=dev, dtype=torch.int32)
+    nums = torch.empty(B, device=dev, dtype=torch.int32)
+    L.call('gpe_tags_to_stitches', tags, *_view_strides(tags), D, lg, lg.stride(0), lg.stride(1), lg.stride(2), B, P, Lp,
+           stitches if S else None, nums)
+    return stitches, nums
+
+
+def pattern_decode(preds, data_stats, explicit_stitch_tags=False, stitches=None, num_stitches=None):
+    """Garment3DPatternFullDataset._pred_to_pattern (nn/data/datasets.py:731-767) up to the pattern's numbers, for a batch, one launch,
+    no host read: un-standardise in fp64, drop padding rows and empty panels, walk the edge loops to vertices, pair the stitch tags
+    (or take `stitches` [B,2,S'] with optional `num_stitches` [B], any integer dtype, instead) and check every stitch against the
+    panels it names.  `preds` is a model's output dict (strided views are fine), `data_stats` is data_config['standardize'].
+    -> dict of device tensors, PATTERN_DECODE_KEYS (layouts: include/gpe_hip.h gpe_pattern_decode)."""
+    ol, rot, tr = preds['outlines'].detach(), preds['rotations'].detach(), preds['translations'].detach()
+    for t in (ol, rot, tr):
+        _dev_check(t)
+    if ol.dim() != 4 or ol.shape[3] != 4:
+        raise ValueError('pattern_decode: outlines [B,P,L,4] expected (got %s)' % (tuple(ol.shape),))
+    B, P, Lp = ol.shape[:3]
+    R, T = rot.shape[-1], tr.shape[-1]
+    if not (1 <= P * Lp <= PATTERN_MAX_EDGES) or not (1 <= R <= PATTERN_MAX_WIDTH) or not (1 <= T <= PATTERN_MAX_WIDTH) or B < 1:
+        raise ValueError('pattern_decode: 1 <= P * L <= %d edge slots and rotation / translation widths of 1 .. %d are supported '
+                         '(got P = %d, L = %d, R = %d, T = %d)' % (PATTERN_MAX_EDGES, PATTERN_MAX_WIDTH, P, Lp, R, T))
+    dev = ol.device
+    widths = {'outlines': 4, 'rotations': R, 'translations': T}
+    if stitches is None:
+        tags, lg = preds['stitch_tags'].detach(), preds['free_edges_mask'].detach()
+        if _edge_views(tags, lg, 'pattern_decode')[:3] != (B, P, Lp):
+            raise ValueError('pattern_decode: stitch_tags %s do not match outlines %s' % (tuple(tags.shape), tuple(ol.shape)))
+        widths['stitch_tags'] = tags.shape[3]
+        t_args = (tags, *_view_strides(tags), tags.shape[3], lg, lg.stride(0), lg.stride(1), lg.stride(2), None, None)
+        S = P * Lp // 2
+    else:
+        if not stitches.is_cuda:
+            raise RuntimeError('gpe ops need tensors on the MI355X (got %s stitches); there is no CPU path' % stitches.device)
+        if stitches.dim() != 3 or stitches.shape[0] != B or stitches.shape[1] != 2 or stitches.shape[2] < 1 or \
+                stitches.dtype.is_floating_point:
+            raise ValueError('pattern_decode: stitches of integer dtype [B,2,S >= 1] expected (got %s %s)'
+                             % (stitches.dtype, tuple(stitches.shape)))
+        S = stitches.shape[2]
+        given = stitches.to(torch.int32).contiguous()
+        nums = num_stitches.to(dev).reshape(B).to(torch.int32).contiguous() if num_stitches is not None else None
+        explicit_stitch_tags = False
+        t_args = (None, 0, 0, 0, 0, None, 0, 0, 0, given, nums)
+    stats = _pattern_decode_stats(data_stats, widths, explicit_stitch_tags)
+    i32 = lambda *shape: torch.empty(*shape, device=dev, dtype=torch.int32)                       # noqa: E731
+    f64 = lambda *shape: torch.empty(*shape, device=dev, dtype=torch.float64)                     # noqa: E731
+    o = {'num_edges': i32(B, P), 'edge_slot': i32(B, P, Lp), 'num_verts': i32(B, P), 'closed': i32(B, P), 'new_panel_id': i32(B, P),
+         'num_panels': i32(B), 'vertices': f64(B, P, Lp + 1, 2), 'curvature': f64(B, P, Lp, 2), 'rotations': f64(B, P, R),
+         'translations': f64(B, P, T), 'curved': i32(B, P, Lp), 'stitches': i32(B, 2, S), 'num_stitches': i32(B),
+         'stitch_flags': i32(B, S), 'first_invalid': i32(B)}
+    L.call('gpe_pattern_decode', ol, *_view_strides(ol), rot, _row_stride(rot, P), R, tr, _row_stride(tr, P), T, *t_args,
+           B, P, Lp, S, 1 if explicit_stitch_tags else 0, stats,
+           *[o[k] if o[k].numel() else None for k in PATTERN_DECODE_KEYS])
+    return o
+
+
 def standardize(x, shift, scale):
     """nn/data/transforms.py:35-50 FeatureStandartization on the device: (x - shift) / scale per column."""
     import ctypes

@@ -543,6 +543,43 @@ int gpe_quality_stitches(const float* tags, long t_sb, long t_sp, long t_sl, int
                          int L, int flags, const float* stats_host, double* part, void* stream);
 int gpe_quality_finalize(const double* part, int B, int P, int L, int flags, float* out, int32_t* counts, void* stream);
 
+/* ---- a prediction decoded to a sewing pattern (Garment3DPatternFullDataset._pred_to_pattern, nn/data/datasets.py:731-767;
+ * tags_to_stitches :917-968; NNSewingPattern.pattern_from_tensors / panel_from_numeric / _edge_dict,
+ * nn/data/pattern_converter.py:118-187, 228-271, 510-515) ----------------------------------------------------------------
+ * Added without a version bump (gpe_abi_version() stays 7): two compute entry points, nothing else changes.  All memory is the
+ * caller's; the library keeps no state.  One launch of B workgroups (one wave each), no atomics: bit-reproducible.
+ * Inputs: outlines / rotation / translation rows as gpe_quality_panels, tags / logits as gpe_quality_stitches (the strided
+ * views of the decoders' output).  stats_host: HOST array of 64 doubles, eight per group — [0:8] outline shift, [8:16] outline
+ * scale, [16:24] rotation shift, [24:32] its scale, [32:40] translation shift, [40:48] its scale, [48:56] stitch-tag shift,
+ * [56:64] its scale.  Every outline, rotation and translation value is un-standardised as fp64 (double)x * scale, then + shift,
+ * each rounded (numpy on float64).  flags: 1 = un-standardise the stitch tags too (fp32, as gpe_quality_stitches flag 64).
+ * given: int32 [B][2][S] caller's stitches (edge ids panel * L + edge) that replace the tag pairing, given_num int32 [B] how many
+ * of the S entries count (NULL: all); given == NULL pairs the tags (tags_to_stitches: greedy by global minimum distance, ties to the
+ * smallest (row, column); an odd count of non-free edges drops the one with the largest logit) and needs S == P * L / 2.
+ * Menu: 1 <= P * L <= 1024, R, T, D in 1 .. 8; anything else returns -22 before any launch.
+ * Panel (b,p): a row is kept unless all four values are within 1.5 of 0 (NaN / inf keep it); fewer than 3 kept rows = empty panel
+ * (num_edges 0, num_verts 0, new_panel_id -1).  Else vertex 0 = origin, vertex k + 1 = vertex k + kept edge k's first two values
+ * (sequential fp64 sums); closed = the end of the last edge is within 3 of 0 in both coordinates, then the last edge ends at vertex
+ * 0 and num_verts = num_edges, else num_verts = num_edges + 1.  Kept edge k: edge_slot = its row, curvature = its last two values,
+ * curved = not both within 0.01 of 0.
+ * Outputs: num_edges, num_verts, closed, new_panel_id (rank among the non-empty panels) int32 [B][P]; edge_slot, curved int32
+ * [B][P][L]; num_panels int32 [B]; vertices fp64 [B][P][L + 1][2]; curvature fp64 [B][P][L][2]; rotations fp64 [B][P][R];
+ * translations fp64 [B][P][T] (the universal translation, passed through); stitches int32 [B][2][S] in the order found (given:
+ * the non-(0, 0) entries in order); num_stitches, first_invalid int32 [B]; stitch_flags int32 [B][S]: bit 0 = an id names a panel
+ * >= P or an empty one (first_invalid = the first such stitch, -1: none), bit 1 = an id names a row that was dropped (the reference
+ * does not notice).  The reported edge of an id is id % L, the row, not the kept-edge index.  Tails are written: -1 (edge_slot) or 0.
+ * gpe_tags_to_stitches: the pairing alone, tags as they are (the reference's static method, batched): stitches int32 [B][2][S] with
+ * S = P * L / 2 in the order taken, zero tails; num_stitches int32 [B].  Same menu, same kernel code (csrc/gpe_stitch_greedy.h). */
+int gpe_tags_to_stitches(const float* tags, long t_sb, long t_sp, long t_sl, int D, const float* logit, long m_sb, long m_sp,
+                         long m_sl, int B, int P, int L, int32_t* stitches, int32_t* num_stitches, void* stream);
+int gpe_pattern_decode(const float* ol, long ol_sb, long ol_sp, long ol_sl, const float* rot, long rot_s, int R, const float* tr,
+                       long tr_s, int T, const float* tags, long t_sb, long t_sp, long t_sl, int D, const float* logit, long m_sb,
+                       long m_sp, long m_sl, const int32_t* given, const int32_t* given_num, int B, int P, int L, int S, int flags,
+                       const double* stats_host, int32_t* num_edges, int32_t* edge_slot, int32_t* num_verts, int32_t* closed,
+                       int32_t* new_panel_id, int32_t* num_panels, double* vertices, double* curvature, double* rotations,
+                       double* translations, int32_t* curved, int32_t* stitches, int32_t* num_stitches, int32_t* stitch_flags,
+                       int32_t* first_invalid, void* stream);
+
 /* ---- graph pooling: DynamicASAPool = PyG ASAPooling on the kNN graph of the node features (nn/net_blocks.py:194-218, used by
  * EdgeConvFeatures with graph_pooling (:113-118, :138-142, :172-176) and EdgeConvPoolingFeatures (:221-268)) -------------------
  * Added without a version bump (gpe_abi_version() stays 7): two compute entry points, nothing else changes.
