@@ -1,6 +1,8 @@
-"""ctypes binding of libgpe_hip.so (C ABI: include/gpe_hip.h).  Signatures are parsed from the header itself, so
-the binding cannot drift from the declared ABI.  There is NO fallback: if the HIP library is missing or a call
-fails, this raises — the product path never routes around the kernels."""
+"""ctypes binding of libgpe_hip.so (C ABI: include/gpe_hip.h).  The header is the one description of the ABI and both
+sides are checked against it: the signatures here are parsed from it (parse_header; a declaration it cannot bind raises,
+and lib() fails on a declared symbol the library does not export), and every definition in csrc/ is compiled with it
+included (csrc/gpe_common.h), so a definition that differs from its declaration does not compile.  There is NO fallback:
+if the HIP library is missing or a call fails, this raises — the product path never routes around the kernels."""
 import ctypes
 import os
 import re
@@ -24,7 +26,9 @@ def _code(ctype):
 
 
 def parse_header(path=HEADER_PATH):
-    """-> {symbol: (restype code, [arg codes])} for every function declared in include/gpe_hip.h"""
+    """-> {symbol: (restype code, [arg codes])} for every function declared in include/gpe_hip.h.  A gpe_* declaration this
+    parser cannot bind (a return type other than int / long, say) raises ValueError: left unbound, ctypes would call it with
+    its default types."""
     src = open(path).read()
     src = re.sub(r'/\*.*?\*/', ' ', src, flags=re.S)
     src = re.sub(r'//[^\n]*', ' ', src)
@@ -38,6 +42,10 @@ def parse_header(path=HEADER_PATH):
                 ctype = a[:a.rfind(' ')] if '*' not in a else a[:a.rfind('*') + 1]
                 codes.append(_code(ctype))
         sigs[name] = (_code(res), codes)
+    unbound = sorted(set(re.findall(r'\b(gpe_\w+)\s*\(', src)) - set(sigs))
+    if unbound:
+        raise ValueError('%s: cannot bind the declaration of %s (only functions returning int or long are parsed)'
+                         % (path, ', '.join(unbound)))
     return sigs
 
 

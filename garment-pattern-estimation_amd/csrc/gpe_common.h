@@ -3,6 +3,9 @@
 #include <cstdlib>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+// the C ABI itself: every translation unit sees the declarations, so an extern "C" definition whose parameters differ from
+// the header Python binds from is a compile error ("conflicting types"), not a silently mis-called symbol
+#include "../../include/gpe_hip.h"
 
 #define GPE_OK 0
 #define GPE_EINVAL (-22)
@@ -97,8 +100,14 @@ __device__ __forceinline__ unsigned gpe_udiv(unsigned n, unsigned d, double rcp)
 // kernels with static __shared__ arrays must leave room for them below the 160 KB of a CU
 #define GPE_ENSURE_MAX_LDS(fn) GPE_ENSURE_MAX_LDS_N(fn, 160 * 1024)
 
-// compute units of the CURRENT device (cached per device ordinal); defined in gpe_pointwise.hip
+// ---- process state (gpe_state.hip: the arithmetic mode, the debug mask, the f16x3 size gate, the CU reservation) ------------------
+// compute units of the CURRENT device (cached per device ordinal) less the caller's reservation
 int gpe_num_cus();
+// the arithmetic mode (gpe_math_get) as the two kernel families read it:
+//   row GEMMs (gpe_edgegemm_try)     0 exact fp32 MFMA, 1 bf16x3, 2 bf16x6 where it fits, 3 f16x3
+//   reduce-GEMM (gpe_redgemm.hip)    0 exact fp32 MFMA, 1 bf16x3, 2 f16x3 where the operand scales are known
+int gpe_math_rowgemm();
+int gpe_math_redgemm();
 // ---- caller-owned workspace of the edge entry points (gpe_edge_mlp_fwd / _bwd / gpe_edge_redgemm / gpe_edge_pq_amax) -----------
 // The library allocates nothing: a caller passes `ws` of gpe_edge_ws_bytes(...) bytes (16-B aligned) and the entry point carves
 //   [0, GPE_WS_DUMMY_BYTES)   the dummy store image of the straight-line edge kernels (64 rows x 512 floats; written, never read)
@@ -131,7 +140,7 @@ int gpe_h3_pq_passes(unsigned* out, float* part, const float* pq, long rows, int
 // largest |x| over [rows][cols] (pitch ld) -> out[0] (cleared first, on the stream)
 int gpe_h3_absmax(unsigned* out, const float* x, long rows, int cols, long ld, hipStream_t s);
 // rows below which the f16x3 kernels are not used (their scale passes cost more than they save at small E); part of the
-// arithmetic mode: gpe_f16x3_min_rows_set (gpe_rowgemm.hip)
+// arithmetic mode: gpe_f16x3_min_rows_set (gpe_state.hip)
 #define GPE_H3_MIN_ROWS_DEFAULT 32768
 long gpe_h3_min_rows();
 // power of two that brings a tensor whose largest magnitude has the bit pattern `amax` into [2^14, 2^15), and its inverse.

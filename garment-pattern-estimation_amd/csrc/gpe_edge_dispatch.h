@@ -15,6 +15,10 @@
 #define GPE_EDGE_LAUNCHED 1
 #define GPE_EDGE_NOT_MINE 0
 
+// ---- the register-stationary fast path of the edge entry points (gpe_rowgemm.hip) for the shipped edge-MLP sizes: launched, or
+// not on any family's menu (the caller runs the generic LDS-streamed kernel), or an error
+int gpe_edgegemm_try(const RgParams& p, int amode, int emode, int stats_nblk, hipStream_t s);
+
 // ---- the register-stationary menu -------------------------------------------------------------------------------------------
 // widths (96, 208]: 10 or 13 tiles of 16 columns / chunks of 16 k
 static inline bool gpe_edge_width_ok(int c) { return c > 96 && c <= 208; }
@@ -50,6 +54,8 @@ int gpe_edge_finish(int rc, const RgParams& p, const GpeFold& fold, hipStream_t 
 // ---- the families: `p` is the re-tiled copy (gpe_edge_pc: the caller's own) ---------------------------------------------------
 int gpe_edge_pc(const RgParams& p, int amode, int emode, int NT, int KCH, int bf16x3, int stats_nblk, hipStream_t s);
 int gpe_edge_sr(const RgParams& p, int amode, int emode, int NT, int KCH, int stats_nblk, hipStream_t s);
+// ... its dense-A variants (gpe_edgegemm_sr_dense.hip: compiled with another scheduling strategy)
+int gpe_edge_sr_dense(const RgParams& p, int amode, int emode, int NT, int KCH, int stats_nblk, hipStream_t s);
 int gpe_edge_bf16x6(const RgParams& p, int amode, int emode, int NT, int KCH, int stats_nblk, hipStream_t s);
 // the scale passes of the f16x3 families: fills p.h3_amax_a / h3_amax_w / amax_out; GPE_OK or an error
 int gpe_edge_f16x3_scales(RgParams& p, long npts, int amode, int emode, int KCH, hipStream_t s);

@@ -2,9 +2,6 @@
 // single-role families share.  Host code only; the pieces are declared in gpe_edge_dispatch.h.
 #include "gpe_edge_dispatch.h"
 
-static int g_eg_math = 0;            // 0: exact fp32 MFMA, 1: bf16x3, 2: bf16x6 where it fits, 3: f16x3 (gpe_math_set)
-void gpe_edgegemm_set_math(int m) { g_eg_math = m; }
-
 // ---- k > 16: pseudo-points ------------------------------------------------------------------------------------------------------
 // A point with k > 16 neighbours is processed as f pseudo-points of kq = k / f rows (kq <= 16, so every wave still owns whole
 // pseudo-points): the divisor of k that fills most of a wave's 16 rows, the largest such on a tie.
@@ -94,7 +91,7 @@ int gpe_edgegemm_try(const RgParams& p, int amode, int emode, int stats_nblk, hi
     // (r02: a "forward-only bf16x3" mode was measured and dropped — 1785 garments/s, but first-layer weight gradients are
     // residuals of cancelling sums that amplify ANY 1e-5 perturbation of the stored activations ~1e3 times (1.5e-2 of
     // max|grad|): nothing short of ~24-bit operands is parity-grade, forward or backward.)
-    const int math = g_eg_math;
+    const int math = gpe_math_rowgemm();                 // 0: exact fp32 MFMA, 1: bf16x3, 2: bf16x6 where it fits, 3: f16x3
     // fp16 activation rows / a lazily formed dz3 exist only in the f16x3 kernels: no other kernel may touch such buffers
     const bool f16_only = p.out_half || p.lz_g;
     if (!gpe_edge_on_menu(p, amode, emode)) return f16_only ? GPE_EINVAL : GPE_EDGE_NOT_MINE;

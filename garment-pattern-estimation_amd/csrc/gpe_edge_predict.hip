@@ -366,8 +366,6 @@ __global__ __launch_bounds__(EP_TPB) void gpe_edge_predict_h3_kernel(EpParams p)
 }
 
 // ---- C ABI -------------------------------------------------------------------------------------------------------------------------
-extern "C" int gpe_math_get(void);
-
 static inline size_t ep_lds_f32(int H, int F)
 {
     return (size_t)(EP_R * ep_lda(max(H, F)) + EP_KS * max(ep_ldw(H), ep_ldw(F))) * sizeof(float);

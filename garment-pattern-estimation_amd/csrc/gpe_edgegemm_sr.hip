@@ -21,9 +21,6 @@
 // LDS: A[2] + C (159 KB at the shipped sizes), two barriers per tile.
 #include "gpe_edgegemm_sr_kernel.h"
 
-// dense-A variants live in gpe_edgegemm_sr_dense.hip (compiled with another scheduling strategy)
-int gpe_edge_sr_dense(const RgParams& p, int amode, int emode, int NT, int KCH, int stats_nblk, hipStream_t s);
-
 // ---- k > 16: merging the per-pseudo-point results ------------------------------------------------------------------------
 // A point with k > 16 neighbours is processed as f pseudo-points of kq = k / f rows (kq <= 16, so every wave still owns whole
 // pseudo-points).  The kernels then write one max / min / argmax / argmin row, or one dP row, per PSEUDO-point into a scratch

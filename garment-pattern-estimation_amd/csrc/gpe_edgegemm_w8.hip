@@ -19,9 +19,6 @@
 //   single-role kernel (round 4)    443   462   524   499
 #include "gpe_edgegemm_w8_kernel.h"
 
-int gpe_w8_select_k5(const RgParams& p, int amode, int emode, int NT, int KCH, int stats_nblk, hipStream_t s);   // gpe_edgegemm_w8_k5.hip
-int gpe_w8_select_k4(const RgParams& p, int amode, int emode, int NT, int KCH, int stats_nblk, hipStream_t s);   // gpe_edgegemm_w8_k4.hip
-
 static int w8_enabled(int kind)
 {
     static int tab[4] = {-1, 0, 0, 0};

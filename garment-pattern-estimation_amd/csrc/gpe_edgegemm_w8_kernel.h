@@ -787,6 +787,9 @@ struct W8Menu {
 // their fp16-row / lazy-dz3 variants
 int gpe_w8_launch_f3(const RgParams& p, int stats_nblk, hipStream_t s);     // gpe_edgegemm_w8_f3.hip
 int gpe_w8_launch_b3(const RgParams& p, int stats_nblk, hipStream_t s);     // gpe_edgegemm_w8_b3.hip
+// k = 5 and the four-row (pseudo-)points: w8_select<5> / <4> below, each from its own translation unit, for gpe_edge_w8
+int gpe_w8_select_k5(const RgParams& p, int amode, int emode, int NT, int KCH, int stats_nblk, hipStream_t s);   // gpe_edgegemm_w8_k5.hip
+int gpe_w8_select_k4(const RgParams& p, int amode, int emode, int NT, int KCH, int stats_nblk, hipStream_t s);   // gpe_edgegemm_w8_k4.hip
 
 // ... for KK rows per point: instantiated once per KK, each from its own translation unit (gpe_edgegemm_w8.hip, _k5, _k4)
 template <int KK>

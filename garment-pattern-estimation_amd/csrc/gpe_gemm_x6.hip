@@ -39,7 +39,6 @@
 #define GX_LDS (2 * GX_BUF)           // two steps; the epilogue's C image 128 x 132 x 4 = 67584 bytes (+ 4 KB of column sums) fits
 
 typedef SplitBf16x3 GXS;
-extern "C" int gpe_debug_get(void);
 
 __device__ __forceinline__ int gx_slot(int row, int kg) { return kg ^ ((row >> 2) & 2); }
 

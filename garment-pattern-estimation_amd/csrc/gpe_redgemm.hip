@@ -25,10 +25,6 @@
 #include "gpe_redgemm_plan.h"
 #include <stdlib.h>
 
-extern "C" int gpe_debug_get(void);
-static int g_rd_math = 0;            // 0: exact fp32 MFMA, 1: bf16x3, 2: f16x3 where the operand scales are known (gpe_math_set)
-void gpe_redgemm_set_math(int m) { g_rd_math = m; }
-
 // b3 kernel, compile-time switches (A/B builds through scripts/ab_build.sh; run-time flags cost this kernel registers it does not
 // have: a run-time `pipe` flag spilled 120 of them in the gathered 13 x 13 instance):
 //   RD_B3_PIPE  producers' order: 0 (default) = fetch tile t + 1 ... left-over MFMAs ... commit it (round 4); 1 = the two operands
@@ -1398,7 +1394,7 @@ static int rd_finish(const RdParams& p, const GpeRdPlan& plan, float* G, int ldG
 // fill the plan, switch on the path, finish
 static int rd_run(RdParams& p, int vmode, float* G, int ldG, float* colsum, float* part, int accumulate, hipStream_t s)
 {
-    const GpeRdPlan plan = gpe_redgemm_plan(p, vmode, colsum != nullptr, g_rd_math, gpe_debug_get(), gpe_rd_switches(), gpe_num_cus());
+    const GpeRdPlan plan = gpe_redgemm_plan(p, vmode, colsum != nullptr, gpe_math_redgemm(), gpe_debug_get(), gpe_rd_switches(), gpe_num_cus());
     if (plan.path == GPE_RD_NOTHING) return plan.rc;
     p.vec = plan.vec; p.MgPad = plan.MgPad; p.NgPad = plan.NgPad; p.num_tiles = plan.num_tiles;
     p.umagic = plan.umagic; p.vmagic = plan.vmagic; p.pin_tpc = plan.pin_tpc;
@@ -1456,7 +1452,7 @@ extern "C" int gpe_edge_redgemm(const float* u, int ldu, int v_mode, const float
             return GPE_EINVAL;
         p.lz_g = lz_g; p.lz_ldg = lz_ldg; p.lz_amx = lz_amx; p.lz_amn = lz_amn; p.lz_ldagg = lz_ldagg; p.lz_coef = lz_coef;
     }
-    if (g_rd_math == 2 && amax_u && p.rows >= gpe_h3_min_rows()) {
+    if (gpe_math_redgemm() == 2 && amax_u && p.rows >= gpe_h3_min_rows()) {
         // f16x3: the operand scales must be known without a pass over an E-row tensor — U (a dz tensor) through the caller's amax
         // word of it, V through the caller's word (dense: the amax the forward kernel measured; gathered: a bound of
         // relu(P_i + Q_j), gpe_edge_pq_amax) or, for the gathered operand only, the bound passes run here; else exact fp32

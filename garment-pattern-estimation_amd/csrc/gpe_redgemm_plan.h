@@ -233,7 +233,7 @@ static inline GpeRdPlan gpe_rd_image(GpeRdPlan p, GpeRdPath path, int nblk, int 
 
 // The ladder (DESIGN.md 5.33 has it as a table).  Pure: no HIP call, no environment, no static, no launch.
 //   c       the call (operands, sizes, words, lazy fields, k, pin_clouds);  vmode  V_DENSE / V_GATHER
-//   math    0 exact fp32, 1 bf16x3, 2 f16x3 (gpe_math_set);  debug  gpe_debug_get();  cus  usable compute units (gpe_num_cus)
+//   math    0 exact fp32, 1 bf16x3, 2 f16x3 (gpe_math_redgemm);  debug  gpe_debug_get();  cus  usable compute units (gpe_num_cus)
 static inline GpeRdPlan gpe_redgemm_plan(const RdParams& c, int vmode, bool want_colsum, int math, int debug, const GpeRdSwitches& sw, int cus)
 {
     GpeRdPlan p = {};

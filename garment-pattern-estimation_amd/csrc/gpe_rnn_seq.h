@@ -8,10 +8,6 @@
 #include "gpe_common.h"
 #include <type_traits>
 
-extern "C" int gpe_math_get(void);
-extern "C" int gpe_debug_get(void);
-extern "C" long gpe_packed_size(int N, int K);
-
 // one result convention for every family entry point (that of gpe_edge_dispatch.h): launched, not mine (the caller tries the next
 // family), or an error code < 0
 #define GPE_RNN_LAUNCHED 1

@@ -76,6 +76,13 @@ struct GpeFold {
 };
 int gpe_edge_pseudo_fold(const RgParams& p, const GpeFold& fd, hipStream_t s);   // gpe_edgegemm_sr.hip
 
+// the two kernels gpe_linear (gpe_rowgemm.hip) hands a shape to before its own:
+// single-stage kernel for latency-bound shapes (gpe_smallgemm.hip)
+int gpe_smallgemm_linear(const RgParams& r, hipStream_t s);
+// f16x3 mode, big dense products on the bf16 pipe (gpe_gemm_x6.hip): 1 launched, 0 not on its menu, < 0 error
+int gpe_gemm_x6_linear(const GpeRows& a, const float* wp, int Npad, int Kq, const float* bias, const GpeRows& addend, float* y,
+                       long y_so, long y_si, int y_inner, long M, int N, int K, int act, hipStream_t s);
+
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 // streaming 16-B store that does NOT keep its line in the XCD's L2 (sc1: write-through + drop, MI355X_MICROARCH.md "stores of

@@ -201,36 +201,6 @@ static int rg_pick_nt_single(int N)   // smallest instantiated NT whose block co
     return -1;
 }
 
-// single-stage kernel for latency-bound shapes (gpe_smallgemm.hip)
-int gpe_smallgemm_linear(const RgParams& r, hipStream_t s);
-// register-stationary fast path for the shipped edge-MLP sizes (gpe_edge_dispatch.hip): 1 launched, 0 not on its menu, < 0 error
-int gpe_edgegemm_try(const RgParams& p, int amode, int emode, int stats_nblk, hipStream_t s);
-
-void gpe_edgegemm_set_math(int m);
-void gpe_redgemm_set_math(int m);
-
-int gpe_gemm_x6_linear(const GpeRows& a, const float* wp, int Npad, int Kq, const float* bias, const GpeRows& addend, float* y,
-                       long y_so, long y_si, int y_inner, long M, int N, int K, int act, hipStream_t s);      // gpe_gemm_x6.hip
-extern "C" long gpe_packed_size(int N, int K);
-static int g_gpe_dbg = 0;
-extern "C" int gpe_debug_set(int flags) { g_gpe_dbg = flags; return 0; }
-extern "C" int gpe_debug_get(void) { return g_gpe_dbg; }
-static int g_gpe_math = 0;
-extern "C" int gpe_edge_lazy_dz3_ok(int B, int N, int k, int F, int Cprev);
-extern "C" int gpe_math_get(void) { return g_gpe_math; }
-extern "C" int gpe_math_set(int mode)
-{
-    if (mode < 0 || mode > 4) return GPE_EINVAL;
-    const int prev = g_gpe_math;
-    g_gpe_math = mode;
-    // row GEMMs (forward, input-gradient half): 0 exact fp32, 1 two-term split-bf16 (modes 1, 2), 2 three-term split-bf16
-    // (mode 3), 3 two-term split-fp16 on tensor-normalised operands (mode 4)
-    gpe_edgegemm_set_math(mode == 4 ? 3 : mode == 3 ? 2 : (mode != 0 ? 1 : 0));
-    // the weight-gradient reduce-GEMM: split-bf16 only in mode 1; mode 4: split-fp16 where the operand scales are known
-    gpe_redgemm_set_math(mode == 1 ? 1 : mode == 4 ? 2 : 0);
-    return prev;
-}
-
 #define GPE_STATS_BLOCKS 512
 extern "C" int gpe_stats_blocks(void) { return GPE_STATS_BLOCKS; }
 
@@ -240,16 +210,6 @@ extern "C" long gpe_edge_ws_bytes(int B, int N, int k, int ldmax)
 {
     if (B <= 0 || N <= 0 || k <= 0 || ldmax <= 0) return GPE_EINVAL;
     return (long)(GPE_WS_DUMMY_BYTES + GPE_WS_H3_BYTES) + (long)gpe_edge_pseudo_bytes((long)B * N, k, ldmax);
-}
-static long g_h3_min_rows = GPE_H3_MIN_ROWS_DEFAULT;
-long gpe_h3_min_rows() { return g_h3_min_rows; }
-extern "C" long gpe_f16x3_min_rows(void) { return g_h3_min_rows; }
-extern "C" long gpe_f16x3_min_rows_set(long rows)
-{
-    if (rows < 0) return GPE_EINVAL;
-    const long prev = g_h3_min_rows;
-    g_h3_min_rows = rows;
-    return prev;
 }
 extern "C" int gpe_edge_pq_amax(const float* pq, int ldpq, int H, long rows, uint32_t* amax, void* ws, long ws_bytes,
                                 void* stream)
@@ -339,7 +299,7 @@ extern "C" int gpe_linear(const float* a, long a_so, long a_si, int a_inner, con
     p.y = y; p.y_so = y_so; p.y_si = y_si; p.y_inner = y_inner; p.act = act;
     // f16x3 mode: the big dense products (the layer-2 [P|Q] projection and its input gradient, 65536 rows x 400 x 150) on the bf16
     // pipe, three-term splits, six MFMAs per product (gpe_gemm_x6.hip); gpe_debug_set(16384) keeps the exact kernels (A/B runs)
-    if (g_gpe_math == 4 && !(g_gpe_dbg & 16384)) {
+    if (gpe_math_get() == 4 && !(gpe_debug_get() & 16384)) {
         const int rc = gpe_gemm_x6_linear(p.a, wp, p.Npad, (int)(gpe_packed_size(N, K) / p.Npad / 4), bias, p.addend, y, y_so, y_si, y_inner, M, N, K,
                                           act, (hipStream_t)stream);
         if (rc != 0) return rc < 0 ? rc : GPE_OK;
@@ -386,7 +346,7 @@ extern "C" int gpe_linear(const float* a, long a_so, long a_si, int a_inner, con
 extern "C" int gpe_edge_lazy_dz3_ok(int B, int N, int k, int F, int Cprev)
 {
     static const int dbg_off = gpe_dbg_env("GPE_LAZY_DZ3", 1) == 0;   // A/B measurements
-    if (dbg_off || (g_gpe_dbg & 512) || g_gpe_math != 4 || k != 16 || B <= 0 || N <= 0) return 0;    // gpe_debug_set(512): eager dz3
+    if (dbg_off || (gpe_debug_get() & 512) || gpe_math_get() != 4 || k != 16 || B <= 0 || N <= 0) return 0;    // gpe_debug_set(512): eager dz3
     if (!gpe_edge_width_ok(F) || !gpe_edge_width_ok(Cprev) || (Cprev & 3)) return 0;
     if (gpe_cdiv(Cprev, 16) != 13 || (gpe_cdiv(F, 16) != 10 && gpe_cdiv(F, 16) != 13)) return 0;   // the fp16 reduce-GEMM's instantiated shapes
     const long rows = (long)B * N * k;
@@ -461,7 +421,7 @@ extern "C" int gpe_edge_mlp_fwd(int a_mode, const float* pq, int ldpq, const int
     p.wp = wp; p.Npad = gpe_round_up(Cout, 16); p.bias = bias;
     p.out = out; p.ldo = ldo; p.stats_part = stats_part;
     p.agg = agg; p.mx = mx; p.mn = mn; p.oamx = amx; p.oamn = amn; p.oldagg = ldagg;
-    p.dbg = g_gpe_dbg; p.pin_clouds = B;
+    p.dbg = gpe_debug_get(); p.pin_clouds = B;
     p.user_amax_a = amax_a; p.user_amax_out = amax_out; p.ws = gpe_edge_ws(ws, ws_bytes);
     p.out_half = out_half;
     p.w_ready = w_ready;
@@ -470,12 +430,12 @@ extern "C" int gpe_edge_mlp_fwd(int a_mode, const float* pq, int ldpq, const int
     p.tracked = &tracked;
     int rc = gpe_edgegemm_try(p, a_mode == 0 ? A_GATHER : A_DENSE, E_EDGE_FWD,
                               stats_part ? GPE_STATS_BLOCKS : 0, (hipStream_t)stream);
-    if (rc == 0) {
+    if (rc == GPE_EDGE_NOT_MINE) {
         dim3 grid(GPE_STATS_BLOCKS, ny);
         rc = (a_mode == 0) ? rg_dispatch_nt<A_GATHER, E_EDGE_FWD>(NT, p, grid, (hipStream_t)stream)
                            : rg_dispatch_nt<A_DENSE, E_EDGE_FWD>(NT, p, grid, (hipStream_t)stream);
     } else
-        rc = rc == 1 ? GPE_OK : rc;
+        rc = rc == GPE_EDGE_LAUNCHED ? GPE_OK : rc;
     // the caller asked for the largest magnitude written and the kernel that ran did not track it: one streaming pass
     if (rc == GPE_OK && out_half && !tracked) return GPE_EINVAL;       // (cannot happen: the f16x3 kernels track what they store)
     if (rc == GPE_OK && amax_out && !tracked) rc = gpe_h3_absmax(amax_out, out, p.M, Cout, ldo, (hipStream_t)stream);
@@ -513,7 +473,7 @@ extern "C" int gpe_edge_mlp_bwd(const float* a, int lda, int act_mode, const flo
     p.wp = wp; p.Npad = gpe_round_up(Cout, 16);
     p.out = dz_out; p.ldo = ldo; p.coef_out = coef_out; p.dP = dP; p.lddp = lddp;
     hipStream_t s = (hipStream_t)stream;
-    p.dbg = g_gpe_dbg; p.pin_clouds = B;
+    p.dbg = gpe_debug_get(); p.pin_clouds = B;
     p.user_amax_a = amax_a; p.user_amax_out = amax_out; p.ws = gpe_edge_ws(ws, ws_bytes);
     p.rev = gpe_walk_rev(1);                           // B3 and B2 walk down: behind a reduce-GEMM that walked up
     if (lz_g) {
@@ -527,13 +487,13 @@ extern "C" int gpe_edge_mlp_bwd(const float* a, int lda, int act_mode, const flo
     int tracked = 0;
     p.tracked = &tracked;
     int rc = gpe_edgegemm_try(p, A_DENSE, act_mode == 1 ? E_BWD_GATHER : E_BWD_INPLACE, 0, s);
-    if (lz_g && rc != 1) return rc < 0 ? rc : GPE_EINVAL;          // no eager kernel may read a3 as if it were dz3
-    if (rc == 0) {
+    if (lz_g && rc != GPE_EDGE_LAUNCHED) return rc < 0 ? rc : GPE_EINVAL;          // no eager kernel may read a3 as if it were dz3
+    if (rc == GPE_EDGE_NOT_MINE) {
         dim3 grid(p.num_tiles < 2048 ? p.num_tiles : 2048, ny);
         rc = (act_mode == 1) ? rg_dispatch_nt<A_DENSE, E_BWD_GATHER>(NT, p, grid, s)
                              : rg_dispatch_nt<A_DENSE, E_BWD_INPLACE>(NT, p, grid, s);
     } else
-        rc = rc == 1 ? GPE_OK : rc;
+        rc = rc == GPE_EDGE_LAUNCHED ? GPE_OK : rc;
     if (rc == GPE_OK && amax_out && !tracked) rc = gpe_h3_absmax(amax_out, dz_out, p.M, Cout, ldo, s);
     return rc;
 }

@@ -705,8 +705,6 @@ static int sp_dispatch_fwd(const PT& p, bool h3, hipStream_t s)
     }
 }
 
-extern "C" int gpe_math_get(void);
-
 // checks and operands shared by the prediction and the evaluating entry point; false: bad arguments
 static bool sp_fwd_params(const float* ab, int ldab, int H, int n_layers, const float* wpk, const void* planes, const uint32_t* w_amax,
                           const float* last_stats, const int32_t* num_edges, int B, int P, int L, uint64_t* table, float* logits,

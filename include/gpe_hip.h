@@ -11,10 +11,10 @@
  *     workspaces (`part`, `ws`: sizes from the gpe_*_ws* queries) and the f16x3 scale words below; the library never allocates
  *     device memory and keeps no record of tensors between calls.  Work is enqueued on `stream` of the CURRENT device and the
  *     call returns immediately.  Calls on different streams may run concurrently as long as they share no output / workspace.
- *     Process-global state is limited to (a) the arithmetic mode (gpe_math_set, gpe_f16x3_min_rows_set) and the profiling
- *     switches (gpe_debug_set), which apply to every stream and device of the process, and (b) per-device caches of the CU
- *     count and of the >64 KB LDS opt-in (hipFuncSetAttribute), keyed by device ordinal.  The mode setters are not
- *     thread-safe against concurrent launches; everything else is.
+ *     Process-global state is limited to (a) the arithmetic mode (gpe_math_set, gpe_f16x3_min_rows_set), the profiling
+ *     switches (gpe_debug_set) and the CU reservation (gpe_reserve_cus_set), which apply to every stream and device of the
+ *     process, and (b) per-device caches of the CU count and of the >64 KB LDS opt-in (hipFuncSetAttribute), keyed by device
+ *     ordinal.  The mode setters are not thread-safe against concurrent launches; everything else is.
  *   - "amax word" (f16x3 mode): a uint32 in device memory holding the bit pattern of a non-negative float that is >= the
  *     largest magnitude of a tensor (a bound is as good as the value; tighter = more precise).  An entry point that writes an
  *     activation / dz tensor fills the word passed as `amax_out` (whatever kernel ran: if it could not track the maximum while

@@ -2,11 +2,13 @@
 entry points behave; compute entry points are NOT called here."""
 import ctypes
 import os
+import re
+import subprocess
 
 import pytest
 
 import gpe_amd
-from gpe_amd import _lib
+from gpe_amd import _lib, build
 
 
 def test_header_declares_expected_surface():
@@ -25,6 +27,41 @@ def test_header_declares_expected_surface():
                     'gpe_pack_job_blocks', 'gpe_adam_hyper'):
             continue
         assert res == 'i' and args[-1] == 'p', name
+
+
+def test_parser_binds_every_declaration_of_the_header():
+    """parse_header returns one signature per gpe_* declaration of the comment-stripped header: none is skipped."""
+    src = open(_lib.HEADER_PATH).read()
+    src = re.sub(r'/\*.*?\*/', ' ', src, flags=re.S)
+    src = re.sub(r'//[^\n]*', ' ', src)
+    declared = re.findall(r'\b(gpe_\w+)\s*\(', src)
+    assert len(declared) == len(set(declared)) == 118
+    sigs = _lib.parse_header()
+    assert len(sigs) == len(declared) and set(sigs) == set(declared)
+
+
+def test_parser_refuses_a_declaration_it_cannot_bind(tmp_path):
+    """A return type other than int / long used to be skipped silently; ctypes would then call the symbol with default types."""
+    h = tmp_path / 'bad.h'
+    h.write_text('/* float gpe_in_a_comment(int a); */\nint gpe_ok(const float* x, long n, void* stream);\nfloat gpe_x(int a);\n')
+    with pytest.raises(ValueError, match=r'\bgpe_x\b'):
+        _lib.parse_header(str(h))
+    h.write_text('/* float gpe_in_a_comment(int a); */\nint gpe_ok(const float* x, long n, void* stream);\n')
+    assert _lib.parse_header(str(h)) == {'gpe_ok': ('i', ['p', 'l', 'p'])}
+
+
+@pytest.mark.skipif(not os.path.exists(build.HIPCC), reason='no hipcc: the compile-time guard cannot be exercised')
+@pytest.mark.parametrize('params, ok', [('void', True), ('int', False)])
+def test_definitions_are_checked_against_the_header(tmp_path, params, ok):
+    """csrc/gpe_common.h includes include/gpe_hip.h, so an extern "C" definition that differs from its declaration does not compile."""
+    src = tmp_path / 'guard.hip'
+    src.write_text('#include "%s"\nextern "C" int gpe_abi_version(%s) { return 7; }\n' % (os.path.join(build.CSRC, 'gpe_common.h'), params))
+    r = subprocess.run([build.HIPCC, '--offload-arch=gfx950', '--cuda-host-only', '-std=c++17', '-fsyntax-only', str(src)],
+                       capture_output=True, text=True)
+    if ok:
+        assert r.returncode == 0, r.stderr
+    else:
+        assert r.returncode != 0 and 'conflicting types' in r.stderr, r.stderr
 
 
 def test_library_exports_every_declared_symbol():
@@ -71,6 +108,39 @@ def test_cu_reservation_is_host_only():
     assert l.gpe_reserve_cus_set(-1) == -22 and l.gpe_reserve_cus_set(500) == -22
     import gpe_amd
     assert gpe_amd.set_reserved_cus(8) == 0 and gpe_amd.set_reserved_cus(0) == 8
+
+
+def test_every_reader_sees_the_one_process_state():
+    """gpe_edge_lazy_dz3_ok (gpe_rowgemm.hip) reads the arithmetic mode, the debug mask, the f16x3 size gate and the CU count, all of
+    which live in gpe_state.hip: each setter must reach it.  32 clouds x 2048 points x 16 neighbours, 150 -> 200: 2^20 rows, on the
+    menu; the answers are those of the library before the state moved (without a GPU the CU count is taken as 256)."""
+    l = _lib.lib()
+    math, dbg, gate = l.gpe_math_get(), l.gpe_debug_get(), l.gpe_f16x3_min_rows()
+    reserved = l.gpe_reserve_cus_set(0)
+    try:
+        l.gpe_debug_set(0)
+        l.gpe_f16x3_min_rows_set(32768)
+        for mode in (0, 1, 2, 3):
+            l.gpe_math_set(mode)
+            assert l.gpe_edge_lazy_dz3_ok(32, 2048, 16, 150, 200) == 0, mode
+        l.gpe_math_set(4)
+        assert l.gpe_edge_lazy_dz3_ok(32, 2048, 16, 150, 200) == 1
+        l.gpe_debug_set(512)
+        assert l.gpe_edge_lazy_dz3_ok(32, 2048, 16, 150, 200) == 0
+        l.gpe_debug_set(0)
+        l.gpe_f16x3_min_rows_set(1 << 30)
+        assert l.gpe_edge_lazy_dz3_ok(32, 2048, 16, 150, 200) == 0
+        l.gpe_f16x3_min_rows_set(32768)
+        assert l.gpe_edge_lazy_dz3_ok(32, 2048, 16, 150, 200) == 1
+        # the CU count: 2 x 1024 x 16 rows are 1024 tiles of 32, too few for 8 per CU on 256 CUs, enough on 256 - 192
+        assert l.gpe_edge_lazy_dz3_ok(2, 1024, 16, 150, 200) == 0
+        l.gpe_reserve_cus_set(192)
+        assert l.gpe_edge_lazy_dz3_ok(2, 1024, 16, 150, 200) == 1
+    finally:
+        l.gpe_reserve_cus_set(reserved)
+        l.gpe_f16x3_min_rows_set(gate)
+        l.gpe_debug_set(dbg)
+        l.gpe_math_set(math)
 
 
 def test_bad_arguments_are_rejected_without_a_gpu():

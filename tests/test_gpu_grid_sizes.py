@@ -25,7 +25,7 @@ RD_RT = 32                      # rows per reduce-GEMM row tile (csrc/gpe_redgem
 
 
 def _usable_cus(reserve):
-    """What gpe_num_cus() answers at this reservation (csrc/gpe_pointwise.hip)."""
+    """What gpe_num_cus() answers at this reservation (csrc/gpe_state.hip)."""
     c = torch.cuda.get_device_properties(0).multi_processor_count
     if c <= 0:
         c = 256
