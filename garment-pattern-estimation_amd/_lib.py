@@ -1,5 +1,5 @@
-"""ctypes binding of libgpe_hip.so (C ABI: include/gpe_hip.h).  The header is the one description of the ABI and both
-sides are checked against it: the signatures here are parsed from it (parse_header; a declaration it cannot bind raises,
+"""ctypes binding of libgpe_hip.so (C ABI: include/gpe_hip.h, plus the additions since ABI version 7 in
+include/gpe_hip_ext.h).  The headers are the one description of the ABI and both sides are checked against them: the signatures here are parsed from it (parse_header; a declaration it cannot bind raises,
 and lib() fails on a declared symbol the library does not export), and every definition in csrc/ is compiled with it
 included (csrc/gpe_common.h), so a definition that differs from its declaration does not compile.  There is NO fallback:
 if the HIP library is missing or a call fails, this raises — the product path never routes around the kernels."""
@@ -13,6 +13,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # GPE_HIP_LIB selects another build of the same ABI (A/B measurements of kernel variants: scripts/ab_probe.sh)
 LIB_PATH = os.environ.get('GPE_HIP_LIB') or os.path.join(_HERE, 'libgpe_hip.so')
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'gpe_hip.h')
+# entry points added since ABI version 7: folded into the main header at the next version bump, bound like it until then
+EXT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'gpe_hip_ext.h')
+HEADERS = (HEADER_PATH, EXT_HEADER_PATH)
 
 _CT = {'p': ctypes.c_void_p, 'i': ctypes.c_int, 'l': ctypes.c_long, 'f': ctypes.c_float, 'd': ctypes.c_double}
 
@@ -60,10 +63,11 @@ def lib():
                 'libgpe_hip.so not built: run `python -c "import __graft_entry__ as g; g.build()"` '
                 '(hipcc --offload-arch=gfx950).  There is no CPU fallback for the product path.')
         l = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in parse_header().items():
-            fn = getattr(l, name)          # AttributeError here = header/library mismatch: fail loudly
-            fn.restype = _CT[res]
-            fn.argtypes = [_CT[a] for a in args]
+        for header in HEADERS:
+            for name, (res, args) in parse_header(header).items():
+                fn = getattr(l, name)      # AttributeError here = header/library mismatch: fail loudly
+                fn.restype = _CT[res]
+                fn.argtypes = [_CT[a] for a in args]
         _lib = l
         env = os.environ.get('GPE_MATH')
         if env:

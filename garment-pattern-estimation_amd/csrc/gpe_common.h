@@ -6,6 +6,8 @@
 // the C ABI itself: every translation unit sees the declarations, so an extern "C" definition whose parameters differ from
 // the header Python binds from is a compile error ("conflicting types"), not a silently mis-called symbol
 #include "../../include/gpe_hip.h"
+// ... and the additions since ABI version 7, declared in a header of their own until the next version bump
+#include "../../include/gpe_hip_ext.h"
 
 #define GPE_OK 0
 #define GPE_EINVAL (-22)

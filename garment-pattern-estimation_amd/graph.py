@@ -18,6 +18,9 @@ What a replay cannot carry in frozen kernel arguments is fed through device memo
 The fp16-activation guard (ops.set_half_act_guard) keeps working in its default 'fallback' mode: the amax words of the captured forward
 are read asynchronously after every replay; a layer that trips it invalidates the graph, and the next step is captured again on the
 fp32 path.  'strict' (a host read inside the forward) cannot be captured and raises.
+FusedAdam's guarded step (max_grad_norm / skip_nonfinite / guard_overflow / param_grad_norms) is captured like the plain one: the norm,
+the clip factor and the skip flag live in device memory and the Adam launch reads them there; optimizer.grad_norm, .skipped, ... are static
+tensors that every replay overwrites, like `loss`.
 
 One process per GPU, world size 1: a gradient exchange inside the captured region is not supported (RCCL launches are not captured
 here).  The captured step is single-stream; the tensors a replay returns are static buffers, overwritten by the next replay."""
@@ -198,7 +201,7 @@ class StepGraph:
                 tripped = False
                 for guard, word in self.guards:
                     was = guard.disabled
-                    guard.watch(word)
+                    guard._watch(word)           # (the poll only: the word went on the optimizer's record during the capture)
                     guard.allow()
                     tripped = tripped or (guard.disabled and not was)
                 if tripped:

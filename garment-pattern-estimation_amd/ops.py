@@ -14,6 +14,7 @@ Two per-model services live here as well (both optional; without them every Func
                 straight into the arena's gradient buffer (no per-parameter tensors, no cat/copy for the all-reduce
                 buckets, one fused Adam launch).
 """
+import collections
 import contextlib
 import math
 import os
@@ -693,6 +694,23 @@ if os.environ.get('GPE_HALF_ACT_GUARD'):                 # (validated: a typo ra
     set_half_act_guard(os.environ['GPE_HALF_ACT_GUARD'])
 
 
+# The amax words handed to HalfActGuard.watch since the last optim.FlatArena.begin_step(), per device ordinal.  Bounded: a model that
+# is never stepped through a FlatArena keeps the newest few only (FusedAdam takes at most eight and refuses more).
+_WATCHED = {}
+_WATCHED_KEEP = 9
+
+
+def watched_words(device):
+    """-> the amax words (int32[1] device tensors) recorded on `device` since the arena's last begin_step()."""
+    return list(_WATCHED.get(torch.device(device).index, ()))
+
+
+def clear_watched_words(device):
+    rec = _WATCHED.get(torch.device(device).index)
+    if rec:
+        rec.clear()
+
+
 class HalfActGuard:
     """Per-layer state of set_half_act_guard: owned by the module that owns the layer (net_blocks.DynamicEdgeConv)."""
     LIMIT = 65504.0
@@ -735,7 +753,16 @@ class HalfActGuard:
 
     def watch(self, word):
         """After the forward launch that filled `word` (int32[1], the activation's amax bits).  'strict': returns False when the
-        launch must be repeated with fp32 storage."""
+        launch must be repeated with fp32 storage.  The word of a launch whose fp16 rows stay in use is also put on the device's
+        record of watched words (watched_words), eagerly and during a capture: optim.FusedAdam(guard_overflow=True) hands them to
+        its norm pass, which leaves the weights alone in the step that reached the limit."""
+        ok = self._watch(word)
+        if ok:
+            _WATCHED.setdefault(word.device.index, collections.deque(maxlen=_WATCHED_KEEP)).append(word)
+        return ok
+
+    def _watch(self, word):
+        """watch() without the record (graph.StepGraph polls the captured words again after every replay)."""
         if _HALF_ACT_GUARD == 'off':
             return True
         if CAPTURE is not None:                          # the StepGraph reads this word after every replay

@@ -11,6 +11,7 @@ this path: all parameters of a model live in ONE flat arena, so that
 
 FlatArena is plain torch (it also runs on CPU tensors: the gloo tests use it); FusedAdam needs the HIP library.
 """
+import ctypes
 import math
 
 import torch
@@ -90,9 +91,12 @@ class FlatArena:
             fn(i)
 
     def begin_step(self):
-        """Forget which gradients were written (call after the optimizer consumed them)."""
+        """Forget which gradients were written (call after the optimizer consumed them), and the fp16-activation words the forward
+        of this step put on the device's record (ops.watched_words)."""
         self.written.clear()
         self.touched.clear()
+        if self.flat.device.type == 'cuda':
+            ops.clear_watched_words(self.flat.device)
 
     def zero_grad(self):
         self.grad.zero_()
@@ -163,9 +167,34 @@ class FusedAdam:
 
         arena = FlatArena(model); opt = FusedAdam(arena, lr=2e-3)            # or FusedAdam(model, ...)
         loss.backward(); opt.step()                                          # gradients are cleared by the same launch
-    """
 
-    def __init__(self, arena_or_module, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, schedule=None):
+    The guarded step (opt-in; any of the four options below turns it on, for step() and for a step captured by graph.StepGraph;
+    with all of them at their defaults the launches are exactly the unguarded ones).  One pass over the gradient arena per run of
+    live parameters plus one small finishing launch form the step's global gradient norm on the device (include/gpe_hip_ext.h),
+    and the Adam launch reads the outcome there — nothing is read on the host:
+      max_grad_norm=M     torch.nn.utils.clip_grad_norm_(parameters, M) in front of the step: the gradient is read scaled by
+                          min(1, M / (norm + 1e-6));
+      skip_nonfinite      a step whose gradient norm is inf or NaN is not applied (AMP's found_inf pattern): parameters and both
+                          moments stay as they are, the gradient is cleared as usual;
+      guard_overflow      the same for a step whose forward stored an fp16 activation that reached the fp16 limit (f16x3 mode,
+                          ops.set_half_act_guard: its 'fallback' mode notices one step late — with this option the step that ran on
+                          clamped values is not applied; the guard's own warning and switch to fp32 rows stay as they are).
+                          The words are local to a rank: with more than one rank step() raises;
+      param_grad_norms    opt.param_norms: the gradient norm of every parameter, in model.parameters() order.
+    Results, device tensors that every step (and every replay) overwrites in place: opt.grad_norm (0-dim fp32, the norm before
+    clipping), opt.clip_coef, opt.last_skipped (int32 0 / 1), opt.skipped (int64 count), opt.param_norms.
+    A skipped step keeps its number: the schedule slot and the bias-correction exponent advance as if it had been taken (the
+    reference steps its scheduler every batch regardless) and the host never reads the flag, so the step after a skipped step t
+    runs with the scalars of step t + 1; state_dict() counts it as a step.  Buffers written by the forward — BatchNorm running
+    statistics — are NOT protected by a skip.
+    """
+    MAX_GUARD_RUNS = 16                # runs of live segments one finishing launch takes (include/gpe_hip_ext.h)
+    MAX_GUARD_WORDS = 8
+
+    def __init__(self, arena_or_module, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, schedule=None,
+                 max_grad_norm=None, skip_nonfinite=False, guard_overflow=False, param_grad_norms=False):
+        if max_grad_norm is not None and not (float(max_grad_norm) > 0 and math.isfinite(float(max_grad_norm))):
+            raise ValueError('FusedAdam: max_grad_norm must be a positive finite number (None = no clipping)')
         self.arena = arena_or_module if isinstance(arena_or_module, FlatArena) else FlatArena(arena_or_module)
         if self.arena.flat.device.type != 'cuda':
             raise RuntimeError('FusedAdam runs on the MI355X (libgpe_hip.so); there is no CPU path')
@@ -178,6 +207,63 @@ class FusedAdam:
         # its count, and its bias correction continues from there when a gradient shows up later.  Same here.
         self.steps = [0] * len(self.arena.params)
         self.last_lr = self.lr if schedule is None else schedule.lr(0)
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.skip_nonfinite, self.guard_overflow = bool(skip_nonfinite), bool(guard_overflow)
+        self.guarded = bool(self.max_grad_norm is not None or skip_nonfinite or guard_overflow or param_grad_norms)
+        self.grad_norm = self.clip_coef = self.last_skipped = self.skipped = self.param_norms = None
+        if self.guarded:
+            self._guard_init(bool(param_grad_norms))
+
+    # ---- the guarded step: norm pass + guard block (include/gpe_hip_ext.h) ----
+    def _guard_init(self, param_grad_norms):
+        a = self.arena
+        nseg, dev = len(a.params), a.flat.device
+        ends = [o + (p.numel() + 3) // 4 * 4 for o, p in zip(a.offsets, a.params)]
+        c_ends, c_slots = (ctypes.c_long * nseg)(*ends), (ctypes.c_long * (nseg + 1))()
+        total = L.query('gpe_grad_norm_slots', c_ends, nseg, c_slots)
+        if total <= 0:
+            raise RuntimeError('gpe_grad_norm_slots failed with code %d (the guarded step takes up to 4096 parameters)' % total)
+        self._seg_of_start = {o: i for i, o in enumerate(a.offsets)}
+        self._seg_of_end = {e: i + 1 for i, e in enumerate(ends)}
+        self._nslots = int(total)
+        self._seg_end = torch.tensor(ends, dtype=torch.int64, device=dev)
+        self._seg_slot = torch.tensor(list(c_slots), dtype=torch.int64, device=dev)
+        self._part = torch.zeros(self._nslots, dtype=torch.float64, device=dev)
+        # the 32-byte guard block: float norm, float coef, int32 skip, int32 reserved, int64 steps, int64 skipped
+        self._guard = torch.zeros(8, dtype=torch.int32, device=dev)
+        self.grad_norm = self._guard[0:1].view(torch.float32)[0]
+        self.clip_coef = self._guard[1:2].view(torch.float32)[0]
+        self.last_skipped = self._guard[2]
+        self.skipped = self._guard[6:8].view(torch.int64)[0]
+        self.param_norms = torch.zeros(nseg, dtype=torch.float32, device=dev) if param_grad_norms else None
+
+    def _guard_check(self):
+        """What the guarded step refuses, looked at before the step touches any state."""
+        if self.guard_overflow and torch.distributed.is_available() and torch.distributed.is_initialized() \
+                and torch.distributed.get_world_size() > 1:
+            raise RuntimeError('FusedAdam(guard_overflow=True): the fp16-activation words are local to a rank, so the ranks would '
+                               'not agree on which step to skip; with more than one rank use max_grad_norm / skip_nonfinite (the '
+                               'averaged gradients are the same bits on every rank)')
+
+    def _guard_pass(self, runs, grad_scale):
+        """The launches in front of the guarded Adam launches of one step: one norm pass per run, one finish."""
+        a = self.arena
+        if not runs or len(runs) > self.MAX_GUARD_RUNS:
+            raise RuntimeError('FusedAdam: the guarded step takes 1 .. %d runs of live parameters, this step has %d'
+                               % (self.MAX_GUARD_RUNS, len(runs)))
+        words = ops.watched_words(a.flat.device) if self.guard_overflow else []
+        if len(words) > self.MAX_GUARD_WORDS:
+            raise RuntimeError('FusedAdam(guard_overflow=True): more than %d fp16-activation words were recorded since the last '
+                               'step (several forward passes per optimizer step?)' % self.MAX_GUARD_WORDS)
+        nseg = len(a.params)
+        segs = [(self._seg_of_start[lo], self._seg_of_end[hi]) for lo, hi, _ in runs]
+        for j0, j1 in segs:
+            L.call('gpe_grad_norm_part', a.grad, a.numel, self._seg_end, self._seg_slot, nseg, j0, j1, self._nslots, self._part)
+        c_runs = (ctypes.c_int * (2 * len(segs)))(*[j for s in segs for j in s])
+        c_words = (ctypes.c_void_p * max(len(words), 1))(*[w.data_ptr() for w in words])
+        L.call('gpe_grad_norm_finish', self._part, self._seg_slot, nseg, self._nslots, c_runs, len(segs), float(grad_scale),
+               self.max_grad_norm if self.max_grad_norm is not None else 0.0, int(self.skip_nonfinite), c_words, len(words),
+               ops.HalfActGuard.LIMIT, self.param_norms, 1, self._guard)
 
     def _runs(self, live, advance):
         """Maximal runs of consecutive live arena segments that share one step count -> [(lo, hi, step)].  torch.optim.Adam leaves a
@@ -211,12 +297,21 @@ class FusedAdam:
 
     def step(self, grad_scale=1.0):
         a = self.arena
+        if self.guarded:
+            self._guard_check()
         # weight gradients written on the side stream (ops.side_grads) — also what a backward pass that died half-way left un-joined
         streams.lane(a.flat.device.index).join()
         lr = self.lr if self.schedule is None else self.schedule.lr(self.t)
         self.t += 1
         runs = self._runs(self._live(), advance=True)
+        if self.guarded:
+            self._guard_pass(runs, grad_scale)
         for lo, hi, st in runs:
+            if self.guarded:
+                L.call('gpe_adam_step_guarded', a.flat[lo:hi], a.grad[lo:hi], self.m[lo:hi], self.v[lo:hi], hi - lo, float(lr),
+                       float(self.betas[0]), float(self.betas[1]), self.eps, self.weight_decay, st, float(grad_scale), 1,
+                       self._guard)
+                continue
             L.call('gpe_adam_step', a.flat[lo:hi], a.grad[lo:hi], self.m[lo:hi], self.v[lo:hi], hi - lo, float(lr),
                    float(self.betas[0]), float(self.betas[1]), self.eps, self.weight_decay, st, float(grad_scale), 1)
         if len(runs) != 1 or runs[0][:2] != (0, a.numel):
@@ -230,10 +325,19 @@ class FusedAdam:
     def step_captured(self, ctx, grad_scale=1.0):
         """Called INSIDE the capture, after backward: queues the launches, advances nothing.  -> the runs' (lo, hi)."""
         a = self.arena
+        if self.guarded:
+            self._guard_check()
         streams.lane(a.flat.device.index).join()
         self._cap_live = self._live()
         runs = self._runs(self._cap_live, advance=False)
+        if self.guarded:
+            self._guard_pass(runs, grad_scale)
         for r, (lo, hi, _) in enumerate(runs):
+            if self.guarded:
+                L.call('gpe_adam_step_guarded_dev', a.flat[lo:hi], a.grad[lo:hi], self.m[lo:hi], self.v[lo:hi], hi - lo,
+                       ctx.hyper_slot(r).dst, float(self.betas[0]), float(self.betas[1]), self.eps, self.weight_decay,
+                       float(grad_scale), 1, self._guard)
+                continue
             L.call('gpe_adam_step_dev', a.flat[lo:hi], a.grad[lo:hi], self.m[lo:hi], self.v[lo:hi], hi - lo, ctx.hyper_slot(r).dst,
                    float(self.betas[0]), float(self.betas[1]), self.eps, self.weight_decay, float(grad_scale), 1)
         if len(runs) != 1 or runs[0][:2] != (0, a.numel):
