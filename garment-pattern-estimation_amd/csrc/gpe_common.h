@@ -8,6 +8,8 @@
 #include "../../include/gpe_hip.h"
 // ... and the additions since ABI version 7, declared in a header of their own until the next version bump
 #include "../../include/gpe_hip_ext.h"
+// ... and the feature additions (the statistics fit), bound through _lib.FEATURE_HEADERS
+#include "../../include/gpe_hip_fit.h"
 
 #define GPE_OK 0
 #define GPE_EINVAL (-22)

@@ -2324,7 +2324,17 @@ def mesh_resident(meshes, device='cuda'):
 MESH_SAMPLE_MAX_POINTS, MESH_SAMPLE_MAX_BATCH = (1 << 28) - 1, (1 << 24) - 1    # the counter fields of csrc/gpe_mesh_sample.hip
 
 
-def mesh_points_sample(resident, index, mesh_samples, state, ticket, point_noise_w=0.0, f_shift=None, f_scale=None):
+def mesh_points_buffers(resident, B, N):
+    """the outputs and the workspace of mesh_points_sample for B garments of N points: (features, segmentation, status, ws or None).
+    A caller that draws many batches into one place (the statistics fit) allocates them once and passes `out=`; the leading slices
+    [t[:b] for t in ...] serve a smaller last batch."""
+    dev = resident.device
+    return (torch.empty(B, N, 3, device=dev, dtype=F32), torch.empty(B, N, device=dev, dtype=torch.int64),
+            torch.empty(B, device=dev, dtype=torch.int32),
+            torch.empty(B, N, 4, device=dev, dtype=F32) if resident.has_unlabelled else None)
+
+
+def mesh_points_sample(resident, index, mesh_samples, state, ticket, point_noise_w=0.0, f_shift=None, f_scale=None, out=None):
     """The input point clouds of B garments and their segmentation labels drawn on the device: what
     Garment3DPatternFullDataset._get_sample_info (nn/data/datasets.py: _sample_points, _point_classes_from_mesh,
     FeatureStandartization) gives per garment, in at most two launches of csrc/gpe_mesh_sample.hip and with no host read (semantics
@@ -2332,7 +2342,8 @@ def mesh_points_sample(resident, index, mesh_samples, state, ticket, point_noise
 
     resident: mesh_resident(...) on the device; index integer [B]: the garment of every batch slot; f_shift / f_scale: 3 numbers
     each or both None; state int64 [2] = {seed, draw} on the device (stitch_sample_state), advanced by the call; ticket: one zeroed
-    int32 of the caller's, left zero.  -> features fp32 [B, N, 3] (N = mesh_samples), segmentation int64 [B, N], status int32 [B]
+    int32 of the caller's, left zero; out: mesh_points_buffers(resident, B, N) to draw into instead of new tensors.
+    -> features fp32 [B, N, 3] (N = mesh_samples), segmentation int64 [B, N], status int32 [B]
     (>= 0 points that fell back to label 0 for want of a labelled point in their cloud, -1 a garment without a face of positive
     area, -2 index outside 0 .. G - 1; such a slot is all zeros)."""
     if not isinstance(resident, MeshResident):
@@ -2359,10 +2370,13 @@ def mesh_points_sample(resident, index, mesh_samples, state, ticket, point_noise
     import ctypes
     sh = (ctypes.c_float * 3)(*[float(v) for v in f_shift]) if f_shift is not None else None
     sc = (ctypes.c_float * 3)(*[float(v) for v in f_scale]) if f_scale is not None else None
-    features = torch.empty(B, N, 3, device=dev, dtype=F32)
-    seg = torch.empty(B, N, device=dev, dtype=torch.int64)
-    status = torch.empty(B, device=dev, dtype=torch.int32)
-    ws = torch.empty(B, N, 4, device=dev, dtype=F32) if resident.has_unlabelled else None
+    features, seg, status, ws = out if out is not None else mesh_points_buffers(resident, B, N)
+    if out is not None and (
+            features.shape != (B, N, 3) or features.dtype != F32 or seg.shape != (B, N) or seg.dtype != torch.int64
+            or status.shape != (B,) or status.dtype != torch.int32 or (ws is None) != (not resident.has_unlabelled)
+            or (ws is not None and (ws.shape != (B, N, 4) or ws.dtype != F32))
+            or any(t.device != dev or not t.is_contiguous() for t in out if t is not None)):
+        raise ValueError('out must be mesh_points_buffers(resident, %d, %d) (or leading slices of a larger set)' % (B, N))
     L.call('gpe_mesh_points_sample', resident.verts4, resident.faces, resident.vert_off, resident.face_off, resident.face_cdf,
            resident.G, _int32(index, -1, resident.G), B, N, float(point_noise_w), sh, sc, 1 if resident.has_unlabelled else 0, ws,
            state, ticket, features, seg, status)
@@ -2606,6 +2620,130 @@ def standardize(x, shift, scale):
     out = torch.empty_like(x)
     L.call('gpe_standardize', x, x.numel() // C, C, sh, sc, out)
     return out
+
+
+# -------------------------------------------------------------------------------------------------
+# Fitting the standardisation statistics (GarmentBaseDataset._get_distribution_stats / _get_norm_stats, nn/data/datasets.py:534-568)
+# -------------------------------------------------------------------------------------------------
+FIT_LEAF, FIT_MAX_C = 512, 16                    # rows per leaf and columns of csrc/gpe_fit_stats.hip
+FIT_STATUS_EMPTY, FIT_STATUS_NONFINITE = 1, 2    # status bits of the result block (include/gpe_hip_fit.h)
+F64 = torch.float64
+
+
+def fit_leaves(sets, rows_per_set):
+    """the records a part image of `sets` sets of `rows_per_set` rows holds (host only)"""
+    n = L.query('gpe_fit_leaves', int(sets), int(rows_per_set))
+    if n < 0:
+        raise ValueError('fit_leaves: sets and rows_per_set must be positive and their leaves fit 63 bits (got %r, %r)'
+                         % (sets, rows_per_set))
+    return n
+
+
+def _fit_columns(C):
+    if isinstance(C, bool) or not isinstance(C, int) or not 1 <= C <= FIT_MAX_C:
+        raise ValueError('the statistics fit handles 1 .. %d columns (got %r)' % (FIT_MAX_C, C))
+    return C
+
+
+def fit_part(x, part, leaf0=0, padded=False):
+    """One record of 1 + 4 C doubles per leaf (512 rows of one set) of x fp32 [S, N, C], written into the caller's part image (fp64
+    [leaves, 1 + 4 C]) from record leaf0 on: n, then per column mean, squared deviations, min, max over the rows kept (padded: rows
+    with |x| <= 1e-5 in every column are dropped, the reference's _unpad).  One launch of csrc/gpe_fit_stats.hip, no host read."""
+    if not torch.is_tensor(x) or x.dim() != 3:
+        raise ValueError('fit_part: x must be [S, N, C] (got %s)' % (tuple(getattr(x, 'shape', ())),))
+    _dev_check(x)
+    S, N, C = x.shape
+    _fit_columns(C)
+    if not x.is_contiguous():
+        raise ValueError('fit_part: x must be contiguous')
+    if (not torch.is_tensor(part) or part.dtype != F64 or part.dim() != 2 or part.shape[1] != 1 + 4 * C or part.device != x.device
+            or not part.is_contiguous()):
+        raise ValueError('fit_part: part must be a contiguous fp64 [leaves, %d] tensor on the device of x' % (1 + 4 * C))
+    leaves = fit_leaves(S, N)
+    if not 0 <= int(leaf0) <= part.shape[0] - leaves:
+        raise ValueError('fit_part: the %d leaves of x from record %d on do not fit a part image of %d' % (leaves, leaf0, part.shape[0]))
+    L.call('gpe_fit_part', x.detach(), S, N, C, 1 if padded else 0, int(leaf0), part.shape[0], part)
+    return part
+
+
+def fit_finish(part, out=None):
+    """Merges the records of a part image (fit_part) in a fixed order -> the result block, fp64 [2 + 5 C] on the device: n, status,
+    mean [C], std [C], min [C], max [C], norm_scale [C] (include/gpe_hip_fit.h).  One launch, no host read."""
+    if not torch.is_tensor(part) or part.dtype != F64 or part.dim() != 2 or part.shape[0] < 1 or (part.shape[1] - 1) % 4 or not part.is_contiguous():
+        raise ValueError('fit_finish: part must be a contiguous fp64 [leaves, 1 + 4 C] tensor')
+    if not part.is_cuda:
+        raise RuntimeError('gpe ops need tensors on the MI355X (got a %s part image); there is no CPU path' % part.device)
+    C = _fit_columns((part.shape[1] - 1) // 4)
+    if out is None:
+        out = torch.empty(2 + 5 * C, device=part.device, dtype=F64)
+    elif out.dtype != F64 or tuple(out.shape) != (2 + 5 * C,) or out.device != part.device or not out.is_contiguous():
+        raise ValueError('fit_finish: out must be a contiguous fp64 [%d] tensor on the device of part' % (2 + 5 * C))
+    L.call('gpe_fit_finish', part, part.shape[0], C, out)
+    return out
+
+
+def fit_read(result):
+    """the result block of fit_finish on the host (ONE device read), rounded to fp32 once like the reference's fp32 results ->
+    {'n': int, 'status': int, 'mean' / 'std' / 'min' / 'max' / 'norm_scale': fp32 numpy [C]}; ValueError when no row was left"""
+    r = result.detach().cpu().numpy()
+    C = (r.size - 2) // 5
+    status = int(r[1])
+    if status & FIT_STATUS_EMPTY:
+        raise ValueError('the statistics fit found no row (every row was dropped as padding)')
+    keys = ('mean', 'std', 'min', 'max', 'norm_scale')
+    out = {k: r[2 + i * C:2 + (i + 1) * C].astype(np.float32) for i, k in enumerate(keys)}
+    out.update(n=int(r[0]), status=status)
+    return out
+
+
+class FitAccumulator:
+    """The statistics of a data set that is handed in as chunks of whole sets:
+
+        acc = FitAccumulator(3, G, 2000, 'cuda')
+        for chunk in ...: acc.add(points)            # fp32 [g, 2000, 3] on the device, consecutive sets
+        stats = acc.read()                           # {'n', 'mean', 'std', 'min', 'max', 'norm_scale', 'status'}
+
+    The part image depends on (sets, rows_per_set) and the data alone, so the result is bit-identical for every chunking, grid size
+    and CU reservation.  Nothing reads the host before read()."""
+
+    def __init__(self, C, sets, rows_per_set, device, padded=False):
+        self.C = _fit_columns(C)
+        for name, v in (('sets', sets), ('rows_per_set', rows_per_set)):
+            if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+                raise ValueError('FitAccumulator: %s must be a positive integer (got %r)' % (name, v))
+        self.sets, self.rows_per_set, self.padded = sets, rows_per_set, bool(padded)
+        self.device = torch.device(device)
+        if self.device.type != 'cuda':
+            raise RuntimeError('gpe ops need tensors on the MI355X (got device %s); there is no CPU path' % self.device)
+        self.leaves = fit_leaves(sets, rows_per_set)
+        self.part = torch.empty(self.leaves, 1 + 4 * self.C, device=self.device, dtype=F64)
+        self.added, self.result = 0, None
+
+    def add(self, x):
+        """x: fp32 [g, rows_per_set, C] on the device: the next g sets"""
+        if (not torch.is_tensor(x) or x.dim() != 3 or x.shape[0] < 1 or tuple(x.shape[1:]) != (self.rows_per_set, self.C)
+                or x.dtype != F32):
+            raise ValueError('FitAccumulator.add: fp32 [g >= 1, %d, %d] expected (got %s %s)'
+                             % (self.rows_per_set, self.C, getattr(x, 'dtype', type(x).__name__), tuple(getattr(x, 'shape', ()))))
+        if x.device != self.part.device:
+            raise ValueError('FitAccumulator.add: x lives on %s, the accumulator on %s' % (x.device, self.part.device))
+        if self.added + x.shape[0] > self.sets:
+            raise ValueError('FitAccumulator.add: %d sets after %d, but %d were announced' % (x.shape[0], self.added, self.sets))
+        fit_part(x.contiguous(), self.part, self.added * (self.leaves // self.sets), self.padded)
+        self.added += x.shape[0]
+        self.result = None
+
+    def finish(self):
+        """-> the result block on the device (fit_finish); every announced set must have been added"""
+        if self.added != self.sets:
+            raise ValueError('FitAccumulator.finish: %d of the %d announced sets were added' % (self.added, self.sets))
+        if self.result is None:
+            self.result = fit_finish(self.part)
+        return self.result
+
+    def read(self):
+        """-> fit_read(finish()): the one host read"""
+        return fit_read(self.finish())
 
 
 # -------------------------------------------------------------------------------------------------

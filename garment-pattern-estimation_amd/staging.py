@@ -9,7 +9,10 @@ StitchPairSampler is the input side of the edge-pair classifier's training (Garm
 nn/data/datasets.py:985-1132): the data set's 3D edges and stitches stay in HBM and every step's pair rows are drawn there.
 
 MeshPointSampler is the input side of the encoder / decoder step (Garment3DPatternFullDataset._get_sample_info): the data set's
-meshes stay in HBM and every step's point clouds and segmentation labels are drawn there."""
+meshes stay in HBM and every step's point clouds and segmentation labels are drawn there.
+
+The statistics both samplers standardise with are fitted on the device as well (fit_feature_stats of either sampler,
+fit_pattern_standardization for the ground truth: the reference's standardize(training), nn/data/datasets.py:596-645, 1018-1041)."""
 import torch
 
 from . import ops
@@ -35,6 +38,69 @@ class BatchStager:
         return out
 
 
+def _fit_index(index, device):
+    """the training garments of a statistics fit as an integer [G'] tensor on the device"""
+    if not torch.is_tensor(index):
+        index = torch.as_tensor(index)
+    if index.dim() != 1 or index.numel() < 1 or index.is_floating_point() or index.is_complex() or index.dtype == torch.bool:
+        raise ValueError('index must be an integer [G] tensor or sequence, G >= 1: the garments the statistics are fitted on')
+    return index.to(device)
+
+
+def _fit_chunk(chunk):
+    if isinstance(chunk, bool) or not isinstance(chunk, int) or chunk < 1:
+        raise ValueError('chunk must be a positive integer: the garments drawn per launch (got %r)' % (chunk,))
+    return chunk
+
+
+def _fit_status_check(status, message):
+    """the one host read of a fit's per-garment status words"""
+    bad = (status.cpu() < 0).nonzero()
+    if bad.numel():
+        raise ValueError(message % int(bad[0]))
+
+
+def fit_pattern_standardization(ground_truth, feature_stats):
+    """The reference's config['standardize'] of a pattern-model experiment (Garment3DPatternFullDataset.standardize,
+    nn/data/datasets.py:612-645), with the ground-truth statistics fitted on the device from the training garments' resident
+    tensors: ground_truth = {'outlines' [G, P, L, E], 'rotations' [G, P, R], 'translations' [G, P, T], 'stitch_tags' [G, P, L, D]},
+    fp32 on the device; feature_stats = {'f_shift', 'f_scale'} (MeshPointSampler.fit_feature_stats).
+      outlines                                   mean / std over the un-padded edge rows, gt_shift['outlines'][0] = [1] = 0 (:618)
+      rotations, translations, stitch_tags       min / norm_scale over all rows (zero is a valid value there)
+    -> {'f_shift', 'f_scale', 'gt_shift': {...}, 'gt_scale': {...}} of fp32 numpy arrays, as MeshPointSampler.from_config,
+    metrics.ComposedPatternLoss and ops.pattern_decode take it.  Four pairs of launches, then one host read per tensor."""
+    keys = ('outlines', 'rotations', 'translations', 'stitch_tags')
+    if not isinstance(ground_truth, dict) or any(k not in ground_truth for k in keys):
+        raise ValueError('ground_truth must hold the device tensors %s' % (keys,))
+    if not isinstance(feature_stats, dict) or any(k not in feature_stats for k in ('f_shift', 'f_scale')):
+        raise ValueError("feature_stats must hold 'f_shift' and 'f_scale'")
+    dims = {'outlines': 4, 'rotations': 3, 'translations': 3, 'stitch_tags': 4}
+    G = None
+    for k in keys:
+        t = ground_truth[k]
+        if not torch.is_tensor(t) or t.dim() != dims[k] or t.dtype != torch.float32 or not 1 <= t.shape[-1] <= ops.FIT_MAX_C or t.numel() < 1:
+            raise ValueError('ground_truth[%r] must be an fp32 %d-dimensional tensor of 1 .. %d columns (got %s %s)'
+                             % (k, dims[k], ops.FIT_MAX_C, getattr(t, 'dtype', type(t).__name__), tuple(getattr(t, 'shape', ()))))
+        G = t.shape[0] if G is None else G
+        if t.shape[0] != G:
+            raise ValueError('the ground-truth tensors hold %d and %d garments' % (G, t.shape[0]))
+    blocks = {}
+    for k in keys:                                    # every launch first, the host reads after
+        t = ground_truth[k].detach()
+        x = t.reshape(G, -1, t.shape[-1])
+        acc = ops.FitAccumulator(x.shape[2], G, x.shape[1], x.device, padded=(k == 'outlines'))
+        acc.add(x)
+        blocks[k] = acc.finish()
+    f32 = lambda v: torch.as_tensor(v).detach().cpu().numpy().astype('float32')        # noqa: E731
+    out = {'f_shift': f32(feature_stats['f_shift']), 'f_scale': f32(feature_stats['f_scale']), 'gt_shift': {}, 'gt_scale': {}}
+    for k in keys:
+        r = ops.fit_read(blocks[k])
+        out['gt_shift'][k], out['gt_scale'][k] = (r['mean'], r['std']) if k == 'outlines' else (r['min'], r['norm_scale'])
+    # the mean of the edge vectors is zero by the loop property, and shifting them would break it (:616-618)
+    out['gt_shift']['outlines'][:2] = 0
+    return out
+
+
 class StitchPairSampler:
     """Fresh training pairs of the stitch classifier for every step, drawn on the device from a resident data set: what
     GarmentStitchPairsDataset._get_sample_info (nn/data/datasets.py:1119-1122: NNSewingPattern.stitches_as_3D_pairs, then
@@ -42,7 +108,8 @@ class StitchPairSampler:
     keyword names and defaults are those of the data set's config.
 
     edges3d [G, P, L, Fe] fp32, num_edges [G, P], gt_stitches [G, 2, S] (edge ids panel * L + edge), gt_num_stitches [G]: the layout
-    StitchOnEdge3DPairs.evaluate_stitches takes; data_stats: {'f_shift', 'f_scale'} of the pair rows.
+    StitchOnEdge3DPairs.evaluate_stitches takes; data_stats: {'f_shift', 'f_scale'} of the pair rows, or None for a new experiment:
+    sample() then raises until fit_feature_stats(index) has fitted them on the device (or f_shift / f_scale are set).
 
         sampler = StitchPairSampler(edges3d, num_edges, gt_stitches, gt_num_stitches, stats)
         sg = graph.StepGraph(lambda idx: (lambda r, y: model.loss(model(r), y)[:2])(*sampler.sample(idx)), opt)
@@ -57,8 +124,8 @@ class StitchPairSampler:
                  non_stitched_edge_pairs_num=200, shuffle_pairs=True, shuffle_pairs_order=True, seed=0):
         self.edges3d, self.num_edges, self.gt_stitches, self.gt_num_stitches = ops.stitch_sample_resident(
             edges3d, num_edges, gt_stitches, gt_num_stitches)
-        self.f_shift = [float(v) for v in data_stats['f_shift']]
-        self.f_scale = [float(v) for v in data_stats['f_scale']]
+        self.f_shift = [float(v) for v in data_stats['f_shift']] if data_stats else None
+        self.f_scale = [float(v) for v in data_stats['f_scale']] if data_stats else None
         self.stitched_edge_pairs_num = int(stitched_edge_pairs_num)
         self.non_stitched_edge_pairs_num = int(non_stitched_edge_pairs_num)
         self.shuffle_pairs, self.shuffle_pairs_order = bool(shuffle_pairs), bool(shuffle_pairs_order)
@@ -80,11 +147,46 @@ class StitchPairSampler:
 
     def sample(self, index):
         """index: integer [B] tensor on the device -> (rows fp32 [B, R, 2 Fe], labels bool [B, R])"""
+        if self.f_shift is None:
+            raise RuntimeError('StitchPairSampler was built without statistics (data_stats=None): call fit_feature_stats(index) '
+                               'or set f_shift / f_scale before sample()')
         rows, labels, self.status = ops.stitch_pairs_sample(
             self.edges3d, self.num_edges, self.gt_stitches, self.gt_num_stitches, index, self.stitched_edge_pairs_num,
             self.non_stitched_edge_pairs_num, self.f_shift, self.f_scale, self.state, self.ticket, self.shuffle_pairs,
             self.shuffle_pairs_order)
         return rows, labels
+
+    def fit_feature_stats(self, index, seed=0, chunk=256, install=True):
+        """The pair rows' statistics of a new experiment, fitted on the device: what GarmentStitchPairsDataset.standardize(training)
+        (nn/data/datasets.py:1034: _get_norm_stats of one sample per training garment) computes on the host.  Draws the rows of
+        every garment of `index` (an integer [G'] tensor or sequence) with shift 0 / scale 1 and the sampler's own settings, `chunk`
+        garments per launch, and accumulates them (ops.FitAccumulator).
+        -> {'f_shift': min, 'f_scale': norm_scale} as fp32 numpy [2 Fe]; with `install` they become the sampler's own statistics.
+
+        The draws come from a generator state of their own, (seed, 0) advanced once per chunk; the sampler's `.state` is left as it
+        was.  The result is a function of (seed, chunk, index, data).  A garment whose status is negative (-1 more stitches than
+        stitched_edge_pairs_num, -2 outside the set) raises after the last chunk: one host read at the end, none per chunk."""
+        index, chunk = _fit_index(index, self.device), _fit_chunk(chunk)
+        G, C = index.numel(), 2 * self.edges3d.shape[3]
+        R = self.stitched_edge_pairs_num + self.non_stitched_edge_pairs_num
+        acc = ops.FitAccumulator(C, G, R, self.device)
+        state = ops.stitch_sample_state(seed, 0, self.device)
+        status = []
+        for g0 in range(0, G, chunk):
+            rows, _, st = ops.stitch_pairs_sample(
+                self.edges3d, self.num_edges, self.gt_stitches, self.gt_num_stitches, index[g0:g0 + chunk],
+                self.stitched_edge_pairs_num, self.non_stitched_edge_pairs_num, [0.0] * C, [1.0] * C, state, self.ticket,
+                self.shuffle_pairs, self.shuffle_pairs_order)
+            acc.add(rows)
+            status.append(st)
+        result = acc.finish()
+        _fit_status_check(torch.cat(status), 'fit_feature_stats: garment %d of the index has more stitches than '
+                                             'stitched_edge_pairs_num or lies outside the set')
+        r = ops.fit_read(result)
+        stats = {'f_shift': r['min'], 'f_scale': r['norm_scale']}
+        if install:
+            self.f_shift, self.f_scale = [float(v) for v in stats['f_shift']], [float(v) for v in stats['f_scale']]
+        return stats
 
 
 class MeshPointSampler:
@@ -134,3 +236,34 @@ class MeshPointSampler:
         features, segmentation, self.status = ops.mesh_points_sample(
             self.resident, index, self.mesh_samples, self.state, self.ticket, self.point_noise_w, self.f_shift, self.f_scale)
         return features, segmentation
+
+    def fit_feature_stats(self, index, seed=0, chunk=256, install=True):
+        """The feature statistics of a new experiment, fitted on the device: what Garment3DPatternFullDataset.standardize(training)
+        (nn/data/datasets.py:612: _get_distribution_stats of one sample per training garment) computes on the host.  Draws one
+        unstandardised cloud (the sampler's mesh_samples and point_noise_w) per garment of `index` (an integer [G'] tensor or sequence:
+        the training garments), `chunk` garments per launch into one reused buffer, and accumulates them (ops.FitAccumulator).
+        -> {'f_shift': mean, 'f_scale': std} as fp32 numpy [3]; with `install` they become the sampler's own statistics.
+
+        The draws come from a generator state of their own, (seed, 0) advanced once per chunk; the sampler's `.state` is left as it
+        was.  The result is a function of (seed, chunk, index, data) — bit-identical for every grid size and CU reservation.  A
+        garment whose status is negative (-1 no face of positive area, -2 outside the set) raises after the last chunk: there is
+        one host read at the end and none per chunk."""
+        index, chunk = _fit_index(index, self.device), _fit_chunk(chunk)
+        G, N = index.numel(), self.mesh_samples
+        acc = ops.FitAccumulator(3, G, N, self.device)
+        state = ops.stitch_sample_state(seed, 0, self.device)
+        buffers = ops.mesh_points_buffers(self.resident, min(chunk, G), N)
+        status = torch.empty(G, device=self.device, dtype=torch.int32)
+        for g0 in range(0, G, chunk):
+            b = min(chunk, G - g0)
+            out = tuple(t[:b] if t is not None else None for t in buffers[:2] + buffers[3:])
+            out = (out[0], out[1], status[g0:g0 + b], out[2])
+            ops.mesh_points_sample(self.resident, index[g0:g0 + b], N, state, self.ticket, self.point_noise_w, None, None, out=out)
+            acc.add(out[0])
+        result = acc.finish()
+        _fit_status_check(status, 'fit_feature_stats: garment %d of the index has no face of positive area or lies outside the set')
+        r = ops.fit_read(result)
+        stats = {'f_shift': r['mean'], 'f_scale': r['std']}
+        if install:
+            self.f_shift, self.f_scale = [float(v) for v in stats['f_shift']], [float(v) for v in stats['f_scale']]
+        return stats
