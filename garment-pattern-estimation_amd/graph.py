@@ -22,6 +22,21 @@ FusedAdam's guarded step (max_grad_norm / skip_nonfinite / guard_overflow / para
 the clip factor and the skip flag live in device memory and the Adam launch reads them there; optimizer.grad_norm, .skipped, ... are static
 tensors that every replay overwrites, like `loss`.
 
+The rule for control flow: which launches a step makes must be a function of the tensor SHAPES, of the non-tensor arguments of
+step() and of `key` — nothing else.  Non-tensor arguments (an epoch, a flag; leaves of nested dicts / lists / tuples too) are handed to
+forward_loss as given, at every call; `key` is an optional callable, evaluated at every step, for whatever forward_loss reads from
+outside its arguments (a closure over the trainer's epoch).  When any of these values differs from the previous step's, the graph is
+dropped, that step runs eagerly (lazily built state of the new branch — workspaces, pack plans — must exist before a capture), and the
+next step is captured again:
+
+    sg = StepGraph(lambda f, g, epoch: model.loss(model(f), g, epoch=epoch)[0], optimizer)
+    loss = sg.step(feats, gt, epoch)                                  # re-captured whenever `epoch` changes
+    sg = StepGraph(lambda f, g: model.loss(model(f), g, epoch=trainer.epoch)[0], optimizer,
+                   key=lambda: trainer.epoch >= model.loss.config['epoch_with_stitches'])      # re-captured when the loss changes
+
+A forward_loss that reads anything else (an outer variable that no argument and no `key` reflects) gets, in every replay, the
+value it had at the capture: a replay runs no Python.  invalidate() drops the graph by hand.
+
 One process per GPU, world size 1: a gradient exchange inside the captured region is not supported (RCCL launches are not captured
 here).  The captured step is single-stream; the tensors a replay returns are static buffers, overwritten by the next replay."""
 import ctypes
@@ -65,25 +80,31 @@ class HostDrawn:
 
 
 class StepGraph:
-    def __init__(self, forward_loss, optimizer, warmup=2, device=None):
+    def __init__(self, forward_loss, optimizer, warmup=2, device=None, key=None):
         """forward_loss(*inputs) -> scalar loss tensor (forward + loss; backward and optimizer.step() are run here), or a tuple /
         list whose first element is that loss: what follows it (tensors, or nested dicts / lists / tuples of tensors — a loss dict)
         is kept, detached, as the tuple `self.extras`: the step's own values during the warm-up, from the capture on the static
         tensors that every replay overwrites (None for a plain tensor return).  step() returns the loss either way.
+        Non-tensor inputs reach forward_loss as the current call gave them; a change of one drops the graph (module docstring).
         optimizer: optim.FusedAdam.  warmup: eager steps before the capture (>= 1: lazily built state — pack plans, workspaces,
-        kernel attributes — must exist before a capture)."""
+        kernel attributes — must exist before a capture).  key: optional callable without arguments, evaluated at every step; its
+        value is compared like a non-tensor input (it names the branch of the step that forward_loss takes for reasons its
+        arguments do not show)."""
         if not (hasattr(optimizer, 'step_captured') and hasattr(optimizer, 'advance_captured')):
             raise TypeError('StepGraph needs an optimizer whose step-dependent scalars live in device memory (optim.FusedAdam); a '
                             'torch optimizer bakes them into its kernels\' arguments')
         self.forward_loss = forward_loss
         self.opt = optimizer
         self.warmup = max(int(warmup), 1)
+        self.key = key
         self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
         self.stream = torch.cuda.Stream(device=self.device)
         self.host = HostDrawn(self.device)
         self.calls = 0
         self.graph = None
         self.static_in = None
+        self.leaves = None           # the non-tensor leaves of the last step's inputs, in order, and the value of `key`
+        self.eager_left = self.warmup
         self.loss = None
         self.extras = None
         self.guards = []             # (HalfActGuard, amax word) pairs met during the capture
@@ -115,15 +136,72 @@ class StepGraph:
             return type(obj)(self._like(v) for v in obj)
         return obj
 
+    def _leaves(self, obj, out):
+        """the non-tensor leaves of `obj`, in the order _flat walks it"""
+        if isinstance(obj, torch.Tensor):
+            pass
+        elif isinstance(obj, dict):
+            for k in obj:
+                self._leaves(obj[k], out)
+        elif isinstance(obj, (list, tuple)):
+            for v in obj:
+                self._leaves(v, out)
+        else:
+            out.append(obj)
+        return out
+
+    def _merge(self, static, obj):
+        """the structure of `obj` with the static tensors in place of its tensors: non-tensor leaves are those of THIS call"""
+        if isinstance(obj, torch.Tensor):
+            if not isinstance(static, torch.Tensor):
+                raise self._changed()
+            return static
+        if isinstance(obj, dict):
+            if not isinstance(static, dict) or list(static) != list(obj):
+                raise self._changed()
+            return {k: self._merge(static[k], v) for k, v in obj.items()}
+        if isinstance(obj, (list, tuple)):
+            if type(static) is not type(obj) or len(static) != len(obj):
+                raise self._changed()
+            return type(obj)(self._merge(s, v) for s, v in zip(static, obj))
+        if isinstance(static, (torch.Tensor, dict, list, tuple)):
+            raise self._changed()
+        return obj
+
+    @staticmethod
+    def _changed():
+        return RuntimeError('StepGraph: the inputs changed shape or type; a captured step is one fixed shape')
+
+    @staticmethod
+    def _same(a, b):
+        try:
+            return type(a) is type(b) and bool(a == b)
+        except Exception:                    # (a leaf whose == has no truth value: compare by identity)
+            return a is b
+
     def _stage(self, inputs):
         if self.static_in is None:
             self.static_in = self._like(inputs)
         dst, src = self._flat(self.static_in, []), self._flat(inputs, [])
         if len(dst) != len(src) or any(d.shape != s.shape or d.dtype != s.dtype for d, s in zip(dst, src)):
-            raise RuntimeError('StepGraph: the inputs changed shape or type; a captured step is one fixed shape')
+            raise self._changed()
+        self.static_in = self._merge(self.static_in, inputs)
+        leaves = self._leaves(inputs, [])
+        if self.key is not None:
+            leaves.append(self.key())
+        was = self.leaves
+        if was is not None and (len(was) != len(leaves) or not all(self._same(a, b) for a, b in zip(was, leaves))):
+            self.invalidate()
+            self.eager_left = max(self.eager_left, 1)      # the new branch builds its lazy state before a capture
+        self.leaves = leaves
         for d, s in zip(dst, src):
             if d.data_ptr() != s.data_ptr():
                 d.copy_(s, non_blocking=True)
+
+    def invalidate(self):
+        """Drop the captured graph: the next step past the warm-up captures again.  The static input buffers, the host-drawn
+        tensors and the step counters stay."""
+        self.graph = None
 
     def _detached(self, obj):
         if isinstance(obj, torch.Tensor):
@@ -190,7 +268,8 @@ class StepGraph:
             try:
                 self.host.begin_step()
                 self.calls += 1
-                if self.calls <= self.warmup:
+                if self.eager_left > 0:
+                    self.eager_left -= 1
                     return self._eager()
                 if self.graph is None:
                     self._capture()
