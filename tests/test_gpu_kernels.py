@@ -1634,8 +1634,12 @@ def test_half_activation_guard(gpe):
         gpe.set_math(prev)
 
 
-@pytest.mark.parametrize('B,N', [(8, 512), (9, 457)])
-def test_lazy_dz3_matches_the_in_place_pass(gpe, B, N):
+@pytest.mark.parametrize('B,N,H,Fo', [pytest.param(8, 512, 200, 150, id='8-512'), pytest.param(9, 457, 200, 150, id='9-457'),
+                                      # the other widths gpe_edge_lazy_dz3_ok admits: F at the top of tile class 10 (160) and in class 13
+                                      # (208: B3 at (13,13), the single-role split kernel's lazy instance), behind class-13 widths
+                                      pytest.param(8, 512, 208, 160, id='8-512-208-160'),
+                                      pytest.param(8, 512, 196, 208, id='8-512-196-208')])
+def test_lazy_dz3_matches_the_in_place_pass(gpe, B, N, H, Fo):
     """f16x3, k = 16, above the size gate: the aggregated block's activation is stored in fp16 and its backward never materialises
     dz3 — the weight-gradient
     reduce-GEMM and the propagation kernel form it from the stored activation while staging it (include/gpe_hip.h "lazy dz3").
@@ -1645,18 +1649,19 @@ def test_lazy_dz3_matches_the_in_place_pass(gpe, B, N):
     # (8, 512): E = 65 536 rows, the smallest launch the lazy path takes; (9, 457): 4113 points — a ragged last tile in both
     # consumers (one point of the 64-row propagation tile, 16 of the reduce-GEMM's 32 rows) and clouds that are not pinned to XCDs
     C, k = 3, 16
-    oconv = _oracle_conv(C, 200, 150, k, seed=5)                 # includes negative BatchNorm scales: the min side
-    conv = _product_conv(gpe, oconv, C, 200, 150, k).train()
+    oconv = _oracle_conv(C, H, Fo, k, seed=5)                    # includes negative BatchNorm scales: the min side
+    conv = _product_conv(gpe, oconv, C, H, Fo, k).train()
     g = torch.Generator().manual_seed(6)
     x = torch.randn(B * N, C, generator=g)
-    wgt = torch.randn(B * N, 150, generator=g)
+    wgt = torch.randn(B * N, Fo, generator=g)
     prev = gpe.set_math('f16x3')
     try:
-        assert L.query('gpe_edge_lazy_dz3_ok', B, N, k, 150, 200) == 1
+        assert L.query('gpe_edge_lazy_dz3_ok', B, N, k, Fo, H) == 1
+        assert L.query('gpe_edge_lazy_dz3_ok', B, N, k, Fo, 160) == 0     # a previous width of tile class 10 is refused
         res = {}
         for flag in (0, 512):
             L.query('gpe_debug_set', flag)
-            assert L.query('gpe_edge_lazy_dz3_ok', B, N, k, 150, 200) == (0 if flag else 1)
+            assert L.query('gpe_edge_lazy_dz3_ok', B, N, k, Fo, H) == (0 if flag else 1)
             for p_ in conv.parameters():
                 p_.grad = None
             xd = x.cuda().requires_grad_()
@@ -1669,6 +1674,8 @@ def test_lazy_dz3_matches_the_in_place_pass(gpe, B, N):
     assert torch.equal(res[0][0], res[512][0])                   # same forward
     # (the lazy run also keeps a3 in fp16 — include/gpe_hip.h "out_half" — which moves the gradients by 2e-6 / 5e-6 of their
     # maximum at the encoder's sizes, profiles/r04_h_row_g_probe.txt)
+    print('lazy dz3 H=%d Fo=%d B=%d N=%d: lazy vs eager dx %.2e dparam %.2e' % (
+        H, Fo, B, N, relerr(res[0][1], res[512][1]), max(relerr(res[0][2][n], res[512][2][n]) for n in res[0][2])))
     assert relerr(res[0][1], res[512][1]) < 1e-5
     for n in res[0][2]:
         assert relerr(res[0][2][n], res[512][2][n]) < 3e-5, n
@@ -1683,6 +1690,9 @@ def test_lazy_dz3_matches_the_in_place_pass(gpe, B, N):
     # eager pass agree element by element above)
     # (the oracle here does not stand on the build's decisions — tests/relu_align.py does that for the model tests — so the bar
     # only guards against gross errors: measured 8.3e-4 on dx at (9, 457), 1e-4 at (8, 512), identical for the eager pass)
+    print('lazy dz3 H=%d Fo=%d B=%d N=%d: vs fp64 oracle fwd %.2e dx %.2e (Frobenius) dparam %.2e (Frobenius)' % (
+        H, Fo, B, N, relerr(res[0][0], yr), relerr_fro(res[0][1], xr.grad),
+        max(relerr_fro(res[0][2][n], p_.grad) for n, p_ in o64.named_parameters())))
     assert relerr(res[0][0], yr) < 5e-5
     assert relerr_fro(res[0][1], xr.grad) < 2e-3
     for n, p_ in o64.named_parameters():
