@@ -43,17 +43,8 @@ class DynamicEdgeConv(nn.Module):
 
     def forward(self, x, n_clouds, n_points, order=None):
         """order: the previous EdgeConv layer's `last_order` (a speed hint for this layer's graph search; results do not depend on it)"""
-        nb = len(self.nn)
-        blocks = [self.nn[i] for i in range(nb)]
-        lin = [b[0] for b in blocks]
-        bn = [b[2] for b in blocks]
-        eps, mom = bn[0].eps, bn[0].momentum
-        args = []
-        for l, b in zip(lin, bn):
-            args += [l.weight, l.bias, b.weight, b.bias]
-        for b in bn:
-            args += [b.running_mean, b.running_var, b.num_batches_tracked]
-        H0 = lin[0].weight.shape[0]
+        eps, mom, nb, args = ops.mlp_tensors(self.nn)
+        H0 = self.nn[0][0].weight.shape[0]
         if H0 % 4 or H0 > 256:
             # a first-block width the fused P|Q kernels do not take: the general (explicit-message) formulation
             out, idx = ops.edge_conv_general(x, n_clouds, n_points, self.k, self.training, eps, mom, nb, self.aggr, args)
@@ -72,27 +63,18 @@ class DynamicEdgeConv(nn.Module):
             raise ValueError('unknown route %r (choose from %s)' % (route, ops.EDGE_PREDICT_ROUTES))
         if self.training:
             raise RuntimeError('DynamicEdgeConv.predict is a prediction path: call .eval() first (BatchNorm running statistics)')
-        nb = len(self.nn)
-        blocks = [self.nn[i] for i in range(nb)]
-        lin = [b[0] for b in blocks]
-        bn = [b[2] for b in blocks]
-        args = []
-        for l, b in zip(lin, bn):
-            args += [l.weight, l.bias, b.weight, b.bias]
-        for b in bn:
-            args += [b.running_mean, b.running_var, b.num_batches_tracked]
-        H0 = lin[0].weight.shape[0]
+        eps, mom, nb, args = ops.mlp_tensors(self.nn)
+        H0 = self.nn[0][0].weight.shape[0]
         if H0 % 4 or H0 > 256:
             # a first-block width off the P|Q menu: the general formulation, as in forward
             if route == 'fused':
                 raise ValueError("route='fused' needs a first-block width <= 256 that is a multiple of 4 (got %d)" % H0)
             with torch.no_grad():
-                out, idx = ops.edge_conv_general(x.detach(), n_clouds, n_points, self.k, False, bn[0].eps, bn[0].momentum, nb,
-                                                 self.aggr, args)
+                out, idx = ops.edge_conv_general(x.detach(), n_clouds, n_points, self.k, False, eps, mom, nb, self.aggr, args)
             self.last_order = None
         else:
             out, idx, self.last_order = ops.edge_conv_predict(x, n_clouds, n_points, self.k, nb, self.aggr, args, order=order,
-                                                              route=route, eps=bn[0].eps)
+                                                              route=route, eps=eps)
         self.last_knn = idx
         return out
 

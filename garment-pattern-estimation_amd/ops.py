@@ -550,6 +550,122 @@ def bn_bwd_coef(part, nblk, stats, C, count, gamma=None, beta=None, training=Tru
     return coef, dg, db
 
 
+def bn_stats(blk, eps, training=False, momentum=None, part=None, nblk=0, count=0):
+    """-> the BatchNorm stat block of the MLPBlock `blk`: from this batch's partial sums, or in eval mode from the running statistics"""
+    if training:
+        return bn_finalize(part, nblk, blk.W.shape[0], count, blk.gamma, blk.beta, eps, momentum, blk.running_mean, blk.running_var,
+                           blk.num_batches_tracked)
+    return bn_from_running(blk.running_mean, blk.running_var, blk.gamma, blk.beta, eps)
+
+
+# -------------------------------------------------------------------------------------------------
+# the tensors of a net_blocks.MLP as autograd takes them: flat, 4 parameters per block, then 3 buffers per block
+# -------------------------------------------------------------------------------------------------
+MLP_PARAMS, MLP_BUFFERS = ('W', 'b', 'gamma', 'beta'), ('running_mean', 'running_var', 'num_batches_tracked')
+MLPBlock = collections.namedtuple('MLPBlock', MLP_PARAMS + MLP_BUFFERS, defaults=(None,) * len(MLP_BUFFERS))
+
+
+def mlp_tensors(mlp):
+    """mlp: the nn.Sequential parameter container built by net_blocks.MLP -> (eps, momentum, nb, the flat tuple of its tensors)"""
+    blocks = [mlp[i] for i in range(len(mlp))]
+    flat = [t for lin, _, bn in blocks for t in (lin.weight, lin.bias, bn.weight, bn.bias)]
+    flat += [t for _, _, bn in blocks for t in (bn.running_mean, bn.running_var, bn.num_batches_tracked)]
+    return blocks[0][2].eps, blocks[0][2].momentum, len(blocks), tuple(flat)
+
+
+def mlp_blocks(tensors, nb):
+    """the inverse of mlp_tensors: nb MLPBlock records (of the 4 nb parameters alone, as a backward saves them: no buffers, None)"""
+    P, Q = len(MLP_PARAMS), len(MLP_BUFFERS)
+    return [MLPBlock(*tensors[P * l: P * l + P], *tensors[P * nb + Q * l: P * nb + Q * l + Q]) for l in range(nb)]
+
+
+def mlp_grads(lead, nb, filed=None, gx=None):
+    """What the backward of a Function whose forward took (x, lead - 1 more arguments, *mlp_tensors) returns: gx, None up to the tensors,
+    the gradients `filed` as {(block, parameter field): tensor} at their places in mlp_tensors' order, None for every buffer"""
+    out = [gx] + [None] * (lead - 1 + (len(MLP_PARAMS) + len(MLP_BUFFERS)) * nb)
+    for (l, field), g in (filed or {}).items():
+        out[lead + len(MLP_PARAMS) * l + MLP_PARAMS.index(field)] = g
+    return tuple(out)
+
+
+def save_groups(ctx, **groups):
+    """ctx.save_for_backward of named groups, flattened in the order given; a group is one tensor or a list of tensors"""
+    ctx.saved_groups = [(name, len(g) if isinstance(g, (list, tuple)) else None) for name, g in groups.items()]
+    ctx.save_for_backward(*[t for g in groups.values() for t in (g if isinstance(g, (list, tuple)) else (g,))])
+
+
+def saved_groups(ctx):
+    """-> {name: group} of what save_groups(ctx, ...) saved"""
+    sv, at, out = ctx.saved_tensors, 0, {}
+    for name, n in ctx.saved_groups:
+        out[name] = sv[at] if n is None else list(sv[at: at + n])
+        at += 1 if n is None else n
+    return out
+
+
+# -------------------------------------------------------------------------------------------------
+# the three big edge entry points by keyword (include/gpe_hip.h): each ends in its one L.call, arguments in the header's order
+# -------------------------------------------------------------------------------------------------
+EdgeSrc = collections.namedtuple('EdgeSrc', 'pq ldpq jg t ld')   # the rows an edge kernel reads: gathered relu(P_i + Q_j), or dense [E][ld]
+NO_LAZY = (None, 0, None, None, 0, None)                         # lz_g, lz_ldg, lz_amx, lz_amn, lz_ldagg, lz_coef: no lazy dz3
+
+
+def edge_gathered(PQ, jg):
+    return EdgeSrc(PQ, PQ.stride(0), jg, None, 0)
+
+
+def edge_rows(t):
+    return EdgeSrc(None, 0, None, t, t.stride(0))
+
+
+def edge_mlp_fwd(*, src, dims, Cin, Cout, wp, bias, out, ldo, stats_part, agg, ldagg, amax_a, amax_out, ws, out_half):
+    """dims = (B, N, k); agg = (mx, mn, amx, amn), [B*N][ldagg] each, or None; ws = edge_workspace(...)"""
+    mx, mn, amx, amn = agg or (None, None, None, None)
+    L.call('gpe_edge_mlp_fwd', int(src.pq is None), *src, *dims, Cin, Cout, wp, bias, out, ldo, stats_part, int(agg is not None),
+           mx, mn, amx, amn, ldagg, amax_a, amax_out, *ws, out_half)
+
+
+def edge_redgemm(*, u, ldu, v, v_shift, dims, Mg, Ng, G, ldG, colsum, part, amax_u, amax_v, ws, lazy=NO_LAZY):
+    L.call('gpe_edge_redgemm', u, ldu, int(v.pq is None), v.t, v.ld, v.pq, v.ldpq, v.jg, v_shift, *dims, Mg, Ng, G, ldG, colsum, part,
+           amax_u, amax_v, *ws, *lazy)
+
+
+def edge_mlp_bwd(*, a, lda, act, dims, Cin, Cout, wp, coef, out, ldo, dP, lddp, amax_a, amax_out, ws, lazy=NO_LAZY):
+    """act: the edge_gathered(..) activation that is crossed, or None = the one stored in `out`, overwritten in place"""
+    pq, ldpq, jg = (None, 0, None) if act is None else act[:3]
+    L.call('gpe_edge_mlp_bwd', a, lda, int(act is not None), pq, ldpq, jg, *dims, Cin, Cout, wp, coef, out, ldo, dP, lddp,
+           amax_a, amax_out, *ws, *lazy)
+
+
+def _block_bwd(filed, blocks, l, dz, src, st_prev, dims, count, training, amax, ws, part, lazy=NO_LAZY, first=None):
+    """Backward across block l >= 1 of an MLP (EdgeConvFn, DenseMLPFn): weight gradient = centred reduce-GEMM of dz against the block's
+    input rows `src` -> coefficients of the BatchNorm in front -> propagate.  Files the gradients of W_l, b_l, gamma_{l-1}, beta_{l-1};
+    -> dz_{l-1}: in place over the stored activation src.t, or with first = (dst, dPQ) — src is the gathered first block — in dst, its
+    sums over each point's slots in dPQ.  amax: the words of (dz_l, src, dz_{l-1}); part: the reduce-GEMM's partials, None = an input
+    wider than the edge kernel takes (the row reduce-GEMM); lazy: dz_l is formed from the stored activation by its two consumers."""
+    W, b, gp, bp = blocks[l].W, blocks[l].b, blocks[l - 1].gamma, blocks[l - 1].beta
+    Cl, Cp = W.shape[0], blocks[l - 1].W.shape[0]
+    G = torch.empty(Cl, Cp, device=W.device, dtype=F32)
+    db = _gbuf(b)
+    if part is None:
+        redgemm_raw((dz, dz.stride(0), 0, 0), (src.t, src.ld, 0, 0), count, Cl, Cp, v_shift=st_prev[0], out=(G, db))
+    else:
+        edge_redgemm(u=dz, ldu=dz.stride(0), v=src, v_shift=st_prev[0], dims=dims, Mg=Cl, Ng=Cp, G=G, ldG=Cp, colsum=db, part=part,
+                     amax_u=amax[0], amax_v=amax[1], ws=ws, lazy=lazy)
+    sums = torch.empty(1, 2, Cp, device=W.device, dtype=torch.float64)
+    dW = _gbuf(W)
+    L.call('gpe_bn_bwd_from_G', G, Cp, db, W, W.stride(0), Cl, Cp, st_prev, sums, dW, Cp)
+    coef_p, dgp, dbp = bn_bwd_coef(sums, 1, st_prev, Cp, count, gp, bp, training)
+    filed[l, 'W'], filed[l, 'b'] = _gret(W, dW), _gret(b, db)
+    filed[l - 1, 'gamma'], filed[l - 1, 'beta'] = _gret(gp, dgp), _gret(bp, dbp)
+    # dz_{l-1} = (a>0) ? s*(dz_l W_l) - c1 - (a-mean)*k2 : 0 with a = the activation of block l - 1, stored or re-gathered
+    (out, ldo), (dP, lddp) = ((src.t, src.ld), (None, 0)) if first is None else ((first[0], Cp), (first[1], first[1].stride(0)))
+    edge_mlp_bwd(a=dz, lda=dz.stride(0), act=None if first is None else src, dims=dims, Cin=Cl, Cout=Cp,
+                 wp=pack_weight(W, transpose=True), coef=coef_p, out=out, ldo=ldo, dP=dP, lddp=lddp, amax_a=amax[0], amax_out=amax[2],
+                 ws=ws, lazy=lazy)
+    return out
+
+
 # -------------------------------------------------------------------------------------------------
 # nn.Linear
 # -------------------------------------------------------------------------------------------------
@@ -798,6 +914,7 @@ class EdgeConvFn(torch.autograd.Function):
     (+max/min over the point's messages in the last block) | last BatchNorm applied AFTER the aggregation.
     Saved for backward: the graph, PQ, the post-ReLU activations a_1..a_{nb-1} [E, .], the aggregates, the BN stat blocks.
     nb = EConv_hidden_depth + 1 >= 2; the shipped configs use nb = 3, aggr = 'max'."""
+    LEAD = 11                                              # forward's arguments in front of *tensors (x .. order)
 
     @staticmethod
     def forward(ctx, x, B, N, k, training, eps, momentum, nb, aggr, guard, order, *tensors):
@@ -808,53 +925,47 @@ class EdgeConvFn(torch.autograd.Function):
         dev = x.device
         BN, C = x.shape
         assert BN == B * N
-        params, bufs = tensors[:4 * nb], tensors[4 * nb:]
-        Ws = [params[4 * l] for l in range(nb)]
-        widths = [w.shape[0] for w in Ws]
+        blocks = mlp_blocks(tensors, nb)
+        widths = [blk.W.shape[0] for blk in blocks]
         H0 = widths[0]
-        assert Ws[0].shape[1] == 2 * C
+        assert blocks[0].W.shape[1] == 2 * C
         if H0 % 4 or H0 > 256:
             raise ValueError('EdgeConvFn (the fused P|Q path) needs a first-block width that is a multiple of 4 and <= 256 '
                              '(got %d): use ops.edge_conv_general' % H0)
         E = BN * k
         _LAST_EDGES[0] = E                                 # (what side_grads takes for the size of the step)
         nblk = L.query('gpe_stats_blocks')
-        wpq_p, _, bpq = edge_first_operands(Ws[0], params[1])
-        ews, ews_n = edge_workspace(B, N, k, max(round_up(widths[-1], 4), 2 * H0), dev)
+        wpq_p, _, bpq = edge_first_operands(blocks[0].W, blocks[0].b)
+        ldws = max(round_up(widths[-1], 4), 2 * H0)
+        ews = edge_workspace(B, N, k, ldws, dev)
         words = f16x3_words(2 * nb + 1, E, dev)           # (+ 1: max |s g| of the layer-output gradient, lazy dz3)
+
+        def project(own_ws):
+            PQ = torch.empty(BN, 2 * H0, device=dev, dtype=F32)
+            linear_raw(_rows2d(x), wpq_p, bpq, BN, 2 * H0, C, _rows2d(PQ))
+            if words is not None:
+                L.call('gpe_edge_pq_amax', PQ, 2 * H0, H0, BN, _word(words, 0), *(edge_workspace(B, N, k, ldws, dev) if own_ws else ews))
+            return PQ
+
         # The [P|Q] projection (and its f16x3 bound) needs the layer input only — not the graph: on a GPU-bound step it runs on the
         # side stream beside the graph search, whose kernels leave most of the chip's issue slots empty
         fork = SIDE_PQ and _side_ok(E)
         if fork:
             lane = streams.lane(dev.index)
             with lane.fork([x, words]):                     # (joined below, once the graph search is queued)
-                PQ = torch.empty(BN, 2 * H0, device=dev, dtype=F32)
-                linear_raw(_rows2d(x), wpq_p, bpq, BN, 2 * H0, C, _rows2d(PQ))
-                if words is not None:
-                    sws, sws_n = edge_workspace(B, N, k, max(round_up(widths[-1], 4), 2 * H0), dev)      # (the side stream's own workspace)
-                    L.call('gpe_edge_pq_amax', PQ, 2 * H0, H0, BN, _word(words, 0), sws, sws_n)
+                PQ = project(own_ws=True)                   # (the side stream's own workspace)
             idx, jg, order_out = knn(x, B, N, k, want_global=True, order=order, want_order=True)
             lane.wait(made=[PQ])
         else:
             idx, jg, order_out = knn(x, B, N, k, want_global=True, order=order, want_order=True)
-            PQ = torch.empty(BN, 2 * H0, device=dev, dtype=F32)
-            linear_raw(_rows2d(x), wpq_p, bpq, BN, 2 * H0, C, _rows2d(PQ))
-            if words is not None:
-                L.call('gpe_edge_pq_amax', PQ, 2 * H0, H0, BN, _word(words, 0), ews, ews_n)
-
-        def stats_of(part, l):
-            g, be = params[4 * l + 2], params[4 * l + 3]
-            rm, rv, nbt = bufs[3 * l: 3 * l + 3]
-            if training:
-                return bn_finalize(part, nblk, widths[l], E, g, be, eps, momentum, rm, rv, nbt)
-            return bn_from_running(rm, rv, g, be, eps)
+            PQ = project(own_ws=False)
 
         # caller-owned state of the edge calls: one workspace, and in f16x3 mode the amax words of this layer's tensors —
         # [0] the bound of relu(P_i + Q_j), [l] activation a_l, [nb + l] dz_l (backward)
         part = torch.empty(nblk, 2, H0, device=dev, dtype=torch.float64) if training else None
         if training:
             L.call('gpe_edge_gather_stats', PQ, 2 * H0, H0, jg, B, N, k, part)
-        stats = [stats_of(part, 0)]
+        stats = [bn_stats(blocks[0], eps, training, momentum, part, nblk, E)]
         acts = [None]
         mx = mn = amx = amn = abar = None
         for l in range(1, nb):
@@ -867,31 +978,31 @@ class EdgeConvFn(torch.autograd.Function):
                         L.query('gpe_edge_lazy_dz3_ok', B, N, k, Cout, Cin) == 1 and (guard is None or guard.allow()))
             a = torch.empty(E, ldo, device=dev, dtype=torch.float16 if half else F32)
             part = torch.empty(nblk, 2, Cout, device=dev, dtype=torch.float64) if training else None
-            agg = int(last and aggr == 'max')
-            if agg:
+            agg = None
+            if last and aggr == 'max':
                 mx = torch.empty(BN, ldo, device=dev, dtype=F32)
                 mn = torch.empty(BN, ldo, device=dev, dtype=F32)
                 amx = torch.empty(BN, ldo, device=dev, dtype=torch.uint8)
                 amn = torch.empty(BN, ldo, device=dev, dtype=torch.uint8)
+                agg = (mx, mn, amx, amn)
             w_out = _word(words, l)                        # (the last activation's word feeds the bound of a lazily formed dz)
             # the BatchNorm fold of this block's Linear: pack + folded bias (+ the packed weight's f16x3 amax) in one launch
-            wp, bf = pack_fold(Ws[l], params[4 * l + 1], stats[l - 1], ews if words is not None else None, ews_n, w_out)
+            wp, bf = pack_fold(blocks[l].W, blocks[l].b, stats[l - 1], ews[0] if words is not None else None, ews[1], w_out)
             wr = 2 if words is not None else 0             # bit 1 of out_half: the weight's scale is in the workspace
-            if l == 1:
-                L.call('gpe_edge_mlp_fwd', 0, PQ, 2 * H0, jg, None, 0, B, N, k, Cin, Cout, wp, bf, a, ldo, part,
-                       agg, mx, mn, amx, amn, ldo, _word(words, 0), w_out, ews, ews_n, wr)
-            else:
-                prev = acts[l - 1]
-                L.call('gpe_edge_mlp_fwd', 1, None, 0, None, prev, prev.stride(0), B, N, k, Cin, Cout, wp, bf, a, ldo,
-                       part, agg, mx, mn, amx, amn, ldo, _word(words, l - 1), w_out, ews, ews_n, int(half) | wr)
-                if half and guard is not None and not guard.watch(w_out):
-                    # 'strict' guard: the activation does not fit fp16 — the same launch once more with fp32 rows (nothing has
-                    # consumed the clamped copy; statistics, maxima and the amax word are rewritten with the same values)
-                    a = torch.empty(E, ldo, device=dev, dtype=F32)
-                    L.call('gpe_edge_mlp_fwd', 1, None, 0, None, prev, prev.stride(0), B, N, k, Cin, Cout, wp, bf, a, ldo,
-                           part, agg, mx, mn, amx, amn, ldo, _word(words, l - 1), w_out, ews, ews_n, 0)
+            src = edge_gathered(PQ, jg) if l == 1 else edge_rows(acts[l - 1])
+
+            def launch(a, out_half):
+                edge_mlp_fwd(src=src, dims=(B, N, k), Cin=Cin, Cout=Cout, wp=wp, bias=bf, out=a, ldo=ldo, stats_part=part, agg=agg,
+                             ldagg=ldo, amax_a=_word(words, l - 1), amax_out=w_out, ws=ews, out_half=out_half)
+
+            launch(a, int(half) | wr)                      # (half: never the gathered block — the aggregated one of nb >= 3)
+            if half and guard is not None and not guard.watch(w_out):
+                # 'strict' guard: the activation does not fit fp16 — the same launch once more with fp32 rows (nothing has
+                # consumed the clamped copy; statistics, maxima and the amax word are rewritten with the same values)
+                a = torch.empty(E, ldo, device=dev, dtype=F32)
+                launch(a, 0)
             acts.append(a)
-            stats.append(stats_of(part, l))
+            stats.append(bn_stats(blocks[l], eps, training, momentum, part, nblk, E))
         Fo = widths[-1]
         ldF = round_up(Fo, 4)
         out = torch.empty(BN, ldF, device=dev, dtype=F32)[:, :Fo]
@@ -917,8 +1028,8 @@ class EdgeConvFn(torch.autograd.Function):
                 del lane.jobs[:]                             # (a new forward pass: whatever an abandoned one left behind is dropped)
             ctx.rev_job = {'fn': knn_reverse, 'src': idx, 'out': None, 'event': None}
             lane.jobs.append(ctx.rev_job)
-        ctx.save_for_backward(x, idx, jg, PQ, *params, *acts[1:], *stats,
-                              *([mx, mn, amx, amn] if aggr == 'max' else [abar]))
+        save_groups(ctx, x=x, idx=idx, jg=jg, PQ=PQ, params=tensors[:len(MLP_PARAMS) * nb], acts=acts[1:], stats=stats,
+                    tail=[mx, mn, amx, amn] if aggr == 'max' else [abar])
         ctx.mark_non_differentiable(idx, order_out)
         return out, idx, order_out
 
@@ -929,16 +1040,13 @@ class EdgeConvFn(torch.autograd.Function):
                                'in place by the first pass (retain_graph is not supported)')
         B, N, k, C, nb, aggr, training = ctx.dims
         if g_out is None:                                  # only the graph / the order were used downstream
-            return (None,) * (11 + 4 * nb + 3 * nb)
+            return mlp_grads(EdgeConvFn.LEAD, nb)
         ctx.done = True
         widths = ctx.widths
-        sv = ctx.saved_tensors
-        x, idx, jg, PQ = sv[:4]
-        params = sv[4: 4 + 4 * nb]
-        acts = [None] + list(sv[4 + 4 * nb: 4 + 4 * nb + (nb - 1)])
-        stats = list(sv[4 + 5 * nb - 1: 4 + 6 * nb - 1])
-        tail = sv[4 + 6 * nb - 1:]
-        Ws = [params[4 * l] for l in range(nb)]
+        sv = saved_groups(ctx)
+        x, idx, jg, PQ, stats, tail = sv['x'], sv['idx'], sv['jg'], sv['PQ'], sv['stats'], sv['tail']
+        blocks = mlp_blocks(sv['params'], nb)
+        acts = [None] + sv['acts']
         dev = x.device
         BN, E = B * N, B * N * k
         H0, Fo = widths[0], widths[-1]
@@ -946,9 +1054,9 @@ class EdgeConvFn(torch.autograd.Function):
         if g_out.stride(1) != 1:
             g_out = g_out.contiguous()
         ldg = g_out.stride(0)
-        grads = [None] * (4 * nb)
+        filed = {}                         # (block, parameter field) -> gradient
         words = ctx.words                  # f16x3 amax words of this layer (None in the other modes): see forward
-        ews, ews_n = edge_workspace(B, N, k, max(ldF, 2 * H0), dev)
+        ews = edge_workspace(B, N, k, max(ldF, 2 * H0), dev)
         # the transposed graph of the gather backward needs the forward's graph only: on a GPU-bound step it is built on the side stream
         # now and finds its CUs in the gaps between the edge kernels (main waits for it in front of gpe_edge_pull_dq)
         rev, rev_event = None, None
@@ -965,9 +1073,9 @@ class EdgeConvFn(torch.autograd.Function):
         # ---- last block: BatchNorm applied after the aggregation -----------------------------------------
         psb = L.query('gpe_point_sums_blocks')
         part = torch.empty(psb, 2, Fo, device=dev, dtype=torch.float64)
-        g_last, be_last = params[4 * (nb - 1) + 2], params[4 * (nb - 1) + 3]
+        g_last, be_last = blocks[-1].gamma, blocks[-1].beta
         a_last = acts[-1]
-        lz = (None, 0, None, None, 0, None)                # lazy dz3 arguments of the two consumers (off)
+        lz = NO_LAZY                                       # lazy dz3 arguments of the two consumers (off)
         if aggr == 'max':
             mx, mn, amx, amn = tail
             # (the forward stored a3 in fp16 exactly when it found the lazy path open; should the mode have changed since — a debug
@@ -999,48 +1107,22 @@ class EdgeConvFn(torch.autograd.Function):
             coef, dg, dbe = bn_bwd_coef(part, psb, stats[-1], Fo, E, g_last, be_last, training)
             L.call('gpe_edge_dz3_all', a_last, ldF, g_out, ldg, 1.0 / k if aggr == 'mean' else 1.0, coef, B, N, k, Fo,
                    _word(words, 2 * nb - 1))
-        grads[4 * (nb - 1) + 2], grads[4 * (nb - 1) + 3] = _gret(g_last, dg), _gret(be_last, dbe)
+        filed[nb - 1, 'gamma'], filed[nb - 1, 'beta'] = _gret(g_last, dg), _gret(be_last, dbe)
 
         # ---- blocks nb-1 .. 1: weight gradient (centred reduce-GEMM) -> previous BN coefficients -> propagate ----
         ws = torch.empty(max(L.query('gpe_redgemm_ws', widths[l], widths[l - 1]) for l in range(1, nb)), device=dev,
                          dtype=F32)
         dPQ = torch.empty(BN, 2 * H0, device=dev, dtype=F32)
         dz = a_last
-        for l in range(nb - 1, 0, -1):
-            Cl, Cp = widths[l], widths[l - 1]
-            W, b = Ws[l], params[4 * l + 1]
-            G = torch.empty(Cl, Cp, device=dev, dtype=F32)
-            db = _gbuf(b)
-            w_dz = _word(words, nb + l)                    # dz_l: written by dz3 (l = nb - 1) or by the propagation below
-            if l == 1:
-                L.call('gpe_edge_redgemm', dz, dz.stride(0), 0, None, 0, PQ, 2 * H0, jg, stats[0][0], B, N, k, Cl, Cp, G,
-                       Cp, db, ws, w_dz, _word(words, 0), ews, ews_n, None, 0, None, None, 0, None)
-            else:
-                prev = acts[l - 1]
-                L.call('gpe_edge_redgemm', dz, dz.stride(0), 1, prev, prev.stride(0), None, 0, None, stats[l - 1][0],
-                       B, N, k, Cl, Cp, G, Cp, db, ws, w_dz, _word(words, l - 1), ews, ews_n,
-                       *(lz if l == nb - 1 else (None, 0, None, None, 0, None)))
-            sums = torch.empty(1, 2, Cp, device=dev, dtype=torch.float64)
-            dW = _gbuf(W)
-            L.call('gpe_bn_bwd_from_G', G, Cp, db, W, W.stride(0), Cl, Cp, stats[l - 1], sums, dW, Cp)
-            gp, bp = params[4 * (l - 1) + 2], params[4 * (l - 1) + 3]
-            coef_p, dgp, dbp = bn_bwd_coef(sums, 1, stats[l - 1], Cp, E, gp, bp, training)
-            grads[4 * l], grads[4 * l + 1] = _gret(W, dW), _gret(b, db)
-            grads[4 * (l - 1) + 2], grads[4 * (l - 1) + 3] = _gret(gp, dgp), _gret(bp, dbp)
-            wt = pack_weight(W, transpose=True)
-            if l == 1:
-                # dz_0 = (a_0>0) ? s_0*(dz_1 W_1) - c1 - (a_0-mean)*k2 : 0 with a_0 re-gathered; dP = sum over slots.
-                # In place over dz_1's buffer when the row pitch fits, else a fresh [E, H0]
-                dst = dz if dz.stride(0) == H0 else torch.empty(E, H0, device=dev, dtype=F32)
-                L.call('gpe_edge_mlp_bwd', dz, dz.stride(0), 1, PQ, 2 * H0, jg, B, N, k, Cl, Cp, wt, coef_p, dst, H0,
-                       dPQ, 2 * H0, w_dz, None, ews, ews_n, None, 0, None, None, 0, None)
-                dz = dst
-            else:
-                prev = acts[l - 1]
-                L.call('gpe_edge_mlp_bwd', dz, dz.stride(0), 0, None, 0, None, B, N, k, Cl, Cp, wt, coef_p, prev,
-                       prev.stride(0), None, 0, w_dz, _word(words, nb + l - 1), ews, ews_n,
-                       *(lz if l == nb - 1 else (None, 0, None, None, 0, None)))
-                dz = prev
+        for l in range(nb - 1, 1, -1):
+            # words: dz_l is written by dz3 (l = nb - 1) or by the propagation of the block behind it
+            dz = _block_bwd(filed, blocks, l, dz, edge_rows(acts[l - 1]), stats[l - 1], (B, N, k), E, training,
+                            (_word(words, nb + l), _word(words, l - 1), _word(words, nb + l - 1)), ews, ws,
+                            lazy=lz if l == nb - 1 else NO_LAZY)
+        # the gathered first block: its dz in place over dz_1's buffer when the row pitch fits, else a fresh [E, H0]
+        dst = dz if dz.stride(0) == H0 else torch.empty(E, H0, device=dev, dtype=F32)
+        dz = _block_bwd(filed, blocks, 1, dz, edge_gathered(PQ, jg), stats[0], (B, N, k), E, training,
+                        (_word(words, nb + 1), _word(words, 0), None), ews, ws, first=(dst, dPQ))
 
         # ---- block 0: gather backward = deterministic pull through the transposed graph -----------------
         if rev is not None:
@@ -1050,18 +1132,18 @@ class EdgeConvFn(torch.autograd.Function):
             rev_off, rev_edge = knn_reverse(idx)
         L.call('gpe_edge_pull_dq', dz, dz.stride(0), rev_off, rev_edge, B, N, k, H0, dPQ[:, H0:], 2 * H0)
         dWpq, dbpq = redgemm_raw(_rows2d(dPQ), _rows2d(x), BN, 2 * H0, C, want_colsum=True)
-        W1, b1 = Ws[0], params[1]
+        W1, b1 = blocks[0].W, blocks[0].b
         dW1 = _gbuf(W1)
         L.call('gpe_w1_grad_from_pq', dWpq, C, H0, C, dW1, 2 * C)
         db1 = _gbuf(b1)
         db1.copy_(dbpq[:H0])
-        grads[0], grads[1] = _gret(W1, dW1), _gret(b1, db1)
+        filed[0, 'W'], filed[0, 'b'] = _gret(W1, dW1), _gret(b1, db1)
         gx = None
         if ctx.needs_input_grad[0]:
             _, wpq_t, _ = edge_first_operands(W1, b1)
             gx = torch.empty(BN, C, device=dev, dtype=F32)
             linear_raw(_rows2d(dPQ), wpq_t, None, BN, C, 2 * H0, _rows2d(gx))
-        return (gx, None, None, None, None, None, None, None, None, None, None, *grads, *([None] * (3 * nb)))
+        return mlp_grads(EdgeConvFn.LEAD, nb, filed, gx)
 
 
 class EdgeInputsFn(torch.autograd.Function):
@@ -1167,8 +1249,8 @@ def edge_conv_predict(x, B, N, k, nb, aggr, tensors, order=None, route='auto', e
                          % (nb, len(tensors)))
     if x.dim() != 2 or x.shape[0] != B * N:
         raise ValueError('x must be [B*N, C] rows (got %s for B = %d, N = %d)' % (tuple(x.shape), B, N))
-    params, bufs = tensors[:4 * nb], tensors[4 * nb:]
-    Ws = [params[4 * l] for l in range(nb)]
+    blocks = mlp_blocks(tensors, nb)
+    Ws = [blk.W for blk in blocks]
     if Ws[0].shape[1] != 2 * x.shape[1]:
         raise ValueError('the first Linear takes %d features per edge, the points have %d' % (Ws[0].shape[1], x.shape[1]))
     on_menu = _edge_widths_on_menu([tuple(w.shape) for w in Ws], k)
@@ -1187,7 +1269,7 @@ def edge_conv_predict(x, B, N, k, nb, aggr, tensors, order=None, route='auto', e
         dev = x.device
         BN, C = x.shape
         idx, jg, order_out = knn(x, B, N, k, want_global=True, order=order, want_order=True)
-        wpq_p, _, bpq = edge_first_operands(Ws[0], params[1])
+        wpq_p, _, bpq = edge_first_operands(Ws[0], blocks[0].b)
         PQ = torch.empty(BN, 2 * H, device=dev, dtype=F32)
         linear_raw(_rows2d(x), wpq_p, bpq, BN, 2 * H, C, _rows2d(PQ))
         # the folded packs of the remaining Linears (the layout of gpe_stitch_pairs_fwd's, include/gpe_hip.h): W^T diag(s) of the
@@ -1199,9 +1281,9 @@ def edge_conv_predict(x, B, N, k, nb, aggr, tensors, order=None, route='auto', e
         wpk = torch.zeros(nh * (H + 1) * ldh + (H + 1) * ldf, device=dev, dtype=F32)
         planes = torch.empty(nh * KP * ldh + KP * ldf, device=dev, dtype=F32) if h3 else None
         words = torch.empty(nh + 1, device=dev, dtype=torch.int32) if h3 else None
-        st = bn_from_running(bufs[0], bufs[1], params[2], params[3], eps)
+        st = bn_stats(blocks[0], eps)
         for l in range(1, nb):
-            W, b = Ws[l], params[4 * l + 1]
+            W, b = Ws[l], blocks[l].b
             ld, n_out = (ldh, H) if l < nb - 1 else (ldf, Fo)
             o = (l - 1) * (H + 1) * ldh
             L.call('gpe_stitch_pairs_pack', W, W.stride(0), n_out, H, st[2], wpk[o:], ld)
@@ -1209,7 +1291,7 @@ def edge_conv_predict(x, B, N, k, nb, aggr, tensors, order=None, route='auto', e
             if h3:
                 L.call('gpe_absmax', wpk[o:], ld, H, ld, words[l - 1:])
                 L.call('gpe_stitch_pairs_planes', wpk[o:], H, ld, words[l - 1:], planes[(l - 1) * KP * ldh:])
-            st = bn_from_running(bufs[3 * l], bufs[3 * l + 1], params[4 * l + 2], params[4 * l + 3], eps)
+            st = bn_stats(blocks[l], eps)
         ldF = round_up(Fo, 4)
         out = torch.empty(BN, ldF, device=dev, dtype=F32)[:, :Fo]
         L.call('gpe_edge_predict_fwd', PQ, 2 * H, jg, BN, k, H, Fo, nh, wpk, planes, words, st, _AGGR_CODE[aggr], out, ldF)
@@ -1564,6 +1646,7 @@ class DenseMLPFn(torch.autograd.Function):
     BatchNorm folded into the next Linear, the last one applied explicitly; backward = the edge MLP's chain (centred
     reduce-GEMM -> BN coefficients -> propagate in place).  Layers wider than 256 (the global-attention MLP is 403 wide,
     an MLP decoder thousands) run as K slabs / several column blocks of the generic row GEMM."""
+    LEAD = 5                                               # forward's arguments in front of *tensors (x .. n_blocks)
 
     @staticmethod
     def forward(ctx, x, training, eps, momentum, n_blocks, *tensors):
@@ -1571,26 +1654,22 @@ class DenseMLPFn(torch.autograd.Function):
         dev = x.device
         M = x.shape[0]
         nblk = L.query('gpe_stats_blocks')
-        params = tensors[:4 * n_blocks]
-        bufs = tensors[4 * n_blocks:]
         acts, stats = [], []
         a_in, Cin = x, x.shape[1]
         scale = tvec = None
-        ews, ews_n = edge_workspace(1, M, 1, 4, dev)
+        ews = edge_workspace(1, M, 1, 4, dev)
         words = f16x3_words(2 * n_blocks, M, dev)          # [l] activation a_l, [n + l] dz_l (backward)
-        for l in range(n_blocks):
-            W, b, g, be = params[4 * l: 4 * l + 4]
-            rm, rv, nb = bufs[3 * l: 3 * l + 3]
+        for l, blk in enumerate(mlp_blocks(tensors, n_blocks)):
+            W, b = blk.W, blk.b
             Cout = W.shape[0]
             ldo = round_up(Cout, 4)
             a = torch.empty(M, ldo, device=dev, dtype=F32)
             part = torch.empty(nblk, 2, Cout, device=dev, dtype=torch.float64) if training else None
-            L.call('gpe_edge_mlp_fwd', 1, None, 0, None, a_in, a_in.stride(0), 1, M, 1, Cin, Cout,
-                   pack_weight(W, col_scale=scale), b if tvec is None else fold_bias(W, b, tvec), a, ldo, part,
-                   0, None, None, None, None, 0, _word(words, l - 1) if l > 0 else None,
-                   _word(words, l) if l < n_blocks - 1 else None, ews, ews_n, 0)
-            st = bn_finalize(part, nblk, Cout, M, g, be, eps, momentum, rm, rv, nb) if training \
-                else bn_from_running(rm, rv, g, be, eps)
+            edge_mlp_fwd(src=edge_rows(a_in), dims=(1, M, 1), Cin=Cin, Cout=Cout, wp=pack_weight(W, col_scale=scale),
+                         bias=b if tvec is None else fold_bias(W, b, tvec), out=a, ldo=ldo, stats_part=part, agg=None, ldagg=0,
+                         amax_a=_word(words, l - 1) if l > 0 else None, amax_out=_word(words, l) if l < n_blocks - 1 else None,
+                         ws=ews, out_half=0)
+            st = bn_stats(blk, eps, training, momentum, part, nblk, M)
             acts.append(a)
             stats.append(st)
             scale, tvec = st[2], st[3]
@@ -1601,7 +1680,7 @@ class DenseMLPFn(torch.autograd.Function):
         ctx.training = training
         ctx.done = False
         ctx.words = words
-        ctx.save_for_backward(x, *params, *acts, *stats)
+        save_groups(ctx, x=x, params=tensors[:len(MLP_PARAMS) * n_blocks], acts=acts, stats=stats)
         return y
 
     @staticmethod
@@ -1611,74 +1690,49 @@ class DenseMLPFn(torch.autograd.Function):
                                'in place by the first pass (retain_graph is not supported)')
         ctx.done = True
         n, training = ctx.n_blocks, ctx.training
-        sv = ctx.saved_tensors
-        x, params, acts, stats = sv[0], sv[1:1 + 4 * n], sv[1 + 4 * n:1 + 5 * n], sv[1 + 5 * n:1 + 6 * n]
+        sv = saved_groups(ctx)
+        x, acts, stats = sv['x'], sv['acts'], sv['stats']
+        blocks = mlp_blocks(sv['params'], n)
         dev = x.device
         M = x.shape[0]
         gy = gy.contiguous()
-        grads = [None] * (4 * n)
+        filed = {}                         # (block, parameter field) -> gradient
         # last block: BN applied explicitly -> same algebra as the edge layer's BN-after-max with one slot per row
         a, st = acts[-1], stats[-1]
-        C = params[4 * (n - 1)].shape[0]
-        g_l, be_l = params[4 * (n - 1) + 2], params[4 * (n - 1) + 3]
+        C = blocks[-1].W.shape[0]
+        g_l, be_l = blocks[-1].gamma, blocks[-1].beta
         psb = L.query('gpe_point_sums_blocks')
         part = torch.empty(psb, 2, C, device=dev, dtype=torch.float64)
         L.call('gpe_edge_bwd_point_sums', gy, C, a, a, a.stride(0), st, M, C, part, None)
         coef, dgam, dbet = bn_bwd_coef(part, psb, st, C, M, g_l, be_l, training)
         words = ctx.words
-        ews, ews_n = edge_workspace(1, M, 1, 4, dev)
+        ews = edge_workspace(1, M, 1, 4, dev)
         L.call('gpe_edge_dz3_all', a, a.stride(0), gy, C, 1.0, coef, 1, M, 1, C, _word(words, 2 * n - 1))
-        grads[4 * (n - 1) + 2], grads[4 * (n - 1) + 3] = _gret(g_l, dgam), _gret(be_l, dbet)
-        for l in reversed(range(n)):
-            W, b = params[4 * l], params[4 * l + 1]
-            dz = acts[l]                          # holds dz_l now
-            C = W.shape[0]
-            if l > 0:
-                prev, stp = acts[l - 1], stats[l - 1]
-                Cp = params[4 * (l - 1)].shape[0]
-                G = torch.empty(C, Cp, device=dev, dtype=F32)
-                db = _gbuf(b)
-                if Cp > 256:
-                    redgemm_raw((dz, dz.stride(0), 0, 0), (prev, prev.stride(0), 0, 0), M, C, Cp, v_shift=stp[0],
-                                out=(G, db))
-                else:
-                    ws = torch.empty(L.query('gpe_redgemm_ws', C, Cp), device=dev, dtype=F32)
-                    L.call('gpe_edge_redgemm', dz, dz.stride(0), 1, prev, prev.stride(0), None, 0, None, stp[0],
-                           1, M, 1, C, Cp, G, Cp, db, ws, _word(words, n + l), _word(words, l - 1), ews, ews_n,
-                           None, 0, None, None, 0, None)
-                sums = torch.empty(1, 2, Cp, device=dev, dtype=torch.float64)
-                dW = _gbuf(W)
-                L.call('gpe_bn_bwd_from_G', G, Cp, db, W, W.stride(0), C, Cp, stp, sums, dW, Cp)
-                gp, bp = params[4 * (l - 1) + 2], params[4 * (l - 1) + 3]
-                coef_p, dgam_p, dbet_p = bn_bwd_coef(sums, 1, stp, Cp, M, gp, bp, training)
-                L.call('gpe_edge_mlp_bwd', dz, dz.stride(0), 0, None, 0, None, 1, M, 1, C, Cp,
-                       pack_weight(W, transpose=True), coef_p, prev, prev.stride(0), None, 0,
-                       _word(words, n + l), _word(words, n + l - 1), ews, ews_n, None, 0, None, None, 0, None)
-                grads[4 * l], grads[4 * l + 1] = _gret(W, dW), _gret(b, db)
-                grads[4 * (l - 1) + 2], grads[4 * (l - 1) + 3] = _gret(gp, dgam_p), _gret(bp, dbet_p)
-            else:
-                K0 = x.shape[1]
-                dW, db = _gbuf(W), _gbuf(b)
-                redgemm_raw((dz, dz.stride(0), 0, 0), _rows2d(x), M, C, K0, out=(dW, db))
-                grads[0], grads[1] = _gret(W, dW), _gret(b, db)
+        filed[n - 1, 'gamma'], filed[n - 1, 'beta'] = _gret(g_l, dgam), _gret(be_l, dbet)
+        dz = a                                     # holds dz_{n-1} now
+        for l in range(n - 1, 0, -1):
+            Cl, Cp = blocks[l].W.shape[0], blocks[l - 1].W.shape[0]
+            # (an input wider than the edge reduce-GEMM takes: the row reduce-GEMM, no partials)
+            ws = None if Cp > 256 else torch.empty(L.query('gpe_redgemm_ws', Cl, Cp), device=dev, dtype=F32)
+            dz = _block_bwd(filed, blocks, l, dz, edge_rows(acts[l - 1]), stats[l - 1], (1, M, 1), M, training,
+                            (_word(words, n + l), _word(words, l - 1), _word(words, n + l - 1)), ews, ws)
+        W0, b0 = blocks[0].W, blocks[0].b
+        H0, K0 = W0.shape[0], x.shape[1]
+        dW, db = _gbuf(W0), _gbuf(b0)
+        redgemm_raw((dz, dz.stride(0), 0, 0), _rows2d(x), M, H0, K0, out=(dW, db))
+        filed[0, 'W'], filed[0, 'b'] = _gret(W0, dW), _gret(b0, db)
         gx = None
         if ctx.needs_input_grad[0]:
-            dz0, W0 = acts[0], params[0]
-            gx = torch.empty(M, x.shape[1], device=dev, dtype=F32)
-            linear_raw((dz0, dz0.stride(0), 0, 0), pack_weight(W0, transpose=True), None, M, x.shape[1],
-                       W0.shape[0], _rows2d(gx))
-        return (gx, None, None, None, None, *grads, *([None] * (3 * n)))
+            gx = torch.empty(M, K0, device=dev, dtype=F32)
+            linear_raw((dz, dz.stride(0), 0, 0), pack_weight(W0, transpose=True), None, M, K0, H0, _rows2d(gx))
+        return mlp_grads(DenseMLPFn.LEAD, n, filed, gx)
 
 
 def dense_mlp(x, mlp, training):
     """mlp: the nn.Sequential parameter container built by net_blocks.MLP."""
-    blocks = [mlp[i] for i in range(len(mlp))]
-    params, bufs = [], []
-    for blk in blocks:
-        params += [blk[0].weight, blk[0].bias, blk[2].weight, blk[2].bias]
-        bufs += [blk[2].running_mean, blk[2].running_var, blk[2].num_batches_tracked]
     x = x if x.stride(1) == 1 else x.contiguous()
-    return DenseMLPFn.apply(x, training, blocks[0][2].eps, blocks[0][2].momentum, len(blocks), *params, *bufs)
+    eps, momentum, n, tensors = mlp_tensors(mlp)
+    return DenseMLPFn.apply(x, training, eps, momentum, n, *tensors)
 
 
 # -------------------------------------------------------------------------------------------------

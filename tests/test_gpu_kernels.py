@@ -1082,6 +1082,19 @@ def test_dense_mlp_wide_layers(gpe, M, chans):
         assert e < max(5e-3 if p.grad.dim() == 1 else 5e-4, 20 * e32), (n, e, e32)
 
 
+def test_dense_mlp_backward_twice_is_refused(gpe):
+    """The first backward overwrites the stored activations in place: a second one over the same graph raises, as EdgeConvFn's does."""
+    M, chans = 64, [6, 8, 5]
+    torch.manual_seed(M)
+    pmlp = gpe.net_blocks.MLP(chans).cuda().train()
+    xd = torch.randn(M, chans[0]).cuda().requires_grad_()
+    s = gpe.ops.dense_mlp(xd, pmlp, True).sum()
+    s.backward(retain_graph=True)
+    assert all(p.grad is not None for p in pmlp.parameters()) and xd.grad is not None
+    with pytest.raises(RuntimeError, match='ran twice'):
+        s.backward()
+
+
 def test_edgeconv_eval_mode_backward(gpe):
     """Backward through a layer in eval() mode: BatchNorm statistics are constants (no mean / projection terms)."""
     from oracle import ref_path as O
