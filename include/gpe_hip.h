@@ -113,8 +113,9 @@ int gpe_knn(const float* x, int B, int N, int C, int ldx, int k, int32_t* idx, i
  * with ordered lists; C > 256: on the fp32 pipe); otherwise the all-pairs VALU kernel.  The whole ladder: csrc/gpe_knn_plan.h. */
 
 /* reverse adjacency of the kNN graph (needed by the gather's backward = scatter-add into x_j rows):
- * rev_off [B][N+1] int32 (local offsets), rev_edge [B][N*k] int32 = local edge ids (i*k+s) sorted ascending
- * inside each bucket, so the pull-style accumulation order is deterministic. */
+ * rev_off [B][N+1] int32 (local offsets: the exclusive scan of the in-degrees, rev_off[N] = N*k), rev_edge [B][N*k] int32 =
+ * local edge ids (i*k+s) sorted ascending inside each bucket, so the pull-style accumulation order is deterministic.
+ * idx holds cloud-local neighbours; 2N + 1 ints must fit 150 KB of LDS, else -22. */
 int gpe_knn_reverse(const int32_t* idx, int B, int N, int k, int32_t* rev_off, int32_t* rev_edge, void* stream);
 
 /* ---- weight packing (+ BatchNorm folding) ------------------------------------------------------------------
@@ -224,7 +225,9 @@ int gpe_edge_pq_amax(const float* pq, int ldpq, int H, long rows, uint32_t* amax
 /* amax[0] = bits of the largest |x| over [rows][cols] (row pitch ldx, 16-B aligned rows) */
 int gpe_absmax(const float* x, int ldx, long rows, int cols, uint32_t* amax, void* stream);
 
-/* layer output: y[i][c] = s[c]*(s[c]>=0 ? mx : mn)[i][c] + t[c]  (BN applied after the max, sign-aware) */
+/* layer output: y[i][c] = s[c]*(s[c]>=0 ? mx : mn)[i][c] + t[c]  (BN applied after the max, sign-aware).  A zero scale of either sign
+ * (+0.0, -0.0) selects mx here, in gpe_edge_bwd_point_sums and in gpe_edge_dz3 alike.  rows = 0 is a no-op; columns from C to the
+ * pitch of y are not written. */
 int gpe_edge_finish(const float* mx, const float* mn, int ldagg, const float* stats, long rows, int C,
                     float* y, int ldy, void* stream);
 
@@ -235,7 +238,8 @@ int gpe_point_sums_blocks(void);
 int gpe_edge_bwd_point_sums(const float* g, int ldg, const float* mx, const float* mn, int ldagg,
                             const float* stats, long rows, int C, double* part, uint32_t* amax_sg, void* stream);
 /* amax_sg (may be NULL): receives the bits of max |s_c * g_ic| (s = the BatchNorm scale in `stats`), measured while g is read —
- * the data term of gpe_edge_dz3_bound */
+ * the data term of gpe_edge_dz3_bound.  The call resets the word itself; the value is never below the true maximum and at most
+ * 8 * 2^-24 relative above it.  Every one of the gpe_point_sums_blocks() partial blocks is written (zeros where a block has no row). */
 /* coefficient vectors for "dz = (a>0) ? s*dy - c1 - (a-mean)*k2 : 0":  coef [4][C] = {s, c1 = s*mean(dy),
  * k2 = s*rstd*mean(dy*xhat), mean} from partial sums part [nblk][2][C]; also the BatchNorm parameter gradients
  * dgamma = sum dy*xhat, dbeta = sum dy (may be NULL) */
@@ -248,9 +252,13 @@ int gpe_bn_bwd_coef(const double* part, int nblk, const float* stats, int C, dou
 int gpe_bn_bwd_from_G(const float* G, int ldG, const float* db, const float* w_next, int ldw, int Cn, int C,
                       const float* stats, double* sums, float* dw, int lddw, void* stream);
 
-/* dz3 = (a3>0) ? [slot==argsel]*s*g - k1 - a3*k2 : 0 written IN PLACE over the stored activation a3 [E][lda3]
+/* dz3 = (a3>0) ? [slot==argsel]*s*g - c1 - (a3-mean)*k2 : 0 written IN PLACE over the stored activation a3 [E][lda3]
  * (BN-after-max backward + ReLU backward of the last edge-MLP block; g [B*N][ldg] is the layer-output gradient,
- * amx/amn the argmax/argmin slots saved by gpe_edge_mlp_fwd, coef [4][F] from gpe_bn_bwd_coef). */
+ * amx/amn the argmax/argmin slots saved by gpe_edge_mlp_fwd, coef [4][F] = {s, c1, k2, mean} from gpe_bn_bwd_coef).
+ * Exactly +0 wherever a3 <= 0.  Rows are handled in quads of columns: columns F .. round_up(F, 4) - 1 of a3 are read (any value,
+ * NaN included) and WRITTEN 0, columns from round_up(F, 4) to lda3 are left alone (lda3 and ldagg % 4 == 0, >= F; amx / amn are
+ * read up to round_up(F, 4) as well).  amax_out (may be NULL) is reset by the call and receives the bits of the largest |value|
+ * written. */
 int gpe_edge_dz3(float* a3, int lda3, const float* g, int ldg, const uint8_t* amx, const uint8_t* amn, int ldagg,
                  const float* coef, int B, int N, int k, int F, uint32_t* amax_out, void* stream);
 
@@ -291,7 +299,9 @@ int gpe_edge_lazy_dz3_ok(int B, int N, int k, int F, int Cprev);
  * with coef [4][F] from gpe_bn_bwd_coef and amax_a3 the word of the stored activation (gpe_edge_mlp_fwd's amax_out) */
 int gpe_edge_dz3_bound(const uint32_t* amax_sg, const float* coef, int F, const uint32_t* amax_a3, uint32_t* amax_out, void* stream);
 
-/* dQ[j] = sum over incoming edges e of dz1[e]  (deterministic pull through the reverse adjacency) */
+/* dQ[j] = sum over incoming edges e of dz1[e]  (deterministic pull through the reverse adjacency: fp32, from +0, in ascending
+ * edge id; a point without incoming edges receives +0).  H % 4 == 0, H <= 256, lddz and lddq % 4 == 0; only columns 0 .. H - 1
+ * of dQ are written, so dQ may be the right half of a [B*N][2H] buffer. */
 int gpe_edge_pull_dq(const float* dz, int lddz, const int32_t* rev_off, const int32_t* rev_edge,
                      int B, int N, int k, int H, float* dQ, int lddq, void* stream);
 
@@ -400,12 +410,15 @@ int gpe_bn_apply(const float* a, int lda, const float* stats, long rows, int C, 
  * messages of a point, applied after the aggregation (nn/net_blocks.py:129 with EConv_aggr != 'max') */
 int gpe_bn_apply_scaled(const float* a, int lda, const float* stats, long rows, int C, float a_scale, float t_scale,
                         float* y, int ldy, void* stream);
-/* out[i][c] = sum over the k messages of point i of a[i*k+s][c] */
+/* out[i][c] = sum over the k messages of point i of a[i*k+s][c], in fp32, slots ascending from +0 */
 int gpe_edge_sum_k(const float* a, int lda, long npts, int k, int F, float* out, int ldo, void* stream);
 /* explicit message inputs of DynamicEdgeConv (nn/net_blocks.py:124-135: cat[x_i, x_j - x_i]) for first-block widths the fused
  * P|Q path does not take (EConv_hidden not a multiple of 4, or > 256): out [npts*k][ldo >= 2C], row e = i*k + s holds
- * [x_i | x_{jg[e]} - x_i] (pad columns zero).  bwd: gx [B*N][C] from g [B*N*k][ldg >= 2C] through the transposed graph of
- * gpe_knn_reverse (rev_off [B][N+1], rev_edge [B][N*k]) — a deterministic pull, no atomics. */
+ * [x_i | x_{jg[e]} - x_i], and EVERY column from 2C to ldo is written 0 (the dense MLP that follows reads whole rows).
+ * bwd: gx [B*N][ldgx >= C] from g [B*N*k][ldg >= 2C] through the transposed graph of gpe_knn_reverse (rev_off [B][N+1], rev_edge
+ * [B][N*k], edge ids local to the cloud) — a deterministic pull, no atomics, in fp32 in this order: sum over the point's slots of
+ * (g1 - g2), ascending, then the g2 of the incoming edges in ascending edge id.  Columns of g past 2C are not read, columns of gx
+ * past C not written. */
 int gpe_edge_inputs_fwd(const float* x, int ldx, int C, const int32_t* jg, long npts, int k, float* out, int ldo,
                         void* stream);
 int gpe_edge_inputs_bwd(const float* g, int ldg, int C, const int32_t* rev_off, const int32_t* rev_edge, int B, int N, int k,
