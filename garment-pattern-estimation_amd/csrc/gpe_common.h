@@ -10,6 +10,8 @@
 #include "../../include/gpe_hip_ext.h"
 // ... and the feature additions (the statistics fit), bound through _lib.FEATURE_HEADERS
 #include "../../include/gpe_hip_fit.h"
+// ... and the evaluation pass (the accumulate and pooling launches), bound through _lib.EVAL_HEADERS
+#include "../../include/gpe_hip_eval.h"
 
 #define GPE_OK 0
 #define GPE_EINVAL (-22)

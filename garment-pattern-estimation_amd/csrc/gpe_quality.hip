@@ -11,14 +11,11 @@
 #include "gpe_stitch_greedy.h"   // QM_TPB (one wave per pattern, both kernels), QM_MAXD, QM_MAXE and the pairing itself
 #include <math.h>
 
-// every product / sum below is rounded on its own, in the reference's order (no contraction into FMAs)
-#pragma clang fp contract(off)
+// (every product / sum below is rounded on its own, in the reference's order: the header switches FMA contraction off)
+#include "gpe_quality_fold.h"    // QM_* flags, QM_PART, and the fold of the per-pattern records (shared with csrc/gpe_eval.hip)
 
 #define QM_MAXP 64           // panels per pattern (shipped: 23)
 #define QM_MAXL 64           // edges per panel (shipped: 14)
-#define QM_PART 16           // doubles of workspace per pattern
-
-enum { QM_DISCRETE = 1, QM_SHAPE = 2, QM_ROT = 4, QM_TR = 8, QM_STITCH = 16, QM_FREE = 32, QM_TAG_STATS = 64 };
 
 // host-array layout of `stats` (include/gpe_hip.h gpe_quality_panels / gpe_quality_stitches)
 enum { QS_OL_SHIFT = 0, QS_OL_SCALE = 4, QS_PAD = 8, QS_PAD_TOL = 12, QS_LOOP_THR = 16, QS_ROT_SHIFT = 24, QS_ROT_SCALE = 32,
@@ -26,9 +23,7 @@ enum { QS_OL_SHIFT = 0, QS_OL_SCALE = 4, QS_PAD = 8, QS_PAD_TOL = 12, QS_LOOP_TH
 
 struct QmStats { float v[QS_N]; };
 
-// workspace slots per pattern: [0] pattern has the right panel count (0/1), [1] its fp32 share of correctly-sized panels,
-// [2] sum of per-panel vertex L2, [3] panels in it, [4] sum of rotation L2, [5] sum of translation L2, [8] stitches
-// detected (0/1), [9] precision (fp64), [10] recall (an fp32 value), [11] free-edge decisions equal to the ground truth
+// (the slots of a pattern's workspace record: gpe_quality_fold.h)
 struct QmPanelParams {
     const float* ol; long ol_sb, ol_sp, ol_sl;          // predicted outlines (b,p,l,c<4) at ol + b*ol_sb + p*ol_sp + l*ol_sl + c
     const float* gt_ol;                                 // dense [B,P,L,4]
@@ -226,48 +221,9 @@ __global__ void gpe_quality_final_kernel(const double* __restrict__ part, int B,
                                          int32_t* __restrict__ counts)
 {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    float np_acc = 0.f, ne_acc = 0.f, ne_corr = 0.f, rec = 0.f, rec_corr = 0.f;
-    double sh = 0, sh_corr = 0, rot = 0, rot_corr = 0, tr = 0, tr_corr = 0, prec = 0, prec_corr = 0;
-    long nsh = 0, nsh_corr = 0, nfree = 0;
-    int ncorr = 0, nst_corr = 0;
-    const bool disc = flags & QM_DISCRETE;
-    for (int b = 0; b < B; ++b) {
-        const double* o = part + (size_t)b * QM_PART;
-        const bool corr = disc && o[0] != 0.0;
-        if (disc) {
-            np_acc += (float)o[0];
-            ne_acc += (float)o[1];
-            if (corr) { ne_corr += (float)o[1]; ++ncorr; }
-        }
-        if (flags & QM_SHAPE) {
-            sh += o[2]; nsh += (long)o[3];
-            if (corr) { sh_corr += o[2]; nsh_corr += (long)o[3]; }
-        }
-        if (flags & QM_ROT) { rot += o[4]; if (corr) rot_corr += o[4]; }
-        if (flags & QM_TR) { tr += o[5]; if (corr) tr_corr += o[5]; }
-        if (flags & QM_STITCH) {
-            prec += o[9]; rec += (float)o[10];
-            if (corr && o[8] != 0.0) { prec_corr += o[9]; rec_corr += (float)o[10]; ++nst_corr; }
-        }
-        if (flags & QM_FREE) nfree += (long)o[11];
-    }
-    const float fB = (float)B;
-    for (int k = 0; k < 14; ++k) out[k] = 0.f;
-    if (disc) { out[0] = np_acc / fB; out[1] = ne_acc / fB; out[2] = ne_corr / (float)ncorr; }      // 0 correct: 0/0 = NaN
-    if (flags & QM_SHAPE) { out[3] = (float)(sh / (double)nsh); out[4] = (float)(sh_corr / (double)nsh_corr); }
-    if (flags & QM_ROT) { out[5] = (float)(rot / ((double)B * P)); out[6] = (float)(rot_corr / ((double)ncorr * P)); }
-    if (flags & QM_TR) { out[7] = (float)(tr / ((double)B * P)); out[8] = (float)(tr_corr / ((double)ncorr * P)); }
-    if (flags & QM_STITCH) {
-        out[9] = (float)(prec / (double)B);
-        out[10] = rec / fB;
-        out[11] = (float)(prec_corr / (double)nst_corr);
-        out[12] = rec_corr / (float)nst_corr;
-    }
-    if (flags & QM_FREE) out[13] = (float)nfree / (float)((long)B * P * L);
-    counts[0] = ncorr;
-    counts[1] = (int32_t)nsh_corr;
-    counts[2] = nst_corr;
-    counts[3] = (int32_t)nsh;
+    QmFold f;
+    for (int b = 0; b < B; ++b) f.add(part + (size_t)b * QM_PART, flags);
+    f.finish(B, P, L, flags, out, counts);
 }
 
 static int qm_stats(const float* stats_host, QmStats* s)

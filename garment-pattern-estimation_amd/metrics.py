@@ -25,7 +25,11 @@ reference's keys, evaluated on the matched ground truth, in at most three launch
 points — metrics.eval_utils.eval_metrics, the trainer's validation loop — run under torch.no_grad()), or in grad-enabled calls
 too when `quality_in_training` is set (the reference's per-step logging; it costs one host read per call).  A training step
 with the defaults therefore makes exactly the launches it made before, with no host read.  Under DistributedHotPath each rank
-reports the metrics of its own shard.  DESIGN.md section 5.22."""
+reports the metrics of its own shard.  DESIGN.md section 5.22.
+
+Evaluation over a data set (the reference's metrics/eval_utils.py) goes through `accumulate` of either loss class instead of
+`__call__`: the same launches, the values added to an ops.EvalAccumulator on the device under the gates that decide a corr_ key's
+None, no host read per batch and no refusal inside a stream capture (evaluation.Evaluator)."""
 import torch
 import torch.nn as nn
 
@@ -130,6 +134,32 @@ class ComposedLoss:
         if 'edge_pair_stitch_recall' in wanted:
             loss_dict.update(stitch_precision=m[2], stitch_recall=m[3])
         return full_loss, loss_dict, False
+
+    # ---- evaluation over a data set without a host read per batch (evaluation.Evaluator) -------------
+    def eval_keys(self, epoch=1000):
+        """-> (keys, gates) of the ops.EvalAccumulator that accumulate() writes into: 'full_loss', then the keys of the loss dict
+        __call__ returns for this configuration, in its order.  Source 0 is ops.pair_class_loss's vector; no key is gated (an empty
+        denominator gives 0 there, never None)."""
+        if 'edge_pair_class' not in self.l_components:
+            raise ValueError("ComposedLoss: without the 'edge_pair_class' loss component full_loss is the number 0, which an "
+                             "evaluation pass cannot average (the reference's pass fails on it too)")
+        keys = [('full_loss', 0, 0), ('edge_pair_class_loss', 0, 0)]
+        if self.with_quality_eval:
+            if 'edge_pair_class' in self.q_components:
+                keys.append(('edge_pair_class_acc', 0, 1))
+            if 'edge_pair_stitch_recall' in self.q_components:
+                keys += [('stitch_precision', 0, 2), ('stitch_recall', 0, 3)]
+        return keys, {}
+
+    def accumulate(self, preds, ground_truth, acc, epoch=1000, names=None, records=None):
+        """What __call__ computes for fp32 device predictions under no_grad — the same one launch — added to `acc`
+        (ops.EvalAccumulator(*self.eval_keys())) instead of returned: no host read, legal inside a stream capture."""
+        from . import ops
+        if not (preds.is_cuda and preds.dtype == torch.float32):
+            raise RuntimeError('ComposedLoss.accumulate runs on fp32 device predictions only (got %s / %s)' % (preds.device, preds.dtype))
+        self.device = preds.device
+        with torch.no_grad():
+            acc.add(ops.pair_class_loss(preds, ground_truth.to(self.device)))
 
     def eval(self):
         self.training = False
@@ -290,7 +320,8 @@ class ComposedPatternLoss:
         return out
 
     # ---- main entry ------------------------------------------------------------------------------------------
-    def __call__(self, preds, ground_truth, names=None, epoch=1000):
+    def _matched_gt(self, preds, ground_truth, epoch):
+        """the ground truth on the device, after the order and origin matchings -> (gt, gt_num_edges)"""
         self.device = preds['outlines'].device
         self.epoch = epoch
         self._need_device(preds['outlines'])
@@ -304,18 +335,31 @@ class ComposedPatternLoss:
         gt_num_edges = gt['num_edges'].int().view(-1)
         if self.config['panel_origin_invariant_loss']:
             gt = self._rotate_gt(preds, gt, gt_num_edges)
-        full_loss, loss_dict = self._main_losses(preds, gt, gt_num_edges)
+        return gt, gt_num_edges
+
+    def _loss_terms(self, preds, gt, gt_num_edges, epoch):
+        """-> (full_loss, loss dict, the result vectors behind them: {'main', 'segm', 'stitch'}, None where a term is off)"""
+        main, loss_dict = self._main_losses(preds, gt, gt_num_edges)
+        full_loss = main[0]
+        vectors = {'main': main, 'segm': None, 'stitch': None}
         if 'segmentation' in self.l_components:                                # composed_loss.py:323-332
             from . import ops
             att = preds['att_weights']
             segm = ops.SparsemaxLossFn.apply(att.reshape(-1, att.shape[-1]), gt['segmentation'].reshape(-1))
             full_loss = full_loss + self.config['segm_loss_weight'] * segm
             loss_dict.update(segm_loss=segm)
+            vectors['segm'] = segm
         if self._stitch_terms_active(epoch):
             self.last_matched_stitch_gt = {k: gt[k] for k in ('stitches', 'free_edges_mask') if k in gt}   # diagnostics / tests
             extra, extra_dict = self._stitch_losses(preds, gt)
-            full_loss = full_loss + extra
+            full_loss = full_loss + extra[0]
             loss_dict.update(extra_dict)
+            vectors['stitch'] = extra
+        return full_loss, loss_dict, vectors
+
+    def __call__(self, preds, ground_truth, names=None, epoch=1000):
+        gt, gt_num_edges = self._matched_gt(preds, ground_truth, epoch)
+        full_loss, loss_dict, _ = self._loss_terms(preds, gt, gt_num_edges, epoch)
         if self._quality_active():                                             # composed_loss.py:268-277
             with torch.no_grad():
                 quality, correct = self._main_quality_metrics(preds, gt, gt_num_edges, names)
@@ -327,6 +371,58 @@ class ComposedPatternLoss:
                 el in self.l_components for el in ['stitch', 'stitch_supervised', 'free_class'])
             or epoch == self.config['epoch_with_order_matching'] and self.config['panel_order_inariant_loss'])
         return full_loss, loss_dict, loss_update_ind
+
+    # ---- evaluation over a data set without a host read per batch (evaluation.Evaluator) -------------
+    # the sources of the accumulator: the result vectors of the main loss launch and of the stitch loss launch, the quality vector,
+    # and [full_loss, segm_loss] (sums that __call__ forms with torch adds, formed the same way here)
+    _SRC_MAIN, _SRC_STITCH, _SRC_QUALITY, _SRC_TOTAL = 0, 1, 2, 3
+
+    def eval_keys(self, epoch=1000):
+        """-> (keys, gates) of the ops.EvalAccumulator that accumulate() writes into at this epoch: 'full_loss', then the keys of the
+        loss dict __call__ returns under no_grad for this configuration and epoch, in its order; a corr_ key is gated by the
+        contributor count that decides its None in __call__ (ops.QUALITY_GATES)."""
+        from . import ops
+        c, q = self.l_components, self.q_components
+        keys = [('full_loss', self._SRC_TOTAL, 0)]
+        keys += [(k, self._SRC_MAIN, i) for comp, k, i in (('shape', 'pattern_loss', 1), ('loop', 'loop_loss', 2),
+                                                           ('rotation', 'rotation_loss', 3), ('translation', 'translation_loss', 4))
+                 if comp in c]
+        if 'segmentation' in c:
+            keys.append(('segm_loss', self._SRC_TOTAL, 1))
+        if self._stitch_terms_active(epoch):
+            if 'stitch' in c:
+                keys += [('stitch_similarity_loss', self._SRC_STITCH, 1), ('stitch_neg_loss', self._SRC_STITCH, 2)]
+            if 'stitch_supervised' in c:
+                keys.append(('stitch_supervised_loss', self._SRC_STITCH, 3))
+            if 'free_class' in c:
+                keys.append(('free_edges_loss', self._SRC_STITCH, 4))
+        if self.with_quality_eval and q:
+            slots = {'discrete': (0, 1, 2), 'shape': (3, 4), 'rotation': (5, 6), 'translation': (7, 8)}
+            wanted = [i for comp in ('discrete', 'shape', 'rotation', 'translation') if comp in q for i in slots[comp]]
+            if epoch >= self.config['epoch_with_stitches']:
+                wanted += (9, 10, 11, 12) if 'stitch' in q else ()
+                wanted += (13,) if 'free_class' in q else ()
+            keys += [(ops.QUALITY_KEYS[i], self._SRC_QUALITY, i) for i in wanted]
+        names = [k[0] for k in keys]
+        if len(set(names)) != len(names):
+            raise ValueError('ComposedPatternLoss.eval_keys: duplicate keys %s' % sorted(n for n in set(names) if names.count(n) > 1))
+        return keys, {k: g for k, g in ops.QUALITY_GATES.items() if k in names}
+
+    def accumulate(self, preds, ground_truth, acc, epoch=1000, names=None, records=None):
+        """What __call__ computes under no_grad with the quality components on — the same matching, the same launches, full_loss and
+        every loss-dict key — added to `acc` (ops.EvalAccumulator(*self.eval_keys(epoch), ...)) instead of returned as a dict: the
+        contributor counts that decide a corr_ key's None gate the add on the device.  No host read, legal inside a stream capture.
+        records: fp64 [B, 16], this batch's rows of the table that ops.quality_pool folds (ops.quality_metrics' `part`)."""
+        with torch.no_grad():
+            gt, gt_num_edges = self._matched_gt(preds, ground_truth, epoch)
+            full_loss, _, vec = self._loss_terms(preds, gt, gt_num_edges, epoch)
+            total = full_loss.reshape(1) if vec['segm'] is None else torch.stack([full_loss, vec['segm']])
+            quality = counts = None
+            if self.with_quality_eval and self.q_components:
+                quality, counts = self._quality_launch(preds, gt, gt_num_edges, records)
+                self.last_quality_vector = quality
+            acc.add(vec['main'], vec['stitch'], quality, total, counts=counts)
+        return total[0]
 
     # ---- quality metrics (composed_loss.py:365-424) -----------------------------------------------------------
     def _quality_active(self):
@@ -364,9 +460,9 @@ class ComposedPatternLoss:
                 flags |= ops.QM_TAG_STATS
         return flags
 
-    def _quality_vector(self, preds, gt, gt_num_edges):
+    def _quality_launch(self, preds, gt, gt_num_edges, part=None):
         """ONE evaluation of every requested component (the main ones and, from epoch_with_stitches on, the stitch ones):
-        -> (result vector fp32 [14] on the device, contributor counts on the host or None).  Cached per call of the loss."""
+        -> (result vector fp32 [14], contributor counts int32 [4]), both on the device; no host read."""
         from . import ops
         flags = self._quality_flags(self.epoch >= self.config['epoch_with_stitches'])
         B, P, Lp = preds['outlines'].shape[:3] if 'outlines' in preds else preds['free_edges_mask'].shape[:3]
@@ -385,7 +481,15 @@ class ComposedPatternLoss:
             stitch_tags=preds['stitch_tags'] if stitch else None,
             free_logits=preds['free_edges_mask'] if flags & (ops.QM_STITCH | ops.QM_FREE) else None,
             stitches=gt['stitches'] if stitch else None, nums=gt['num_stitches'] if stitch else None,
-            gt_free_mask=gt['free_edges_mask'] if flags & ops.QM_FREE else None)
+            gt_free_mask=gt['free_edges_mask'] if flags & ops.QM_FREE else None, part=part)
+        return out, counts
+
+    def _quality_vector(self, preds, gt, gt_num_edges):
+        """_quality_launch -> (result vector fp32 [14] on the device, contributor counts on the host or None).  Cached per call of
+        the loss."""
+        from . import ops
+        flags = self._quality_flags(self.epoch >= self.config['epoch_with_stitches'])
+        out, counts = self._quality_launch(preds, gt, gt_num_edges)
         # the corr_ values exist only with the `discrete` component (the reference's correct-pattern mask); then their
         # contributor counts decide None — the one host read of the evaluation path
         host = counts.tolist() if flags & ops.QM_DISCRETE else None
@@ -423,7 +527,7 @@ class ComposedPatternLoss:
         return d
 
     def _stitch_losses(self, preds, gt):
-        """composed_loss.py:336-362 through ops.StitchLossFn."""
+        """composed_loss.py:336-362 through ops.StitchLossFn -> (its result vector [5]: element 0 is the term's total, loss dict)."""
         from . import ops
         comps = self.l_components
         flags = (ops.STITCH_MAIN if 'stitch' in comps else 0) | (ops.STITCH_FREE if 'free_class' in comps else 0) | \
@@ -446,10 +550,10 @@ class ComposedPatternLoss:
             loss_dict.update(stitch_supervised_loss=out[3])
         if 'free_class' in comps:
             loss_dict.update(free_edges_loss=out[4])
-        return out[0], loss_dict
+        return out, loss_dict
 
     def _main_losses(self, preds, gt, gt_num_edges):
-        """composed_loss.py:294-321."""
+        """composed_loss.py:294-321 -> (ops.PatternLossFn's result vector [5]: element 0 is the total, loss dict)."""
         comps = self.l_components
         ol = preds['outlines']
         if ol.is_cuda and ol.dtype == torch.float32:
@@ -480,7 +584,7 @@ class ComposedPatternLoss:
                 loss_dict.update(rotation_loss=out[3])
             if 'translation' in comps:
                 loss_dict.update(translation_loss=out[4])
-            return out[0], loss_dict
+            return out, loss_dict
         raise RuntimeError('ComposedPatternLoss runs on fp32 device tensors only (got %s / %s); there is no CPU path'
                            % (ol.device, ol.dtype))
 

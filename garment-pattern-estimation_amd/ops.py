@@ -2510,15 +2510,22 @@ def quality_stats(ol_stats, rot_stats=None, tr_stats=None, tag_stats=None):
 
 def quality_metrics(flags, stats, B, P, Lp, outlines=None, gt_outlines=None, num_edges=None, num_panels=None, rotations=None,
                     gt_rotations=None, translations=None, gt_translations=None, stitch_tags=None, free_logits=None,
-                    stitches=None, nums=None, gt_free_mask=None):
+                    stitches=None, nums=None, gt_free_mask=None, part=None):
     """ComposedPatternLoss quality metrics (nn/metrics/composed_loss.py:365-424) in <= 3 launches, no host read:
     -> (out fp32 [14] in the order of QUALITY_KEYS, counts int32 [4]: contributors of the corr_ slots, include/gpe_hip.h).
     `flags` selects the components (QM_*), `stats` is quality_stats(...).  Predictions are the strided views of the decoders'
-    outputs; ground truth is what the loss matched (order / origin), any dtype (converted on the device)."""
+    outputs; ground truth is what the loss matched (order / origin), any dtype (converted on the device).
+    `part`: a caller-owned workspace for the per-pattern records, fp64 [B, 16] — B rows of a larger table that quality_pool folds
+    later with the same flags; the default is a private one."""
     ref = outlines if outlines is not None else free_logits
     _dev_check(ref)
     dev = ref.device
-    part = torch.empty(B * QUALITY_WS_DOUBLES, device=dev, dtype=torch.float64)
+    if part is None:
+        part = torch.empty(B * QUALITY_WS_DOUBLES, device=dev, dtype=torch.float64)
+    else:
+        _quality_table(part, 'quality_metrics: part', B)
+        if part.device != dev:
+            raise ValueError('quality_metrics: part lives on %s, the predictions on %s' % (part.device, dev))
     out = torch.empty(len(QUALITY_KEYS), device=dev, dtype=F32)
     counts = torch.empty(4, device=dev, dtype=torch.int32)
     main = flags & (QM_DISCRETE | QM_SHAPE | QM_ROT | QM_TR)
@@ -2558,6 +2565,152 @@ def quality_metrics(flags, stats, B, P, Lp, outlines=None, gt_outlines=None, num
                gt_free_mask.float().contiguous() if flags & QM_FREE else None, B, P, Lp, st_flags, stats, part)
     L.call('gpe_quality_finalize', part, B, P, Lp, flags, out, counts)
     return out, counts
+
+
+def _quality_table(t, what, rows=None):
+    if (not torch.is_tensor(t) or t.dtype != torch.float64 or t.dim() != 2 or t.shape[1] != QUALITY_WS_DOUBLES or t.shape[0] < 1
+            or not t.is_contiguous() or (rows is not None and t.shape[0] != rows)):
+        raise ValueError('%s must be a contiguous fp64 [%s, %d] tensor (got %s %s)'
+                         % (what, 'G' if rows is None else rows, QUALITY_WS_DOUBLES, getattr(t, 'dtype', type(t).__name__),
+                            tuple(getattr(t, 'shape', ()))))
+    if not t.is_cuda:
+        raise RuntimeError('gpe ops need tensors on the MI355X (got a %s table); there is no CPU path' % t.device)
+
+
+def quality_pool(table, group, n_groups, P, Lp, flags):
+    """The per-garment records of a whole data set (the `part` rows quality_metrics wrote, fp64 [G, 16]) folded per group and
+    overall: -> (out fp32 [n_groups + 1, 14], counts int32 [n_groups + 1, 4]).  Row g is bit for bit what quality_metrics returns
+    for the garments of group g alone, in table order, as one batch; the last row covers all garments.  group: int32 [G] on the
+    device (an id outside 0 .. n_groups-1 belongs to no group), or None with n_groups = 0.  One launch (include/gpe_hip_eval.h
+    gpe_eval_pool), no host read."""
+    _quality_table(table, 'quality_pool: table')
+    G = table.shape[0]
+    if isinstance(n_groups, bool) or not isinstance(n_groups, int) or not 0 <= n_groups <= 65535:
+        raise ValueError('quality_pool: n_groups must be an integer in 0 .. 65535 (got %r)' % (n_groups,))
+    if group is None:
+        if n_groups:
+            raise ValueError('quality_pool: %d groups need a group id per garment' % n_groups)
+    elif (not torch.is_tensor(group) or group.dtype != torch.int32 or tuple(group.shape) != (G,) or group.device != table.device
+          or not group.is_contiguous()):
+        raise ValueError('quality_pool: group must be a contiguous int32 [%d] tensor on the device of the table' % G)
+    out = torch.empty(n_groups + 1, len(QUALITY_KEYS), device=table.device, dtype=F32)
+    counts = torch.empty(n_groups + 1, 4, device=table.device, dtype=torch.int32)
+    L.call('gpe_eval_pool', table, group, G, n_groups, int(P), int(Lp), int(flags), out, counts)
+    return out, counts
+
+
+# QUALITY_KEYS index -> the contributor count (of the int32 [4] counts) that must be positive for the key to have a value; the other
+# keys always have one (corr_num_edges_accuracy included: the reference averages its 0 / 0 NaN in).  metrics._main_quality_metrics /
+# _stitch_quality_metrics apply these rules on the host, EvalAccumulator and Evaluator.pooled on the device / after the one read.
+QUALITY_GATES = {'corr_panel_shape_l2': 1, 'corr_rotation_l2': 0, 'corr_translation_l2': 0, 'corr_stitch_precision': 2,
+                 'corr_stitch_recall': 2}
+EVAL_MAX_KEYS, EVAL_MAX_SOURCES = 64, 4
+
+
+class EvalAccumulator:
+    """The reference's evaluation rule (nn/metrics/eval_utils.py:35-76: per key the mean of the per-batch values, a batch whose value is
+    None skipped) kept on the device: one launch per batch (include/gpe_hip_eval.h gpe_eval_add), ONE host read at the end.
+
+        acc = EvalAccumulator([('full_loss', 3, 0), ('pattern_loss', 0, 1), ('corr_rotation_l2', 2, 6)], {'corr_rotation_l2': 0})
+        for ...: acc.add(loss_vec, None, quality_vec, misc_vec, counts=counts)
+        result = acc.read()[0]             # {'full_loss': np.float32, ..., 'corr_rotation_l2': np.float32 or None}
+
+    keys: (name, source, index) per key, in the order of the result dict: the value of `name` in a batch is sources[source][index].
+    gates: {name: j} — the key is counted in a batch iff counts[j] > 0 (counts: quality_metrics' int32 [4]); other keys always.
+    slots: rows of accumulators (one per data folder); `.slot` is the device word that names the row the next add() goes to, set by
+    set_slot(i) as a queued copy — a captured add() serves every row."""
+
+    def __init__(self, keys, gates=None, slots=1, device='cuda'):
+        import ctypes
+        keys, gates = [tuple(k) for k in keys], dict(gates or {})
+        if not 1 <= len(keys) <= EVAL_MAX_KEYS:
+            raise ValueError('EvalAccumulator: 1 .. %d keys (got %d)' % (EVAL_MAX_KEYS, len(keys)))
+        if isinstance(slots, bool) or not isinstance(slots, int) or slots < 1:
+            raise ValueError('EvalAccumulator: slots must be a positive integer (got %r)' % (slots,))
+        names = [k[0] for k in keys]
+        if len(set(names)) != len(names) or set(gates) - set(names):
+            raise ValueError('EvalAccumulator: key names must be distinct and every gate must name a key')
+        packed = []
+        for name, src, idx in keys:
+            g = gates.get(name)
+            if not (0 <= src < EVAL_MAX_SOURCES and 0 <= idx < 256 and (g is None or 0 <= g < 4)):
+                raise ValueError('EvalAccumulator: key %r: source 0 .. 3, index 0 .. 255, gate 0 .. 3 (got %r, %r, %r)' % (name, src, idx, g))
+            packed.append(idx | (src << 8) | ((0 if g is None else g + 1) << 16))
+        self.device = torch.device(device)
+        if self.device.type != 'cuda':
+            raise RuntimeError('gpe ops need tensors on the MI355X (got device %s); there is no CPU path' % self.device)
+        self.keys, self.names, self.gated, self.slots = keys, names, bool(gates), slots
+        self.n_sources = 1 + max(k[1] for k in keys)
+        self._need = [1 + max([k[2] for k in keys if k[1] == s], default=-1) for s in range(self.n_sources)]
+        self._packed = (ctypes.c_int32 * len(packed))(*packed)
+        K = len(keys)
+        # one allocation, one read: sum [slots, K] as its fp32 bits | cnt [slots, K] | batches [slots] | status [1]
+        self.state = torch.zeros(2 * slots * K + slots + 1, device=self.device, dtype=torch.int32)
+        self.sum = self.state[:slots * K].view(F32).view(slots, K)
+        self.cnt = self.state[slots * K:2 * slots * K].view(slots, K)
+        self.batches = self.state[2 * slots * K:2 * slots * K + slots]
+        self.status = self.state[-1:]
+        self.slot = torch.zeros(1, device=self.device, dtype=torch.int32)
+        self._slot_host = torch.arange(slots, dtype=torch.int32).pin_memory()      # sources of set_slot's queued one-word copies
+
+    def reset(self):
+        """sums, counts, batches and the status back to zero, the slot word to row 0 (queued; no device read)"""
+        self.state.zero_()
+        self.slot.zero_()
+
+    def set_slot(self, i):
+        """the following add() calls go to row i: a queued copy from pinned memory, no device read"""
+        if isinstance(i, bool) or not isinstance(i, int) or not 0 <= i < self.slots:
+            raise ValueError('EvalAccumulator.set_slot: row 0 .. %d (got %r)' % (self.slots - 1, i))
+        self.slot.copy_(self._slot_host[i:i + 1], non_blocking=True)
+
+    def add(self, *sources, counts=None):
+        """one batch: sources[s] is the fp32 device vector the keys of source s index (None where no key refers to it)"""
+        if len(sources) > EVAL_MAX_SOURCES or len(sources) < self.n_sources:
+            raise ValueError('EvalAccumulator.add: %d .. %d source vectors (got %d)' % (self.n_sources, EVAL_MAX_SOURCES, len(sources)))
+        args = []
+        for s in range(EVAL_MAX_SOURCES):
+            t = sources[s] if s < len(sources) else None
+            need = self._need[s] if s < self.n_sources else 0
+            if t is None:
+                if need:
+                    raise ValueError('EvalAccumulator.add: source %d is None but keys refer to it' % s)
+                args += [None, 0]
+                continue
+            if not torch.is_tensor(t) or t.dtype != F32 or t.dim() != 1 or not t.is_contiguous() or t.numel() < need or t.numel() > 256:
+                raise ValueError('EvalAccumulator.add: source %d must be a contiguous fp32 vector of %d .. 256 values (got %s %s)'
+                                 % (s, need, getattr(t, 'dtype', type(t).__name__), tuple(getattr(t, 'shape', ()))))
+            _dev_check(t)
+            args += [t.detach(), t.numel()]
+        if self.gated and counts is None:
+            raise ValueError('EvalAccumulator.add: gated keys need the contributor counts')
+        if counts is not None and (counts.dtype != torch.int32 or counts.numel() != 4 or not counts.is_contiguous() or not counts.is_cuda):
+            raise ValueError('EvalAccumulator.add: counts must be a contiguous int32 [4] device tensor')
+        L.call('gpe_eval_add', *args, len(sources), counts, self._packed, len(self.keys), self.sum, self.cnt, self.batches, self.slot,
+               self.slots, self.status)
+
+    def read(self, along=()):
+        """THE host read -> one dict per row: np.float32(sum) / np.float32(cnt) per key, None where the key was never counted (the
+        reference's None for an empty list).  `.last_sums` / `.last_counts` / `.last_batches` keep what was read.  along: further
+        device tensors of fp32 / int32 to bring over in the same transfer; `.last_along` holds them as numpy arrays of their own
+        dtype and shape, in order."""
+        K, S = len(self.keys), self.slots
+        along = [t.detach() for t in along]
+        if any(t.dtype not in (F32, torch.int32) or t.device != self.state.device for t in along):
+            raise ValueError('EvalAccumulator.read: along takes fp32 / int32 tensors on the accumulator\'s device')
+        parts = [self.state] + [t.contiguous().view(torch.int32).reshape(-1) for t in along]
+        host = (torch.cat(parts) if along else self.state).cpu().numpy()
+        edges = np.cumsum([p.numel() for p in parts])
+        self.last_along = [host[a:b].view(np.float32 if t.dtype == F32 else np.int32).reshape(tuple(t.shape))
+                           for a, b, t in zip(edges[:-1], edges[1:], along)]
+        host = host[:edges[0]]
+        if host[-1]:
+            raise RuntimeError('EvalAccumulator: an add() met a slot word outside 0 .. %d and was dropped' % (S - 1))
+        sums = host[:S * K].view(np.float32).reshape(S, K)
+        cnts = host[S * K:2 * S * K].reshape(S, K)
+        self.last_sums, self.last_counts, self.last_batches = sums, cnts, host[2 * S * K:2 * S * K + S]
+        return [{n: (np.float32(sums[s, k]) / np.float32(cnts[s, k]) if cnts[s, k] else None) for k, n in enumerate(self.names)}
+                for s in range(S)]
 
 
 # -------------------------------------------------------------------------------------------------
