@@ -436,26 +436,21 @@ def _init_weights(module, init_type=''):
 
 
 def _rnn_params(rnn, n_layers):
-    ps = []
-    for l in range(n_layers):
-        ps += [getattr(rnn, 'weight_ih_l%d' % l), getattr(rnn, 'weight_hh_l%d' % l),
-               getattr(rnn, 'bias_ih_l%d' % l), getattr(rnn, 'bias_hh_l%d' % l)]
-    return ps
+    """the parameters of an nn.LSTM / nn.GRU as ops.rnn_stack takes them: flat, ops.RNN_PARAMS per layer (ops.rnn_layers is the inverse)"""
+    return [getattr(rnn, '%s_l%d' % (name, l)) for l in range(n_layers) for name in ('weight_ih', 'weight_hh', 'bias_ih', 'bias_hh')]
 
 
 def _register_rnn_packs(plan, rnn, n_layers, hidden, gates):
-    for l in range(n_layers):
-        w_ih, w_hh = getattr(rnn, 'weight_ih_l%d' % l), getattr(rnn, 'weight_hh_l%d' % l)
-        plan.add_linear(w_ih)
-        plan.add_gates(w_hh, hidden, gates)
-        plan.add_linear(w_hh, fwd=False, bwd=True)
-        b_ih, b_hh = getattr(rnn, 'bias_ih_l%d' % l), getattr(rnn, 'bias_hh_l%d' % l)
+    for l, ly in enumerate(ops.rnn_layers(_rnn_params(rnn, n_layers), n_layers)):
+        plan.add_linear(ly.w_ih)
+        plan.add_gates(ly.w_hh, hidden, gates)
+        plan.add_linear(ly.w_hh, fwd=False, bwd=True)
         if l > 0:
-            plan.add_gates(w_ih, hidden, gates)        # layers > 0 project h_{l-1,t} inside the fused cell launch
+            plan.add_gates(ly.w_ih, hidden, gates)     # layers > 0 project h_{l-1,t} inside the fused cell launch
         if gates == 4:
-            plan.add_bias_sum(b_ih, b_hh)
+            plan.add_bias_sum(ly.b_ih, ly.b_hh)
         else:
-            plan.add_gru_bias(b_ih, b_hh, hidden)
+            plan.add_gru_bias(ly.b_ih, ly.b_hh, hidden)
 
 
 class LSTMEncoderModule(nn.Module):

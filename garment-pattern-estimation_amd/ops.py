@@ -157,13 +157,43 @@ def side_grads(params, tensors):
 # PackPlan: weight-derived operands refreshed by one launch
 # -------------------------------------------------------------------------------------------------
 WEIGHTS_EPOCH = 0          # bumped by optimizers that update parameters through raw pointers (optim.FusedAdam)
-_PACKS = {}                # (param data_ptr, kind) -> (plan, output tensor); a plan's entries die with the plan (weakref.finalize)
+_PACKS = {}                # (param data_ptr, kind) -> (weakref to the plan, output tensor, index of the job in plan.specs); a plan's
+#                            entries die with the plan (weakref.finalize)
 
 K_PLAIN, K_TRANS, K_GATES, K_PQ, K_PQT, K_VADD, K_BPQ, K_GRUB = 0, 1, 2, 3, 4, 5, 6, 7
 K_GATES_H3, K_AMAX, K_TRANS_H3 = 8, 9, 10      # f16x3 operands of the recurrences: fp16 plane packs + the amax job they depend on
+PLANE_KINDS = (K_GATES_H3, K_TRANS_H3)
 _JOB = np.dtype([('w', '<u8'), ('w2', '<u8'), ('out', '<u8'), ('total', '<i8'), ('first_block', '<i8'),
                  ('ldw', '<i4'), ('N', '<i4'), ('K', '<i4'), ('kind', '<i4'), ('Npad', '<i4'), ('aux', '<i4')])
 assert _JOB.itemsize == 64
+# one job of a PackPlan: source parameter, second source (a bias pair) or None, K_* kind, output rows and columns, the kind's own
+# number (units per gate, width of a half), length of a vector output or None
+PackSpec = collections.namedtuple('PackSpec', 'p p2 kind N K aux out_numel')
+
+
+def _pack_geometry(sp):
+    """-> (Npad, total) of a PackSpec: the padded row count its job record carries and the floats of its output"""
+    if sp.kind in (K_VADD, K_BPQ, K_GRUB):
+        return 0, sp.out_numel
+    if sp.kind in (K_GATES, K_GATES_H3):
+        npad = 16 * (sp.N // sp.aux) * ((sp.aux + 15) // 16)      # gate-interleaved: each gate's units filled up to whole blocks of 16
+    else:
+        npad = round_up(sp.N, 16)
+    if sp.kind == K_GATES:
+        return npad, npad * round_up(sp.K, 16)
+    if sp.kind in PLANE_KINDS:
+        return npad, L.query('gpe_packed_planes_size', npad, sp.K)
+    return npad, L.query('gpe_packed_size', sp.N, sp.K)           # K filled up to the edge kernels' resident chunk count
+
+
+def _job_table(rows, dev):
+    """rows: per job the fields of _JOB without first_block -> (the records gpe_pack_multi reads, as bytes on `dev`; blocks of the launch)"""
+    tab = np.zeros(len(rows), dtype=_JOB)
+    blk = 0
+    for i, (w, w2, out, total, ldw, N, K, kind, npad, aux) in enumerate(rows):
+        tab[i] = (w, w2, out, total, blk, ldw, N, K, kind, npad, aux)
+        blk += L.query('gpe_pack_job_blocks', kind, total, npad, K)
+    return torch.from_numpy(tab.view(np.uint8).copy()).to(dev), blk
 
 
 # (PackPlan.refresh on a side stream under the layer-1 kNN search was built in round 5 and MEASURED SLOWER — cfg 2, one session, twice
@@ -193,7 +223,7 @@ class PackPlan:
     one stream to another between forwards is handled: refresh() makes the new stream wait for the previous one."""
 
     def __init__(self):
-        self.specs = []        # (param, param2, kind, N, K, aux)
+        self.specs = []        # PackSpec records, one per job
         self.outs = []
         self.table = None
         self.blocks = 0
@@ -211,7 +241,7 @@ class PackPlan:
         self._me = me
 
     def _add(self, p, kind, N, K, aux=0, p2=None, out_numel=None):
-        self.specs.append((p, p2, kind, N, K, aux, out_numel))
+        self.specs.append(PackSpec(p, p2, kind, N, K, aux, out_numel))
 
     def add_linear(self, w, fwd=True, bwd=True):
         if fwd:
@@ -243,7 +273,7 @@ class PackPlan:
         self._add(b_ih, K_GRUB, b_ih.numel(), 0, aux=2 * H, p2=b_hh, out_numel=b_ih.numel())
 
     def _versions(self):
-        return [p._version + (p2._version if p2 is not None else 0) for p, p2, *_ in self.specs]
+        return [sp.p._version + (sp.p2._version if sp.p2 is not None else 0) for sp in self.specs]
 
     def _build(self):
         for k in self.keys:
@@ -251,72 +281,41 @@ class PackPlan:
                 _PACKS.pop(k, None)
         self.keys, self.outs = [], []
         del self._keys_box[:]
-        dev = self.specs[0][0].device
-        tab = np.zeros(len(self.specs), dtype=_JOB)
-        blk = 0
-        # f16x3 plane packs are normalised by their tensor's largest magnitude: one amax word per planes job, filled by a kind-9
-        # job of an EARLIER launch (self.pre_table) into self.words (zeroed before every refresh)
-        h3 = [i for i, sp in enumerate(self.specs) if sp[2] in (K_GATES_H3, K_TRANS_H3)]
-        # ... one word and one amax job per MATRIX (its gate-interleaved and its transposed planes share them)
-        mats = []
-        for i in h3:
-            if all(self.specs[i][0] is not self.specs[j][0] for j in mats):
-                mats.append(i)
+        dev = self.specs[0].p.device
+        # f16x3 plane packs are normalised by their tensor's largest magnitude: one amax word per MATRIX (its gate-interleaved and
+        # its transposed planes share it), numbered by first appearance and filled by a kind-9 job of an EARLIER launch
+        # (self.pre_table) into self.words (zeroed before every refresh)
+        mats = {id(sp.p): sp.p for sp in self.specs if sp.kind in PLANE_KINDS}       # (a dict keeps the order of first insertion)
         self.words = torch.zeros(max(len(mats), 1), device=dev, dtype=torch.int32)
-        pre = np.zeros(len(mats), dtype=_JOB)
-        pblk = 0
-        for wi, i in enumerate(mats):
-            p = self.specs[i][0]
-            n_el = p.numel()
-            pre[wi] = (p.data_ptr(), 0, self.words[wi:wi + 1].data_ptr(), n_el, pblk, p.stride(0), p.shape[0], p.shape[1], K_AMAX, 0, 0)
-            pblk += L.query('gpe_pack_job_blocks', K_AMAX, n_el, 0, 0)
-        self.pre_blocks = pblk
-        self.pre_table = torch.from_numpy(pre.view(np.uint8).copy()).to(dev) if h3 else None
-        self.word_of = {}
-        for i, (p, p2, kind, N, K, aux, out_numel) in enumerate(self.specs):
-            w2 = p2.data_ptr() if p2 is not None else 0
-            if kind in (K_VADD, K_BPQ, K_GRUB):
-                total, npad = out_numel, 0
-            elif kind == K_GATES:
-                npad = 16 * (N // aux) * ((aux + 15) // 16)
-                total = npad * round_up(K, 16)
-            elif kind in (K_GATES_H3, K_TRANS_H3):
-                npad = 16 * (N // aux) * ((aux + 15) // 16) if kind == K_GATES_H3 else round_up(N, 16)
-                total = L.query('gpe_packed_planes_size', npad, K)
-                wi = [j for j, m_ in enumerate(mats) if self.specs[m_][0] is p][0]
-                word = self.words[wi:wi + 1]
-                w2 = word.data_ptr()
-                self.word_of[(p.data_ptr(), kind)] = word
-            else:
-                npad = round_up(N, 16)
-                total = L.query('gpe_packed_size', N, K)      # K filled up to the edge kernels' resident chunk count
+        word = {m: self.words[wi:wi + 1] for wi, m in enumerate(mats)}
+        pre = [(p.data_ptr(), 0, word[m].data_ptr(), p.numel(), p.stride(0), p.shape[0], p.shape[1], K_AMAX, 0, 0) for m, p in mats.items()]
+        self.pre_table, self.pre_blocks = _job_table(pre, dev) if mats else (None, 0)
+        rows, self.word_of = [], {}
+        for i, sp in enumerate(self.specs):
+            npad, total = _pack_geometry(sp)
             out = torch.empty(total, device=dev, dtype=F32)
             self.outs.append(out)
-            tab[i] = (p.data_ptr(), w2, out.data_ptr(), total, blk,
-                      p.stride(0) if p.dim() == 2 else 0, N, K, kind, npad, aux)
-            blk += L.query('gpe_pack_job_blocks', kind, total, npad, K)
-            key = (p.data_ptr(), kind)
+            key = (sp.p.data_ptr(), sp.kind)
+            w2 = sp.p2.data_ptr() if sp.p2 is not None else 0
+            if sp.kind in PLANE_KINDS:
+                self.word_of[key] = word[id(sp.p)]
+                w2 = word[id(sp.p)].data_ptr()
+            rows.append((sp.p.data_ptr(), w2, out.data_ptr(), total, sp.p.stride(0) if sp.p.dim() == 2 else 0, sp.N, sp.K, sp.kind, npad, sp.aux))
             _PACKS[key] = (self._me, out, i)
             self.keys.append(key)
             self._keys_box.append(key)
-        self.blocks = blk
-        self.table = torch.from_numpy(tab.view(np.uint8).copy()).to(dev)
+        self.table, self.blocks = _job_table(rows, dev)
         # the same table without the fp16-plane jobs, for every arithmetic mode but f16x3 (their outputs and amax words are only
         # read by the f16x3 recurrences: ADVICE r4 — two launches and the plane arithmetic per step for nothing)
-        keep = [i for i in range(len(self.specs)) if i not in h3]
-        tab2 = tab[keep].copy()
-        blk2 = 0
-        for j in range(len(keep)):
-            tab2[j]['first_block'] = blk2
-            blk2 += L.query('gpe_pack_job_blocks', int(tab2[j]['kind']), int(tab2[j]['total']), int(tab2[j]['Npad']), int(tab2[j]['K']))
-        self.table_noh3 = torch.from_numpy(tab2.view(np.uint8).copy()).to(dev) if h3 else self.table
-        self.blocks_noh3, self.n_noh3 = (blk2, len(keep)) if h3 else (blk, len(self.specs))
+        noh3 = [row for row, sp in zip(rows, self.specs) if sp.kind not in PLANE_KINDS]
+        self.table_noh3, self.blocks_noh3 = _job_table(noh3, dev) if mats else (self.table, self.blocks)
+        self.n_noh3 = len(noh3)
         self.home = self._home()
 
     def _home(self):
         """where every source parameter lives right now: the job table holds raw pointers, so ANY parameter that moved
         (a partial re-homing, `p.data = ...` on a subset) must rebuild it"""
-        return tuple((p.data_ptr(), p2.data_ptr() if p2 is not None else 0, p.device) for p, p2, *_ in self.specs)
+        return tuple((sp.p.data_ptr(), sp.p2.data_ptr() if sp.p2 is not None else 0, sp.p.device) for sp in self.specs)
 
     def refresh(self):
         """Called at the start of a model forward: one gpe_pack_multi launch (skipped only by a `frozen` plan whose parameters'
@@ -324,42 +323,45 @@ class PackPlan:
         if not self.specs:
             return
         vers = self._versions()
-        if self.specs[0][0].is_cuda:
-            st = torch.cuda.current_stream(self.specs[0][0].device)
+        first = self.specs[0].p
+        if first.is_cuda:
+            st = torch.cuda.current_stream(first.device)
             if self._stream is not None and st != self._stream:
                 st.wait_stream(self._stream)     # the packs / words the previous stream's launches still read are about to change
             self._stream = st
-        if self.table is None or self.home != self._home():
+        rebuilt = self.table is None or self.home != self._home()
+        if rebuilt:
             self._build()                      # first use, or a parameter moved (.to(device), arena re-homing)
-        elif (self.frozen and self.vers == vers and self.epoch == WEIGHTS_EPOCH and
-              self.h3_current == (self.pre_table is not None and L.get_math() == 'f16x3')):   # (a mode change re-runs the packs)
-            return
-        self.h3_current = self.pre_table is not None and L.get_math() == 'f16x3'
-
-        def launches():
-            if self.h3_current:
-                self.words.zero_()
-                L.call('gpe_pack_multi', self.pre_table, self.pre_table.numel() // 64, self.pre_blocks)
-                L.call('gpe_pack_multi', self.table, len(self.specs), self.blocks)
-            else:
-                L.call('gpe_pack_multi', self.table_noh3, self.n_noh3, self.blocks_noh3)
-
-        launches()
+        h3 = self.pre_table is not None and L.get_math() == 'f16x3'        # the planes are wanted now
+        if not rebuilt and self.frozen and self.vers == vers and self.epoch == WEIGHTS_EPOCH and self.h3_current == h3:
+            return                             # (a mode change re-runs the packs)
+        self.h3_current = h3
+        if h3:
+            self.words.zero_()
+            L.call('gpe_pack_multi', self.pre_table, self.pre_table.numel() // 64, self.pre_blocks)
+            L.call('gpe_pack_multi', self.table, len(self.specs), self.blocks)
+        else:
+            L.call('gpe_pack_multi', self.table_noh3, self.n_noh3, self.blocks_noh3)
         self.vers, self.epoch = vers, WEIGHTS_EPOCH
+
+
+def _current(t, kind, t2=None):
+    """-> (plan, its persistent packed operand of parameter `t`) if a PackPlan owns one that is still current, else (None, None)"""
+    hit = _PACKS.get((t.data_ptr(), kind))
+    if hit is None:
+        return None, None
+    ref, out, i = hit
+    plan = ref()
+    if plan is None or plan.vers is None or plan.epoch != WEIGHTS_EPOCH:
+        return None, None
+    if plan.vers[i] != t._version + (t2._version if t2 is not None else 0):
+        return None, None
+    return plan, out
 
 
 def _planned(t, kind, t2=None):
     """The persistent packed operand of parameter `t` if a PackPlan owns one that is still current, else None."""
-    hit = _PACKS.get((t.data_ptr(), kind))
-    if hit is None:
-        return None
-    plan, out, i = hit
-    plan = plan()
-    if plan is None or plan.vers is None or plan.epoch != WEIGHTS_EPOCH:
-        return None
-    if plan.vers[i] != t._version + (t2._version if t2 is not None else 0):
-        return None
-    return out
+    return _current(t, kind, t2)[1]
 
 
 # -------------------------------------------------------------------------------------------------
@@ -417,12 +419,8 @@ def pack_gates(w, H, G=4):
 def planned_planes(w, kind):
     """(fp16 plane pack, amax word) of a recurrent weight when a PackPlan owns them (f16x3 arithmetic of the recurrences), else
     (None, None): the wavefront kernels then run the exact fp32 instruction."""
-    hit = _PACKS.get((w.data_ptr(), kind))
-    if hit is None:
-        return None, None
-    plan = hit[0]()
-    out = _planned(w, kind)
-    if plan is None or out is None or not plan.h3_current:   # (planes are only rebuilt by a refresh that ran in f16x3 mode)
+    plan, out = _current(w, kind)
+    if plan is None or not plan.h3_current:                  # (planes are only rebuilt by a refresh that ran in f16x3 mode)
         return None, None
     return out, plan.word_of.get((w.data_ptr(), kind))
 
@@ -1391,6 +1389,63 @@ def asap_pool(x, B, N, params, ratio, order=None, trace=None):
 # recurrent stacks (LSTM / GRU)
 # -------------------------------------------------------------------------------------------------
 RNN_WS_HOOK = None         # measurement aid (scripts/rnn_trace.py): called with ('fwd' | 'bwd', workspace tensor) of every recurrence
+RNN_PARAMS = ('w_ih', 'w_hh', 'b_ih', 'b_hh')                    # the tensors of one layer as autograd takes them: flat, layer by layer
+RNNLayer = collections.namedtuple('RNNLayer', RNN_PARAMS)
+NO_PLANES = (None, None, None, None)
+
+
+def rnn_layers(params, n_layers):
+    """the inverse of net_blocks._rnn_params: n_layers RNNLayer records"""
+    P = len(RNN_PARAMS)
+    assert len(params) == P * n_layers
+    return [RNNLayer(*params[P * l: P * l + P]) for l in range(n_layers)]
+
+
+def rnn_grads(n_layers, filed=None, d_x=None, d_h0=None, d_c0=None):
+    """What RNNStackFn.backward returns: d_x, d_h0, d_c0, None up to the parameters, the gradients `filed` as {(layer, parameter field):
+    tensor} at their places in _rnn_params' order"""
+    out = [d_x, d_h0, d_c0] + [None] * (RNNStackFn.LEAD - 3 + len(RNN_PARAMS) * n_layers)
+    for (l, field), g in (filed or {}).items():
+        out[RNNStackFn.LEAD + len(RNN_PARAMS) * l + RNN_PARAMS.index(field)] = g
+    return tuple(out)
+
+
+def rnn_planes(layers, kind):
+    """-> (hh planes, ih planes, hh amax words, ih amax words) per layer, entry 0 of the ih lists unused: the plan's fp16 plane packs of
+    `kind` (K_GATES_H3, K_TRANS_H3) of every recurrent weight for the f16x3 arithmetic; NO_PLANES unless every one of them is there
+    (the kernels then run the exact fp32 instruction)"""
+    hh = [planned_planes(ly.w_hh, kind) for ly in layers]
+    ih = [planned_planes(ly.w_ih, kind) for ly in layers[1:]]
+    if any(t is None for pair in hh + ih for t in pair):
+        return NO_PLANES
+    return [p for p, _ in hh], [None] + [p for p, _ in ih], [a for _, a in hh], [None] + [a for _, a in ih]
+
+
+def _strides(t, n):
+    """the first n strides of t; zeros for a tensor that is not there"""
+    return (0,) * n if t is None else tuple(t.stride()[:n])
+
+
+def _ptr_arrays(lists):
+    return [None if ts is None else _ptr_array(ts) for ts in lists]
+
+
+# the two recurrence entry points by keyword (include/gpe_hip.h): each ends in its one L.call, arguments in the header's order.  dims =
+# (L, T, Bn, H); per-layer operands are lists (the pointer arrays are built here and live until the launch is queued — the CALLER keeps
+# the tensors themselves); strides are read off the tensors; cs: None for a GRU; planes: rnn_planes(..)
+def rnn_seq_fwd(*, gates, dims, xproj, whh, wih, bias, bhn, hs, cs, saved, planes, ws):
+    """xproj = (layer 0's input projection, its row stride, its step stride); wih[0], bias[0] unused; bhn: the GRU's b_hn slices or None;
+    ws = (arrival counters of the persistent launch or None, bytes)"""
+    L.call('gpe_rnn_seq_fwd', gates, *dims, *xproj, *_ptr_arrays((whh, wih, bias, bhn)), hs, *_strides(hs, 3), cs, *_strides(cs, 2),
+           saved, *_strides(saved, 2), *_ptr_arrays(planes), *ws)
+
+
+def rnn_seq_bwd(*, gates, dims, g_top, d_hN, d_cN, whh_t, wih_t, hs, cs, saved, dgx, dgh, part, carry, planes):
+    """g_top [Bn, T, H] (unit stride inside a row), d_hN, d_cN: the gradients that arrived, or None; dgx, dgh: gate gradients out (one
+    tensor for an LSTM), same strides"""
+    assert dgh.stride() == dgx.stride()
+    L.call('gpe_rnn_seq_bwd', gates, *dims, g_top, *_strides(g_top, 2), d_hN, d_cN, *_ptr_arrays((whh_t, wih_t)), hs, *_strides(hs, 3),
+           cs, *_strides(cs, 2), saved, *_strides(saved, 2), dgx, dgh, *_strides(dgx, 3), part, carry, *_ptr_arrays(planes))
 
 
 class RNNStackFn(torch.autograd.Function):
@@ -1406,6 +1461,7 @@ class RNNStackFn(torch.autograd.Function):
     gradients are reduce-GEMMs over all Bn*T rows afterwards.  Gate orders follow torch: LSTM i,f,g,o; GRU r,z,n.
     Start states may carry gradient (LSTMDoubleReverseDecoderModule threads the first LSTM's final state into the
     second), final states too."""
+    LEAD = 8                   # forward's arguments in front of *params
 
     @staticmethod
     def forward(ctx, x, h0, c0, T, n_layers, kind, want_state, h0_ok, *params):
@@ -1428,47 +1484,33 @@ class RNNStackFn(torch.autograd.Function):
             cs = torch.empty(Lr, T + 1, Bn, Hh, device=dev, dtype=F32)
             cs[:, 0].copy_(c0)
         saved = torch.empty(Lr, T, Bn, 4 * Hh, device=dev, dtype=F32)
-        w_ih0, _, b_ih0, b_hh0 = params[0:4]
-        bias0 = bias_sum(b_ih0, b_hh0) if lstm else gru_bias(b_ih0, b_hh0, Hh)
+        layers = rnn_layers(params, Lr)
+        # the operands of every layer — fused bias, gate packs (layer 0's input weight is a GEMM of its own, below), the GRU's b_hn —
+        # stay referenced by these lists until the launch is queued
+        whh, wih, biases = [], [], []
+        for l, ly in enumerate(layers):
+            biases.append(bias_sum(ly.b_ih, ly.b_hh) if lstm else gru_bias(ly.b_ih, ly.b_hh, Hh))
+            whh.append(pack_gates(ly.w_hh, Hh, G))
+            wih.append(pack_gates(ly.w_ih, Hh, G) if l > 0 else None)
+        bhns = None if lstm else [ly.b_hh[2 * Hh:] for ly in layers]
         if seq:
             xproj = torch.empty(Bn, T, G * Hh, device=dev, dtype=F32)
-            linear_raw(_rows3d(x), pack_weight(w_ih0), bias0, Bn * T, G * Hh, In, (xproj, G * Hh, 0, 0))
+            linear_raw(_rows3d(x), pack_weight(layers[0].w_ih), biases[0], Bn * T, G * Hh, In, (xproj, G * Hh, 0, 0))
             xp_sb, xp_st = T * G * Hh, G * Hh
         else:
             xproj = torch.empty(Bn, G * Hh, device=dev, dtype=F32)
-            linear_raw(_rows2d(x), pack_weight(w_ih0), bias0, Bn, G * Hh, In, _rows2d(xproj))
+            linear_raw(_rows2d(x), pack_weight(layers[0].w_ih), biases[0], Bn, G * Hh, In, _rows2d(xproj))
             xp_sb, xp_st = G * Hh, 0
-        whh, wih, biases, bhns = [], [None], [None], []
-        for l in range(Lr):
-            w_ih, w_hh, b_ih, b_hh = params[4 * l: 4 * l + 4]
-            whh.append(pack_gates(w_hh, Hh, G))
-            if l > 0:
-                wih.append(pack_gates(w_ih, Hh, G))
-                biases.append(bias_sum(b_ih, b_hh) if lstm else gru_bias(b_ih, b_hh, Hh))
-            bhns.append(None if lstm else b_hh[2 * Hh:])
         # f16x3 arithmetic: the plan's fp16 plane packs + amax words of every recurrent weight (absent -> exact fp32 kernels)
-        pl_hh, am_hh, pl_ih, am_ih = [], [], [None], [None]
-        for l in range(Lr):
-            w_ih, w_hh = params[4 * l], params[4 * l + 1]
-            a, b = planned_planes(w_hh, K_GATES_H3)
-            pl_hh.append(a); am_hh.append(b)
-            if l > 0:
-                a, b = planned_planes(w_ih, K_GATES_H3)
-                pl_ih.append(a); am_ih.append(b)
         # (h0_ok: the fp16-pipe kernels scale the state rows by GPE_STATE_SA = 2^12 (csrc/gpe_device.h) before the fp16 split — a start
         # state of magnitude >= 16 would overflow to inf; rnn_stack decides)
-        h3 = bool(h0_ok) and all(t is not None for t in pl_hh + am_hh + pl_ih[1:] + am_ih[1:])
-        keep = (whh, wih, biases, pl_hh, am_hh, pl_ih, am_ih)   # operands stay referenced until the launches are queued
+        planes = rnn_planes(layers, K_GATES_H3) if h0_ok else NO_PLANES
         ws_n = L.query('gpe_rnn_seq_fwd_ws', G, Lr, T, Bn, Hh)    # arrival counters of the persistent launch (0: diagonal launches)
         ws = torch.empty(ws_n, device=dev, dtype=torch.uint8) if ws_n > 0 else None
         if RNN_WS_HOOK is not None:
             RNN_WS_HOOK('fwd', ws)
-        L.call('gpe_rnn_seq_fwd', G, Lr, T, Bn, Hh, xproj, xp_sb, xp_st, _ptr_array(whh), _ptr_array(wih),
-               _ptr_array(biases), None if lstm else _ptr_array(bhns), hs, hs.stride(0), hs.stride(1), hs.stride(2),
-               cs, cs.stride(0) if lstm else 0, cs.stride(1) if lstm else 0, saved, saved.stride(0), saved.stride(1),
-               _ptr_array(pl_hh) if h3 else None, _ptr_array(pl_ih) if h3 else None,
-               _ptr_array(am_hh) if h3 else None, _ptr_array(am_ih) if h3 else None, ws, max(ws_n, 0))
-        del keep
+        rnn_seq_fwd(gates=G, dims=(Lr, T, Bn, Hh), xproj=(xproj, xp_sb, xp_st), whh=whh, wih=wih, bias=[None] + biases[1:], bhn=bhns,
+                    hs=hs, cs=cs, saved=saved, planes=planes, ws=(ws, max(ws_n, 0)))
         hN = cN = None
         if want_state:
             hN = hs[:, :, T, :Hh].contiguous()
@@ -1489,6 +1531,7 @@ class RNNStackFn(torch.autograd.Function):
         sv = ctx.saved_tensors
         x, hs, cs, saved = sv[:4]
         params = sv[4:]
+        layers = rnn_layers(params, Lr)
         dev = x.device
         want_h0, want_c0 = ctx.needs_state_grad
         GH = G * Hh
@@ -1499,29 +1542,16 @@ class RNNStackFn(torch.autograd.Function):
         if RNN_WS_HOOK is not None:
             RNN_WS_HOOK('bwd', part)
         carry = torch.empty(2, Lr, Bn, Hh, device=dev, dtype=F32)
-        whh_t = [pack_weight(params[4 * l + 1], transpose=True) for l in range(Lr)]
-        wih_t = [None] + [pack_weight(params[4 * l], transpose=True) for l in range(1, Lr)]
+        whh_t = [pack_weight(ly.w_hh, transpose=True) for ly in layers]
+        wih_t = [None] + [pack_weight(ly.w_ih, transpose=True) for ly in layers[1:]]
         if g_top is not None and g_top.stride(2) != 1:
             g_top = g_top.contiguous()
         ghN = g_hN.contiguous() if g_hN is not None else None
         gcN = g_cN.contiguous() if (lstm and g_cN is not None) else None
         # f16x3: transposed fp16 plane packs + amax words for the persistent backward launch (absent -> exact fp32 there)
-        tp_hh, ta_hh, tp_ih, ta_ih = [], [], [None], [None]
-        if lstm:
-            for l in range(Lr):
-                a, b = planned_planes(params[4 * l + 1], K_TRANS_H3)
-                tp_hh.append(a); ta_hh.append(b)
-                if l > 0:
-                    a, b = planned_planes(params[4 * l], K_TRANS_H3)
-                    tp_ih.append(a); ta_ih.append(b)
-        h3b = lstm and all(t is not None for t in tp_hh + ta_hh + tp_ih[1:] + ta_ih[1:])
-        L.call('gpe_rnn_seq_bwd', G, Lr, T, Bn, Hh, g_top, g_top.stride(0) if g_top is not None else 0,
-               g_top.stride(1) if g_top is not None else 0, ghN, gcN, _ptr_array(whh_t), _ptr_array(wih_t),
-               hs, hs.stride(0), hs.stride(1), hs.stride(2), cs, cs.stride(0) if lstm else 0, cs.stride(1) if lstm else 0,
-               saved, saved.stride(0), saved.stride(1), dgx, dgh, dgx.stride(0), dgx.stride(1), dgx.stride(2), part, carry,
-               _ptr_array(tp_hh) if h3b else None, _ptr_array(tp_ih) if h3b else None,
-               _ptr_array(ta_hh) if h3b else None, _ptr_array(ta_ih) if h3b else None)
-        grads = [None] * (4 * Lr)
+        rnn_seq_bwd(gates=G, dims=(Lr, T, Bn, Hh), g_top=g_top, d_hN=ghN, d_cN=gcN, whh_t=whh_t, wih_t=wih_t, hs=hs, cs=cs, saved=saved,
+                    dgx=dgx, dgh=dgh, part=part, carry=carry, planes=rnn_planes(layers, K_TRANS_H3) if lstm else NO_PLANES)
+        filed = {}
         d_x = None
         d_h0 = torch.empty(Lr, Bn, Hh, device=dev, dtype=F32) if want_h0 else None
         d_c0 = carry[0].clone() if want_c0 else None
@@ -1536,10 +1566,10 @@ class RNNStackFn(torch.autograd.Function):
             L.call('gpe_reduce_inner', dgx[0], T * GHp, GHp, T, Bn, GH, dGs, GH, 0)
             if ctx.needs_input_grad[0]:
                 d_x = torch.empty(Bn, In, device=dev, dtype=F32)
-                linear_raw(_rows2d(dGs), pack_weight(params[0], transpose=True), None, Bn, In, GH, _rows2d(d_x))
+                linear_raw(_rows2d(dGs), pack_weight(layers[0].w_ih, transpose=True), None, Bn, In, GH, _rows2d(d_x))
         elif ctx.needs_input_grad[0]:
             d_x = torch.empty(Bn, T, In, device=dev, dtype=F32)
-            linear_raw(gx0, pack_weight(params[0], transpose=True), None, Bn * T, In, GH, (d_x, In, 0, 0))
+            linear_raw(gx0, pack_weight(layers[0].w_ih, transpose=True), None, Bn * T, In, GH, (d_x, In, 0, 0))
         if want_h0:
             for l in range(Lr):
                 # dh_0 = dG_{l,0} . W_hh (+ the z-gated direct path of a GRU)
@@ -1550,8 +1580,7 @@ class RNNStackFn(torch.autograd.Function):
                     L.call('gpe_add', d_h0[l], carry[0][l], d_h0[l], Bn * Hh)
         # ---- the weight gradients: leaves of the backward pass (on the side stream when every one of them lands in the arena) ----
         with side_grads(list(params), [dgx, dgh, hs, x, dGs]):
-            for l in range(Lr):
-                w_ih, w_hh, b_ih, b_hh = params[4 * l: 4 * l + 4]
+            for l, (w_ih, w_hh, b_ih, b_hh) in enumerate(layers):
                 gx_rows, gh_rows = _rows3d(dgx[l][:, :, :GH]), _rows3d(dgh[l][:, :, :GH])
                 d_whh, d_bhh = _gbuf(w_hh), _gbuf(b_hh)
                 redgemm_raw(gh_rows, _rows3d(hs[l][:, :T, :Hh]), Bn * T, GH, Hh, out=(d_whh, d_bhh))
@@ -1562,9 +1591,9 @@ class RNNStackFn(torch.autograd.Function):
                     Kin = In if l == 0 else Hh
                     src = _rows3d(x) if l == 0 else _rows3d(hs[l - 1][:, 1:, :Hh])
                     redgemm_raw(gx_rows, src, Bn * T, GH, Kin, out=(d_wih, d_bih))
-                grads[4 * l: 4 * l + 4] = [_gret(w_ih, d_wih), _gret(w_hh, d_whh), _gret(b_ih, d_bih),
-                                           _gret(b_hh, d_bhh)]
-        return (d_x, d_h0, d_c0, None, None, None, None, None, *grads)
+                filed[l, 'w_ih'], filed[l, 'w_hh'] = _gret(w_ih, d_wih), _gret(w_hh, d_whh)
+                filed[l, 'b_ih'], filed[l, 'b_hh'] = _gret(b_ih, d_bih), _gret(b_hh, d_bhh)
+        return rnn_grads(Lr, filed, d_x, d_h0, d_c0)
 
 
 class DropoutMulFn(torch.autograd.Function):
@@ -1621,9 +1650,10 @@ def rnn_stack(x, h0, c0, T, n_layers, kind, params, want_state=False, dropout=0.
         out = RNNStackFn.apply(x, h0, c0, T, n_layers, kind, want_state, h0_ok, *params)
         return out if kind == 'lstm' else (out[0], out[1], None)
     lstm = kind == 'lstm'
+    layers = rnn_layers(params, n_layers)
     inp, hs, cs = x, [], []
     for l in range(n_layers):
-        out = RNNStackFn.apply(inp, h0[l:l + 1], c0[l:l + 1] if lstm else None, T, 1, kind, want_state, h0_ok, *params[4 * l:4 * l + 4])
+        out = RNNStackFn.apply(inp, h0[l:l + 1], c0[l:l + 1] if lstm else None, T, 1, kind, want_state, h0_ok, *layers[l])
         top = out[0]
         if want_state:
             hs.append(out[1])

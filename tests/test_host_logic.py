@@ -71,39 +71,65 @@ def test_every_fixture_config_constructs_with_reference_layout(tag, golden_dir):
 def test_pack_plan_job_table():
     """the 64-byte job records gpe_pack_multi reads (include/gpe_hip.h): gpe_pack_job_blocks(kind, ..) 256-thread blocks per job (ABI 6:
     64 x 64 tiles for the row-major sources, 1024 outputs per block otherwise), jobs sorted by first_block, every output buffer sized
-    to its job; one amax word per MATRIX, shared by its two plane packs"""
+    to its job; one amax word per MATRIX, shared by its two plane packs; the table every arithmetic but f16x3 launches (table_noh3) is
+    the full one without the plane jobs.  For the shipped LSTM decoders and for GRU decoders (three gates, no transposed planes)."""
     import numpy as np
     ops = gpe_amd.ops
     dc = configs.data_config()
-    cfg = configs.lstm_model_config(k_neighbors=5)
-    model = nets.GarmentFullPattern3D(dc, dict(cfg), dict(cfg['loss']))
-    plan = ops.PackPlan()
-    for m in model._pack_modules():
-        m.register_packs(plan)
-    model._register_own_packs(plan)
-    plan._build()
-    tab = plan.table.numpy().view(ops._JOB)
-    assert tab.dtype.itemsize == 64 and len(tab) == len(plan.specs)
-    blk = 0
-    for job, out in zip(tab, plan.outs):
-        assert int(job['first_block']) == blk
-        assert int(job['total']) == out.numel() and int(job['out']) == out.data_ptr()
-        if int(job['kind']) < 5:
-            assert int(job['total']) % 4 == 0                 # whole float4 quads
-        kind, total, npad, K = int(job['kind']), int(job['total']), int(job['Npad']), int(job['K'])
-        nb = gpe_amd._lib.query('gpe_pack_job_blocks', kind, total, npad, K)
-        if kind in (0, 2):
-            assert nb == -(-npad // 64) * -(-(total // npad) // 64)
-        elif kind == 8:
-            assert nb == -(-npad // 64) * -(-(-(-K // 32) * 32) // 64)
+    for gates, override in ((4, {}), (3, dict(panel_decoder='GRUDecoderModule', pattern_decoder='GRUDecoderModule'))):
+        cfg = configs.lstm_model_config(k_neighbors=5, **override)
+        model = nets.GarmentFullPattern3D(dc, dict(cfg), dict(cfg['loss']))
+        plan = ops.PackPlan()
+        for m in model._pack_modules():
+            m.register_packs(plan)
+        model._register_own_packs(plan)
+        plan._build()
+        tab = plan.table.numpy().view(ops._JOB)
+        assert tab.dtype.itemsize == 64 and len(tab) == len(plan.specs)
+        blk = 0
+        for job, out in zip(tab, plan.outs):
+            assert int(job['first_block']) == blk
+            assert int(job['total']) == out.numel() and int(job['out']) == out.data_ptr()
+            if int(job['kind']) < 5:
+                assert int(job['total']) % 4 == 0                 # whole float4 quads
+            kind, total, npad, K = int(job['kind']), int(job['total']), int(job['Npad']), int(job['K'])
+            nb = gpe_amd._lib.query('gpe_pack_job_blocks', kind, total, npad, K)
+            if kind in (0, 2):
+                assert nb == -(-npad // 64) * -(-(total // npad) // 64)
+            elif kind == 8:
+                assert nb == -(-npad // 64) * -(-(-(-K // 32) * 32) // 64)
+            else:
+                assert nb == (total + 1023) // 1024
+            blk += nb
+        assert plan.blocks == blk
+        pre = plan.pre_table.numpy().view(ops._JOB)
+        assert len(set(int(j['w']) for j in pre)) == len(pre) == plan.words.numel()          # one amax job per matrix
+        planes = [j for j in tab if int(j['kind']) in (8, 10)]
+        assert all(int(j['w2']) in set(int(q['out']) for q in pre) for j in planes)
+        if gates == 4:
+            assert len(planes) > len(pre)
         else:
-            assert nb == (total + 1023) // 1024
-        blk += nb
-    assert plan.blocks == blk
-    pre = plan.pre_table.numpy().view(ops._JOB)
-    assert len(set(int(j['w']) for j in pre)) == len(pre) == plan.words.numel()          # one amax job per matrix
-    planes = [j for j in tab if int(j['kind']) in (8, 10)]
-    assert len(planes) > len(pre) and all(int(j['w2']) in set(int(q['out']) for q in pre) for j in planes)
+            assert len(planes) == len(pre) and not any(int(j['kind']) == 10 for j in tab)
+        # the word of a plane job is the one whose address the job carries, and the one its matrix's amax job fills
+        assert len(plan.word_of) == len(planes)
+        for sp, job in zip(plan.specs, tab):
+            assert int(job['kind']) == sp.kind and int(job['w']) == sp.p.data_ptr()
+            if sp.kind in (8, 10):
+                word = plan.word_of[(sp.p.data_ptr(), sp.kind)]
+                assert word.numel() == 1 and word.data_ptr() == int(job['w2'])
+                assert [int(q['w']) for q in pre if int(q['out']) == word.data_ptr()] == [sp.p.data_ptr()]
+                at = (word.data_ptr() - plan.words.data_ptr()) // 4
+                assert 0 <= at < plan.words.numel() and plan.words[at:at + 1].data_ptr() == word.data_ptr()
+        # table_noh3: the rows of the full table that are no plane jobs, field by field, first_block running over them alone
+        keep = [j for j in tab if int(j['kind']) not in (8, 10)]
+        noh3 = plan.table_noh3.numpy().view(ops._JOB)
+        assert plan.n_noh3 == len(noh3) == len(keep) < len(tab)
+        blk = 0
+        for job, full in zip(noh3, keep):
+            for field in ops._JOB.names:
+                assert int(job[field]) == (blk if field == 'first_block' else int(full[field])), field
+            blk += gpe_amd._lib.query('gpe_pack_job_blocks', int(job['kind']), int(job['total']), int(job['Npad']), int(job['K']))
+        assert plan.blocks_noh3 == blk < plan.blocks
 
 
 def test_stitch_model_layout(golden_dir):

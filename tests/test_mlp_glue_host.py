@@ -2,25 +2,15 @@
 by (block, field), the saved tensors by name, and the argument order of the keyword wrappers of gpe_edge_mlp_fwd / gpe_edge_redgemm /
 gpe_edge_mlp_bwd against the declarations of include/gpe_hip.h.  No tensor reaches a kernel and no library is loaded."""
 import inspect
-import re
 
 import pytest
 import torch
 
-from gpe_amd import _lib, net_blocks, ops
+from gpe_amd import net_blocks, ops
+from glue_host import Named, check, declared, missing_each, named, recorded  # noqa: F401  (recorded: a fixture)
 
 CHANNELS = {2: [6, 8, 5], 3: [6, 8, 12, 5], 4: [6, 8, 12, 16, 5]}
 FUNCTIONS = [(ops.EdgeConvFn, 11), (ops.DenseMLPFn, 5)]
-
-
-class Named:
-    """a stand-in for one argument: equal to nothing but itself"""
-
-    def __init__(self, name):
-        self.name = name
-
-    def __repr__(self):
-        return '<%s>' % self.name
 
 
 # ---- the layout ------------------------------------------------------------------------------------------------------------------
@@ -111,39 +101,6 @@ def test_saved_groups_round_trip_in_the_flat_order(nb, tail_len):
 
 
 # ---- the wrappers ----------------------------------------------------------------------------------------------------------------
-def declared(entry):
-    """the parameter names of `entry` as include/gpe_hip.h declares them"""
-    src = re.sub(r'/\*.*?\*/', ' ', open(_lib.HEADER_PATH).read(), flags=re.S)
-    m = re.search(r'\bint\s+%s\s*\(([^)]*)\)\s*;' % entry, src)
-    names = [re.search(r'(\w+)\s*$', p).group(1) for p in m.group(1).split(',')]
-    assert len(names) == len(_lib.parse_header()[entry][1]) and names[-1] == 'stream'
-    return names
-
-
-@pytest.fixture
-def recorded(monkeypatch):
-    calls = []
-    monkeypatch.setattr(ops.L, 'call', lambda name, *args: calls.append((name, args)))
-    return calls
-
-
-def check(recorded, entry, expect):
-    """the one call recorded is `entry`, and every position carries what `expect` has under the declaration's name for it"""
-    names = declared(entry)[:-1]                               # (L.call appends the stream)
-    assert len(recorded) == 1 and recorded[0][0] == entry
-    args = recorded[0][1]
-    assert len(args) == len(names)
-    assert set(expect) == set(names)
-    for pos, (name, arg) in enumerate(zip(names, args)):
-        want = expect[name]
-        assert (arg is want) if isinstance(want, Named) or want is None else (type(arg) is int and arg == want), (pos, name, arg)
-    del recorded[:]
-
-
-def named(*names):
-    return {n: Named(n) for n in names}
-
-
 def source(s, is_gathered, rows, pitch):
     """(the EdgeSrc of a variant, what the declaration's source parameters must then receive)"""
     if is_gathered:
@@ -153,16 +110,6 @@ def source(s, is_gathered, rows, pitch):
 
 LAZY = ('lz_g', 'lz_ldg', 'lz_amx', 'lz_amn', 'lz_ldagg', 'lz_coef')
 NO_LAZY = dict(zip(LAZY, (None, 0, None, None, 0, None)))
-
-
-def missing_each(wrapper, kw, recorded, optional=()):
-    for name in kw:
-        if name not in optional:
-            with pytest.raises(TypeError):
-                wrapper(**{k: v for k, v in kw.items() if k != name})
-    with pytest.raises(TypeError):
-        wrapper(*kw.values())                                  # (keywords only: a position cannot be mistaken for another)
-    assert recorded == []
 
 
 @pytest.mark.parametrize('with_agg', [True, False])
