@@ -329,7 +329,8 @@ extern "C" int gpe_stitch_renumber(const int64_t* stitches, const int64_t* nums,
 }
 
 // per-edge ground truth [npanels][L][D] follows its panel's new loop origin (composed_loss.py:705-725): rows l < n of a panel
-// with n >= 3 edges and lead != 0 become feat[(l + lead) mod n]; padding rows and every other panel are copied.
+// with n >= 3 edges (n = min(num_edges, L)) and 0 < lead < n become feat[(l + lead) mod n]; padding rows and every other panel are
+// copied.  A lead at or past n (num_edges > L with lead >= L) leaves the reference's rows where they are, and so does this.
 __global__ void gpe_panel_shift_kernel(const float* __restrict__ feat, int D, const int32_t* __restrict__ lead,
                                        const int32_t* __restrict__ num_edges, long npanels, int L, float* __restrict__ out)
 {
@@ -343,7 +344,7 @@ __global__ void gpe_panel_shift_kernel(const float* __restrict__ feat, int D, co
         int n = num_edges[pn];
         n = n > L ? L : n;
         int src = l;
-        if (n >= 3 && ld != 0 && l < n) { src = l + ld; if (src >= n) src -= n; }
+        if (n >= 3 && ld > 0 && ld < n && l < n) { src = l + ld; if (src >= n) src -= n; }   // ld outside (0, n): no shift, in bounds
         out[e] = feat[(pn * L + src) * D + d];
     }
 }

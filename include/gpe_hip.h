@@ -476,7 +476,9 @@ int gpe_ragged_max_bwd(const float* gy, int ldgy, const int64_t* off, const int6
  * flags: 1 shape | 2 loop | 4 rotation | 8 translation.  pad0/pad1: the standardised padding vector's first two entries.
  * fwd: part [B][4] fp64 and loop_sums [B*P][2] are workspaces (loop_sums is re-used by bwd);
  *      out5 = {total, shape, loop, rotation, translation} (each term a mean, total = shape + loop_w*loop + rot + tr).
- * bwd: gradients of `total`, times the device scalar *gscale (NULL = 1), dense: g_ol [B,P,L,4], g_rot [B,P,R], g_tr [B,P,T]. */
+ * bwd: gradients of `total`, times the device scalar *gscale (NULL = 1), dense: g_ol [B,P,L,4], g_rot [B,P,R], g_tr [B,P,T];
+ *      g_rot / g_tr may be NULL (not written).  num_edges > L acts as L, a negative count as 0 (a panel under 3 edges has no
+ *      loop term, value or gradient; the loop gradient reaches columns 0-1 of the first n edges only). */
 int gpe_pattern_loss_fwd(const float* ol, long ol_sb, long ol_sp, long ol_sl, const float* rot, long rot_s,
                          const float* tr, long tr_s, const float* gt_ol, const float* gt_rot, const float* gt_tr,
                          const int32_t* num_edges, int B, int P, int L, int R, int T, int flags, float pad0, float pad1,
@@ -506,7 +508,14 @@ int gpe_order_match(const float* pred_feat, const float* gt_feat, int B, int P, 
  * fwd: part [B][6] fp64 workspace (re-used by bwd); out5 = {total, similarity, negative, supervised, free} with
  *      total = (similarity + negative) + sup_w * supervised + free.  A pattern without stitches gives NaN (the reference
  *      divides by its zero stitch count as well).
- * bwd: gradient of `total` times the device scalar *gscale (NULL = 1), dense: g_tags [B,P,L,D], g_mask [B,P,L]. */
+ * bwd: gradient of `total` times the device scalar *gscale (NULL = 1), dense: g_tags [B,P,L,D], g_mask [B,P,L]; g_tags is
+ *      required under bits 1 | 8 and g_mask under bit 4, either may be NULL otherwise.
+ * Conventions: nums[b] outside [0, S] is clamped; entries past nums[b] are never read; an edge id outside [0, P*L) is clamped
+ * (the reference would raise or wrap).  A pair of tags at a gap of exactly 0 (margin - d == 0) is inactive: the value is the
+ * reference's, the gradient is 0, where the reference's autograd sends that pair's full gradient (HardNet: Python's max(t, 0)
+ * returns t) or half of it (all pairs: torch.max(a, zeros) splits at equality).  Tied HardNet minima share the gradient equally,
+ * as torch's min() does.  A pattern with nums[b] = 0 makes the similarity and the total NaN, as in the reference; every
+ * gradient stays finite and that pattern's gradients are 0 apart from the supervised and free terms. */
 int gpe_stitch_loss_fwd(const float* tags, long t_sb, long t_sp, long t_sl, int D, const float* logit, long m_sb, long m_sp,
                         long m_sl, const int64_t* stitches, const int64_t* nums, int S, const float* gt_mask,
                         const float* gt_tags, int B, int P, int L, int flags, float margin, float sup_w, double* part,
@@ -517,11 +526,14 @@ int gpe_stitch_loss_bwd(const float* tags, long t_sb, long t_sp, long t_sl, int 
                         const float* gscale, float* g_tags, float* g_mask, void* stream);
 /* stitched-edge re-numbering of the ground truth (composed_loss.py:592-620 after the panel-order permutation `perm` int64
  * [B][P], then :727-755 for the panel-origin shift `lead` int32 [B*P] with `num_edges` int32 [B*P] of the permuted panels);
- * either step is skipped when its pointer is NULL.  out int64 [B][2][S]; entries past nums[b] are copied. */
+ * either step is skipped when its pointer is NULL.  out int64 [B][2][S]; entries past nums[b] (clamped to [0, S]) are copied;
+ * there is no limit on S.  A panel moves to the LAST slot r with perm[b][r] == panel; a panel no slot names gets slot -1, and
+ * the origin step then floor-divides the negative id (a negative flat panel number reads lead[0] / num_edges[0]). */
 int gpe_stitch_renumber(const int64_t* stitches, const int64_t* nums, int B, int S, int P, int L, const int64_t* perm,
                         const int32_t* lead, const int32_t* num_edges, int64_t* out, void* stream);
 /* per-edge ground truth [npanels][L][D] follows its panel's new loop origin (composed_loss.py:705-725 `_per_panel_shift`):
- * rows l < n of a panel with n >= 3 edges and lead != 0 become feat[(l + lead) mod n], everything else is copied. */
+ * rows l < n of a panel with n = min(num_edges, L) >= 3 edges and 0 < lead < n become feat[(l + lead) mod n], everything else
+ * (padding rows, shorter panels, a lead outside (0, n)) is copied. */
 int gpe_panel_shift(const float* feat, int D, const int32_t* lead, const int32_t* num_edges, long npanels, int L, float* out,
                     void* stream);
 
