@@ -379,13 +379,19 @@ __global__ __launch_bounds__(768) void gpe_gemm_x6_tn_kernel(GxRedParams p)
 // =====================================================================================================================
 // host side (called by gpe_linear / gpe_redgemm when the arithmetic mode allows it)
 // =====================================================================================================================
+// the NT kernel's menu (host only; gpe_linear's ladder asks it too, gpe_rowgemm.hip rg_linear_path)
+bool gpe_gemm_x6_linear_ok(const GpeRows& a, const float* wp, long M, int N, int K)
+{
+    // worth it from ~0.25 GFLOP with at least one full wave of blocks' worth of rows; A rows 16-byte loadable up to round4(K)
+    if (M < 2048 || N < 48 || K < 32 || 2.0 * M * N * K < 2.5e8) return false;
+    return gpe_rd_rows_x6(a, K) && !(((uintptr_t)wp) & 15);
+}
+
 // 1 = launched, 0 = not on this kernel's menu
 int gpe_gemm_x6_linear(const GpeRows& a, const float* wp, int Npad, int Kq, const float* bias, const GpeRows& addend, float* y,
                        long y_so, long y_si, int y_inner, long M, int N, int K, int act, hipStream_t s)
 {
-    // worth it from ~0.25 GFLOP with at least one full wave of blocks' worth of rows; A rows 16-byte loadable up to round4(K)
-    if (M < 2048 || N < 48 || K < 32 || 2.0 * M * N * K < 2.5e8) return 0;
-    if (!gpe_rd_rows_x6(a, K) || (((uintptr_t)wp) & 15)) return 0;
+    if (!gpe_gemm_x6_linear_ok(a, wp, M, N, K)) return 0;
     GxLinParams p = {};
     p.a = a; p.wp = wp; p.Npad = Npad; p.Kq = Kq; p.bias = bias; p.addend = addend;
     p.y = y; p.y_so = y_so; p.y_si = y_si; p.y_inner = y_inner; p.act = act; p.M = M; p.N = N; p.K = K;

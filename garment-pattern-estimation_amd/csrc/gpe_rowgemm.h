@@ -78,8 +78,11 @@ int gpe_edge_pseudo_fold(const RgParams& p, const GpeFold& fd, hipStream_t s);  
 
 // the two kernels gpe_linear (gpe_rowgemm.hip) hands a shape to before its own:
 // single-stage kernel for latency-bound shapes (gpe_smallgemm.hip)
-int gpe_smallgemm_linear(const RgParams& r, hipStream_t s);
-// f16x3 mode, big dense products on the bf16 pipe (gpe_gemm_x6.hip): 1 launched, 0 not on its menu, < 0 error
+// (NT = 1 or 4, its column block in 16-column tiles, chosen by gpe_smallgemm_linear_nt)
+int gpe_smallgemm_linear_nt(long M, int N);
+int gpe_smallgemm_linear(const RgParams& r, int NT, hipStream_t s);
+// f16x3 mode, big dense products on the bf16 pipe (gpe_gemm_x6.hip): 1 launched, 0 not on its menu (gpe_gemm_x6_linear_ok), < 0 error
+bool gpe_gemm_x6_linear_ok(const GpeRows& a, const float* wp, long M, int N, int K);
 int gpe_gemm_x6_linear(const GpeRows& a, const float* wp, int Npad, int Kq, const float* bias, const GpeRows& addend, float* y,
                        long y_so, long y_si, int y_inner, long M, int N, int K, int act, hipStream_t s);
 

@@ -285,41 +285,29 @@ static bool rg_rows_aligned16(const float* base, long so, long si, int inner)
     return !(((uintptr_t)base) & 15) && !(so & 3) && (inner <= 0 || !(si & 3));
 }
 
-extern "C" int gpe_linear(const float* a, long a_so, long a_si, int a_inner, const float* wp, const float* bias,
-                          const float* addend, long ad_so, long ad_si, int ad_inner, float* y, long y_so,
-                          long y_si, int y_inner, int M, int N, int K, int act, void* stream)
+// gpe_linear's ladder, host only: which kernel a call runs.  Codes (include/gpe_hip.h gpe_linear_path): rung * 100 + NT
+enum { LIN_NOTHING = 0, LIN_X6 = 100, LIN_SMALLK = 200, LIN_SINGLE = 300, LIN_STREAM = 400 };
+static int rg_linear_path(const float* a, long a_so, long a_si, int a_inner, const float* wp, const float* addend, long ad_so,
+                          long ad_si, int ad_inner, const float* y, long y_so, long y_si, int y_inner, int M, int N, int K, int act)
 {
     if (!a || !wp || !y || M < 0 || N <= 0 || K <= 0 || (act != 0 && act != 1)) return GPE_EINVAL;
-    if (M == 0) return GPE_OK;
-    RgParams p = {};
-    p.M = M; p.N = N; p.K = K; p.R = RG_BM; p.num_tiles = gpe_cdiv(M, RG_BM);
-    p.a = GpeRows{a, a_so, a_si, a_inner};
-    p.wp = wp; p.Npad = gpe_round_up(N, 16); p.bias = bias;
-    p.addend = GpeRows{addend, ad_so, ad_si, ad_inner};
-    p.y = y; p.y_so = y_so; p.y_si = y_si; p.y_inner = y_inner; p.act = act;
+    if (M == 0) return LIN_NOTHING;
+    const int num_tiles = gpe_cdiv(M, RG_BM);
     // f16x3 mode: the big dense products (the layer-2 [P|Q] projection and its input gradient, 65536 rows x 400 x 150) on the bf16
     // pipe, three-term splits, six MFMAs per product (gpe_gemm_x6.hip); gpe_debug_set(16384) keeps the exact kernels (A/B runs)
-    if (gpe_math_get() == 4 && !(gpe_debug_get() & 16384)) {
-        const int rc = gpe_gemm_x6_linear(p.a, wp, p.Npad, (int)(gpe_packed_size(N, K) / p.Npad / 4), bias, p.addend, y, y_so, y_si, y_inner, M, N, K,
-                                          act, (hipStream_t)stream);
-        if (rc != 0) return rc < 0 ? rc : GPE_OK;
-    }
+    if (gpe_math_get() == 4 && !(gpe_debug_get() & 16384) && gpe_gemm_x6_linear_ok(GpeRows{a, a_so, a_si, a_inner}, wp, M, N, K))
+        return LIN_X6;
     if (K <= RG_SMALLK && !(N & 3) && M >= 4096 && rg_rows_aligned16(y, y_so, y_si, y_inner) &&
-        (!addend || rg_rows_aligned16(addend, ad_so, ad_si, ad_inner))) {
-        long gx = gpe_cdiv(M, 4 * 8);                      // >= 8 rows per wave
-        if (gx > 4096) gx = 4096;
-        hipLaunchKernelGGL(gpe_linear_smallk_kernel, dim3((unsigned)gx, gpe_cdiv(N, 256)), dim3(256), 0, (hipStream_t)stream, p);
-        GPE_CHECK_LAUNCH();
-        return GPE_OK;
-    }
+        (!addend || rg_rows_aligned16(addend, ad_so, ad_si, ad_inner)))
+        return LIN_SMALLK;
     // latency-bound regime (the streaming kernel could not even put one workgroup on half the CUs): single-stage kernel
-    if ((long)p.num_tiles * gpe_cdiv(N, 208) < 128) return gpe_smallgemm_linear(p, (hipStream_t)stream);
+    if ((long)num_tiles * gpe_cdiv(N, 208) < 128) return LIN_SINGLE + gpe_smallgemm_linear_nt(M, N);
     // widest column block that still gives the chip >= 256 workgroups, else the narrowest
     int NT = 4;
     const int opts[5] = {16, 13, 10, 7, 4};
     for (int i = 0; i < 5; ++i) {
         const int nblk = gpe_cdiv(N, 16 * opts[i]);
-        if ((long)nblk * p.num_tiles >= 256 || opts[i] == 4) { NT = opts[i]; break; }
+        if ((long)nblk * num_tiles >= 256 || opts[i] == 4) { NT = opts[i]; break; }
     }
     // never use a block much wider than N
     const int single = rg_pick_nt_single(N);
@@ -331,12 +319,54 @@ extern "C" int gpe_linear(const float* a, long a_so, long a_si, int a_inner, con
         const int wide[3] = {16, 13, 10};
         for (int i = 0; i < 3; ++i) {
             const int pad = gpe_cdiv(N, 16 * wide[i]) * 16 * wide[i];
-            if (pad < best_pad && (long)gpe_cdiv(N, 16 * wide[i]) * p.num_tiles >= 256) { best = wide[i]; best_pad = pad; }
+            if (pad < best_pad && (long)gpe_cdiv(N, 16 * wide[i]) * num_tiles >= 256) { best = wide[i]; best_pad = pad; }
         }
         NT = best;
     }
-    dim3 grid(p.num_tiles, gpe_cdiv(N, 16 * NT));
-    return rg_dispatch_nt<A_DENSE, E_LINEAR>(NT, p, grid, (hipStream_t)stream);
+    return LIN_STREAM + NT;
+}
+
+extern "C" int gpe_linear_path(const float* a, long a_so, long a_si, int a_inner, const float* wp, const float* bias,
+                               const float* addend, long ad_so, long ad_si, int ad_inner, const float* y, long y_so,
+                               long y_si, int y_inner, int M, int N, int K, int act)
+{
+    (void)bias;                                            // no rung depends on the bias
+    return rg_linear_path(a, a_so, a_si, a_inner, wp, addend, ad_so, ad_si, ad_inner, y, y_so, y_si, y_inner, M, N, K, act);
+}
+
+extern "C" int gpe_linear(const float* a, long a_so, long a_si, int a_inner, const float* wp, const float* bias,
+                          const float* addend, long ad_so, long ad_si, int ad_inner, float* y, long y_so,
+                          long y_si, int y_inner, int M, int N, int K, int act, void* stream)
+{
+    const int path = rg_linear_path(a, a_so, a_si, a_inner, wp, addend, ad_so, ad_si, ad_inner, y, y_so, y_si, y_inner, M, N, K, act);
+    if (path <= 0) return path;                            // refused, or M == 0: nothing to do
+    RgParams p = {};
+    p.M = M; p.N = N; p.K = K; p.R = RG_BM; p.num_tiles = gpe_cdiv(M, RG_BM);
+    p.a = GpeRows{a, a_so, a_si, a_inner};
+    p.wp = wp; p.Npad = gpe_round_up(N, 16); p.bias = bias;
+    p.addend = GpeRows{addend, ad_so, ad_si, ad_inner};
+    p.y = y; p.y_so = y_so; p.y_si = y_si; p.y_inner = y_inner; p.act = act;
+    const int NT = path % 100;
+    switch (path - NT) {
+        case LIN_X6: {
+            const int rc = gpe_gemm_x6_linear(p.a, wp, p.Npad, (int)(gpe_packed_size(N, K) / p.Npad / 4), bias, p.addend, y, y_so, y_si, y_inner, M, N, K,
+                                              act, (hipStream_t)stream);
+            return rc < 0 ? rc : rc == 1 ? GPE_OK : GPE_EINVAL;        // (0 cannot happen: the path asked the same menu)
+        }
+        case LIN_SMALLK: {
+            long gx = gpe_cdiv(M, 4 * 8);                  // >= 8 rows per wave
+            if (gx > 4096) gx = 4096;
+            hipLaunchKernelGGL(gpe_linear_smallk_kernel, dim3((unsigned)gx, gpe_cdiv(N, 256)), dim3(256), 0, (hipStream_t)stream, p);
+            GPE_CHECK_LAUNCH();
+            return GPE_OK;
+        }
+        case LIN_SINGLE: return gpe_smallgemm_linear(p, NT, (hipStream_t)stream);
+        case LIN_STREAM: {
+            dim3 grid(p.num_tiles, gpe_cdiv(N, 16 * NT));
+            return rg_dispatch_nt<A_DENSE, E_LINEAR>(NT, p, grid, (hipStream_t)stream);
+        }
+    }
+    return GPE_EINVAL;
 }
 
 // ---- lazy dz3 (round 4): the 1.3 GB in-place pass of gpe_edge_dz3 folded into its two consumers -----------------------------------

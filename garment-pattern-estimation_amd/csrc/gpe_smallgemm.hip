@@ -274,8 +274,16 @@ static int sg_launch(const SgParams& p, dim3 grid, hipStream_t s)
     return GPE_OK;
 }
 
-// used by gpe_linear (gpe_rowgemm.hip) when the streaming kernel's grid would be latency-bound
-int gpe_smallgemm_linear(const RgParams& r, hipStream_t s)
+// the column block of the single-stage Linear, in 16-column tiles (host only; gpe_linear's ladder asks it too, gpe_rowgemm.hip
+// rg_linear_path): 64-column blocks unless that leaves most CUs idle, then 16-column blocks
+int gpe_smallgemm_linear_nt(long M, int N)
+{
+    const int tiles = gpe_cdiv(M, RG_BM);
+    return ((long)tiles * gpe_cdiv(N, 64) >= 128 && N > 16) ? 4 : 1;
+}
+
+// used by gpe_linear (gpe_rowgemm.hip) when the streaming kernel's grid would be latency-bound; NT = gpe_smallgemm_linear_nt
+int gpe_smallgemm_linear(const RgParams& r, int NT, hipStream_t s)
 {
     SgParams p = {};
     p.M = (int)r.M; p.N = r.N; p.K = r.K;
@@ -283,12 +291,9 @@ int gpe_smallgemm_linear(const RgParams& r, hipStream_t s)
     p.y = r.y; p.y_so = r.y_so; p.y_si = r.y_si; p.y_inner = r.y_inner; p.act = r.act;
     p.a_padded = !(p.K & 3);
     const int tiles = gpe_cdiv(p.M, RG_BM);
-    // 64-column blocks unless that leaves most CUs idle, then 16-column blocks
-    if ((long)tiles * gpe_cdiv(p.N, 64) >= 128 || p.N <= 16) {
-        if (p.N <= 16) return sg_launch<1, EPI_LINEAR>(p, dim3(tiles, gpe_cdiv(p.N, 16)), s);
-        return sg_launch<4, EPI_LINEAR>(p, dim3(tiles, gpe_cdiv(p.N, 64)), s);
-    }
-    return sg_launch<1, EPI_LINEAR>(p, dim3(tiles, gpe_cdiv(p.N, 16)), s);
+    if (NT == 4) return sg_launch<4, EPI_LINEAR>(p, dim3(tiles, gpe_cdiv(p.N, 64)), s);
+    if (NT == 1) return sg_launch<1, EPI_LINEAR>(p, dim3(tiles, gpe_cdiv(p.N, 16)), s);
+    return GPE_EINVAL;
 }
 
 extern "C" int gpe_lstm_step_fwd(const float* h_prev, long hp_stride, const float* whh_gates_packed,

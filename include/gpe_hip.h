@@ -164,6 +164,24 @@ int gpe_linear(const float* a, long a_so, long a_si, int a_inner,
                const float* addend, long ad_so, long ad_si, int ad_inner,
                float* y, long y_so, long y_si, int y_inner,
                int M, int N, int K, int act, void* stream);
+/* Which kernel a gpe_linear call with these arguments runs (nn/net_blocks.py:45,158,373-376,397: the same nn.Linear).  Added without
+ * a version bump (gpe_abi_version() stays 7): one host-only query, nothing else changes.  HOST ONLY: gpe_linear's arguments without the
+ * stream; the pointers are looked at for NULL and for their 16-byte alignment and never followed (bias not at all), no HIP call is
+ * made and nothing is allocated; the arithmetic mode (gpe_math_get) and the debug word (gpe_debug_get) are read as gpe_linear reads
+ * them, and gpe_linear dispatches through the same function.  Returns -22 where gpe_linear refuses the arguments, 0 for M == 0
+ * (nothing is launched), else rung * 100 + NT:
+ *   100       bf16-pipe kernel, three-term splits, 128 x 128 blocks (f16x3 mode with debug bit 16384 clear, M >= 2048, N >= 48,
+ *             K >= 32, 2 M N K >= 2.5e8, A rows and wp 16-byte loadable up to round4(K))
+ *   200       K <= 8 streaming-store kernel (N % 4 == 0, M >= 4096, y and addend rows 16-byte aligned)
+ *   301, 304  single-stage kernel with 16- / 64-column blocks (ceil(M / 64) * ceil(N / 208) < 128; 64-column blocks when
+ *             ceil(M / 64) * ceil(N / 64) >= 128 and N > 16)
+ *   404, 407, 410, 413, 416   streaming kernel with 16 NT-column blocks (everything else)
+ * The thresholds are the library's to change; the codes are not. */
+int gpe_linear_path(const float* a, long a_so, long a_si, int a_inner,
+                    const float* wp, const float* bias,
+                    const float* addend, long ad_so, long ad_si, int ad_inner,
+                    const float* y, long y_so, long y_si, int y_inner,
+                    int M, int N, int K, int act);
 
 /* reduce-GEMM: G[m][n] (+)= sum_r U[r][m]*V[r][n]  (weight gradients, nn.Linear backward), colsum[m] = sum_r U[r][m].
  * part: workspace of gpe_redgemm_ws(Mg,Ng) floats.  accumulate != 0 adds into G / colsum. */

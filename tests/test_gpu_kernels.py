@@ -317,6 +317,13 @@ def test_knn_reverse(gpe):
 
 
 # --------------------------------------------------------------------------------------------------
+# The rung of gpe_linear's ladder each shape reaches, as gpe_linear_path answers for dense rows in either arithmetic mode — the forward
+# product M x N x K / the input gradient's M x K x N:
+#   (64, 200, 200) 301 / 301     (100, 8, 250) 301 / 301      (736, 1000, 250) 304 / 301    (32, 250, 1000) 301 / 301
+#   (33, 7, 3) 301 / 301         (1000, 400, 150) 301 / 301   (130, 23, 153) 301 / 301      (65, 300, 520) 301 / 301
+#   (5000, 400, 3) 200 / 301     (4100, 152, 6) 200 / 301     (70000, 400, 3) 200 / 404
+# (301 / 304 single-stage with 16- / 64-column blocks, 200 the K <= 8 kernel, 404 the streaming kernel with 64-column blocks.)  The
+# ladder itself is walked rung by rung, edge by edge, in tests/test_gpu_linear.py.
 LIN_CASES = [(64, 200, 200), (100, 8, 250), (736, 1000, 250), (32, 250, 1000), (33, 7, 3), (1000, 400, 150),
              (130, 23, 153), (65, 300, 520),
              # K <= 8 streaming-store kernel / deep reduce-GEMM with an unaligned V (the layer-1 [P|Q] projection shapes)
