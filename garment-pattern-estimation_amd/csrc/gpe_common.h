@@ -12,6 +12,8 @@
 #include "../../include/gpe_hip_fit.h"
 // ... and the evaluation pass (the accumulate and pooling launches), bound through _lib.EVAL_HEADERS
 #include "../../include/gpe_hip_eval.h"
+// ... and the 3D placement of decoded panels, bound through _lib.PLACE_HEADERS
+#include "../../include/gpe_hip_place.h"
 
 #define GPE_OK 0
 #define GPE_EINVAL (-22)

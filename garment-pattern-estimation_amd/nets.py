@@ -80,6 +80,19 @@ class BaseModule(nn.Module):
         return DecodedPatterns(ops.pattern_decode(preds, data_config['standardize'],
                                                   bool(data_config.get('explicit_stitch_tags', False)), stitches=stitches))
 
+    def predict_garment(self, positions_batch, data_config, stitch_model, stitch_data_stats, route='auto', **kw):
+        """Both prediction stages on the device (the reference's evaluation_scripts/on_test_set.py and predict_per_example.py run the
+        pattern model, build every pattern on the host and hand its 3D edges to the edge-pair classifier): predict_pattern, the
+        panels placed in 3D (DecodedPatterns.place: ops.pattern_place), then stitch_model.predict_stitches on the placed edges
+        (`stitch_model` a StitchOnEdge3DPairs in eval mode, `stitch_data_stats` its {'f_shift', 'f_scale'}; **kw are
+        predict_stitches' keywords).  -> the DecodedPatterns with the classifier's answer attached as `pair_stitches`,
+        `num_pair_stitches`, `pair_scores`; no host read before its as_spec(i, stitches='classifier') / to_json."""
+        if stitch_model.training:
+            raise RuntimeError('predict_garment runs the eval-mode stitch classifier: call .eval() on it first (the reference does, '
+                               'pattern_converter.py:415)')
+        d = self.predict_pattern(positions_batch, data_config, route=route).place()
+        return d.attach_pair_stitches(stitch_model.predict_stitches(d.edges3d, d.num_edges, stitch_data_stats, **kw))
+
     _predicts_patterns = False
 
 

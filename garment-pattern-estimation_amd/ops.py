@@ -1797,6 +1797,23 @@ def _stitch_row_off(e, Lm, E):
     return Lm * q * E - Lm * Lm * (q * (q + 1) // 2) + r * (E - (q + 1) * Lm)
 
 
+_STITCH_STAT_CONSTS = {}     # (device, shift, scale) -> (1 / scale, - shift / scale) on the device, read-only
+
+
+def _stitch_stat_consts(shift, scale, dev):
+    """the two vectors that fold the pair rows' standardisation into the first Linear.  They come from host numbers, and a copy from
+    the host cannot be captured: a call with statistics seen before (a warm-up call, as for every lazily built state) reuses the
+    tensors of the first, so that stitch_pairs is legal inside a stream capture (model.predict_garment)."""
+    key = (dev, tuple(shift), tuple(scale))
+    hit = _STITCH_STAT_CONSTS.get(key)
+    if hit is None:
+        hit = (torch.tensor([1.0 / s for s in scale], device=dev, dtype=F32),
+               torch.tensor([-sh / sc for sh, sc in zip(shift, scale)], device=dev, dtype=F32))
+        if len(_STITCH_STAT_CONSTS) < 16:       # a kept pair is never dropped (another stream may still read it); past 16 sets: as before
+            _STITCH_STAT_CONSTS[key] = hit
+    return hit
+
+
 def _stitch_fused(edges, ne, blocks, shift, scale, table, dense, ev=None):
     """the store-free route: per-edge projections [A | Bv] of the first Linear (standardisation folded in), then one launch that
     classifies every pair from them (ev: the workspaces of an evaluating pass, _stitch_eval_ws)"""
@@ -1805,8 +1822,7 @@ def _stitch_fused(edges, ne, blocks, shift, scale, table, dense, ev=None):
     n = len(blocks) - 1
     H = blocks[0][0].weight.shape[0]
     W1, b1 = blocks[0][0].weight, blocks[0][0].bias
-    inv = torch.tensor([1.0 / s for s in scale], device=dev, dtype=F32)
-    off = torch.tensor([-sh / sc for sh, sc in zip(shift, scale)], device=dev, dtype=F32)
+    inv, off = _stitch_stat_consts(shift, scale, dev)
     ab = torch.empty(B * P * Lm, 2 * H, device=dev, dtype=F32)
     rows = _rows2d(edges.view(-1, Fe))
     linear_raw(rows, pack_weight(W1[:, :Fe], col_scale=inv[:Fe]), fold_bias(W1, b1, off), B * P * Lm, H, Fe, (ab, 2 * H, 0, 0))
@@ -2843,6 +2859,47 @@ def pattern_decode(preds, data_stats, explicit_stitch_tags=False, stitches=None,
     L.call('gpe_pattern_decode', ol, *_view_strides(ol), rot, _row_stride(rot, P), R, tr, _row_stride(tr, P), T, *t_args,
            B, P, Lp, S, 1 if explicit_stitch_tags else 0, stats,
            *[o[k] if o[k].numel() else None for k in PATTERN_DECODE_KEYS])
+    return o
+
+
+# the panels of a decoded prediction placed in 3D (csrc/gpe_pattern_place.hip)
+PATTERN_PLACE_KEYS = ('rot_matrix', 'translation', 'top_mid', 'vertices3d', 'edges3d', 'place_flags')
+PATTERN_PLACE_INPUTS = ('num_edges', 'num_verts', 'vertices', 'curvature', 'curved', 'rotations', 'translations')
+PLACE_BAD_QUAT = 1                                      # include/gpe_hip_place.h GPE_PLACE_BAD_QUAT
+
+
+def pattern_place(decoded):
+    """The step between the two prediction stages (NNSewingPattern._3D_edges_per_panel, nn/data/pattern_converter.py:517-552, and the
+    inverse of the universal translation, :281-288) for a batch, one launch, no host read: `decoded` is pattern_decode's dict (or
+    anything with its PATTERN_PLACE_INPUTS).  Per non-empty panel, in fp64: the rotation matrix of the normalised quaternion, the
+    bounding-box side midpoint that lies highest in 3D (`top_mid`), the translation of the panel's origin, the vertices in 3D, and
+    the compact fp32 edge rows `edges3d` [B,P,L,8] that stitch_pairs takes with `num_edges`.
+    -> dict of device tensors, PATTERN_PLACE_KEYS (layouts: include/gpe_hip_place.h gpe_pattern_place)."""
+    t = {k: decoded[k] for k in PATTERN_PLACE_INPUTS}
+    for v in t.values():
+        if not v.is_cuda:
+            raise RuntimeError('gpe ops need tensors on the MI355X (got a %s tensor); there is no CPU path' % v.device)
+    if t['curved'].dim() != 3:
+        raise ValueError('pattern_place: curved [B,P,L] expected (got %s)' % (tuple(t['curved'].shape),))
+    B, P, Lp = t['curved'].shape
+    if t['rotations'].shape[-1] != 4 or t['translations'].shape[-1] != 3:
+        raise ValueError('pattern_place: quaternions (rotation width 4) and 3D translations (width 3) are placed (got widths %d, %d)'
+                         % (t['rotations'].shape[-1], t['translations'].shape[-1]))
+    if not (1 <= P * Lp <= PATTERN_MAX_EDGES) or B < 1:
+        raise ValueError('pattern_place: 1 <= P * L <= %d edge slots are supported (got P = %d, L = %d)' % (PATTERN_MAX_EDGES, P, Lp))
+    shapes = {'num_edges': (B, P), 'num_verts': (B, P), 'vertices': (B, P, Lp + 1, 2), 'curvature': (B, P, Lp, 2),
+              'curved': (B, P, Lp), 'rotations': (B, P, 4), 'translations': (B, P, 3)}
+    for k, shape in shapes.items():
+        want = torch.int32 if k in ('num_edges', 'num_verts', 'curved') else F64
+        if tuple(t[k].shape) != shape or t[k].dtype != want:
+            raise ValueError('pattern_place: %s of %s %s expected (got %s %s)' % (k, want, shape, t[k].dtype, tuple(t[k].shape)))
+        t[k] = t[k].detach().contiguous()
+    dev = t['curved'].device
+    o = {'rot_matrix': torch.empty(B, P, 3, 3, device=dev, dtype=F64), 'translation': torch.empty(B, P, 3, device=dev, dtype=F64),
+         'top_mid': torch.empty(B, P, device=dev, dtype=torch.int32),
+         'vertices3d': torch.empty(B, P, Lp + 1, 3, device=dev, dtype=F64),
+         'edges3d': torch.empty(B, P, Lp, 8, device=dev, dtype=F32), 'place_flags': torch.empty(B, P, device=dev, dtype=torch.int32)}
+    L.call('gpe_pattern_place', *[t[k] for k in PATTERN_PLACE_INPUTS], B, P, Lp, *[o[k] for k in PATTERN_PLACE_KEYS])
     return o
 
 
