@@ -14,6 +14,8 @@
 #include "../../include/gpe_hip_eval.h"
 // ... and the 3D placement of decoded panels, bound through _lib.PLACE_HEADERS
 #include "../../include/gpe_hip_place.h"
+// ... and the two-stage evaluation pass (the classifier scored on predicted patterns), bound through _lib.FRAMEWORK_HEADERS
+#include "../../include/gpe_hip_framework.h"
 
 #define GPE_OK 0
 #define GPE_EINVAL (-22)

@@ -2740,7 +2740,6 @@ class EvalAccumulator:
         reference's None for an empty list).  `.last_sums` / `.last_counts` / `.last_batches` keep what was read.  along: further
         device tensors of fp32 / int32 to bring over in the same transfer; `.last_along` holds them as numpy arrays of their own
         dtype and shape, in order."""
-        K, S = len(self.keys), self.slots
         along = [t.detach() for t in along]
         if any(t.dtype not in (F32, torch.int32) or t.device != self.state.device for t in along):
             raise ValueError('EvalAccumulator.read: along takes fp32 / int32 tensors on the accumulator\'s device')
@@ -2749,7 +2748,12 @@ class EvalAccumulator:
         edges = np.cumsum([p.numel() for p in parts])
         self.last_along = [host[a:b].view(np.float32 if t.dtype == F32 else np.int32).reshape(tuple(t.shape))
                            for a, b, t in zip(edges[:-1], edges[1:], along)]
-        host = host[:edges[0]]
+        return self.parse(host[:edges[0]])
+
+    def parse(self, host):
+        """read()'s result from `.state` as it arrived on the host (int32 numpy): for a caller that brought the state over in a
+        transfer of its own (evaluation.FrameworkEvaluator reads it along with the second stage's accumulator)"""
+        K, S = len(self.keys), self.slots
         if host[-1]:
             raise RuntimeError('EvalAccumulator: an add() met a slot word outside 0 .. %d and was dropped' % (S - 1))
         sums = host[:S * K].view(np.float32).reshape(S, K)
@@ -2901,6 +2905,185 @@ def pattern_place(decoded):
          'edges3d': torch.empty(B, P, Lp, 8, device=dev, dtype=F32), 'place_flags': torch.empty(B, P, device=dev, dtype=torch.int32)}
     L.call('gpe_pattern_place', *[t[k] for k in PATTERN_PLACE_INPUTS], B, P, Lp, *[o[k] for k in PATTERN_PLACE_KEYS])
     return o
+
+
+# the edge-pair classifier scored on predicted patterns over a whole set (csrc/gpe_framework_eval.hip)
+FRAMEWORK_EVAL_KEYS = ('full_loss', 'edge_pair_class_loss', 'edge_pair_class_acc', 'stitch_precision', 'stitch_recall',
+                       'selected_precision', 'selected_recall')              # include/gpe_hip_framework.h, in the kernel's order
+FRAMEWORK_SKIP_REASONS = ('bad_rotation', 'no_stitches', 'no_pairs', 'wrong_panel_count')       # states 1, 2, 3; counted but not corr
+FRAMEWORK_SETS = ('stitch', 'stitch_corr')
+FRAMEWORK_RECORD = ('state', 'corr', 'loss_sum') + STITCH_EVAL_COUNTS + ('num_selected',)
+FRAMEWORK_TOTALS = STITCH_EVAL_COUNTS + ('num_selected', 'garments')
+FRAMEWORK_MAX_PANELS = 64
+
+
+class FrameworkAccumulator:
+    """Step 3 of the reference's on_test_set.py -st ... -corr kept on the device: which garments of a batch count
+    (GarmentStitchPairsDataset._clean_datapoint_list, nn/data/datasets.py:1134-1159), their per-garment values folded as
+    _eval_metrics_per_loader folds batches of one garment (nn/metrics/eval_utils.py:35-76), for all counted garments ('stitch') and
+    for those with the right number of panels ('stitch_corr').  One launch per batch (include/gpe_hip_framework.h
+    gpe_framework_eval_add), ONE host read at the end.  It mirrors EvalAccumulator:
+
+        acc = FrameworkAccumulator(slots=len(folders), total=garments, device='cuda')
+        for ...: acc.add(stitch_pairs_eval's dict, DecodedPatterns after place(), gt_num_panels)
+        totals, loss, ratios = acc.pool(groups, n_groups)        # device tensors, batch-independent
+        rows = acc.read()                                        # [{'stitch': {...}, 'stitch_corr': {...}, 'skipped': {...}}] per slot
+
+    `.table` fp64 [total, 10] keeps one record per garment in visiting order (FRAMEWORK_RECORD); `.rows` counts the garments seen."""
+
+    def __init__(self, slots=1, total=1, device='cuda'):
+        if isinstance(slots, bool) or not isinstance(slots, int) or slots < 1:
+            raise ValueError('FrameworkAccumulator: slots must be a positive integer (got %r)' % (slots,))
+        if isinstance(total, bool) or not isinstance(total, int) or not 1 <= total <= 0x7fffffff:
+            raise ValueError('FrameworkAccumulator: total must be the number of garments of the pass, 1 .. 2^31 - 1 (got %r)' % (total,))
+        self.device = torch.device(device)
+        if self.device.type != 'cuda':
+            raise RuntimeError('gpe ops need tensors on the MI355X (got device %s); there is no CPU path' % self.device)
+        K = len(FRAMEWORK_EVAL_KEYS)
+        self.slots, self.total, self.rows = slots, total, 0
+        # one allocation, one read: sum [2, slots, K] as its fp32 bits | cnt [2, slots] | skipped [slots, 4] | status [1]
+        self.state = torch.zeros(2 * slots * K + 2 * slots + 4 * slots + 1, device=self.device, dtype=torch.int32)
+        self.device = self.state.device                        # with its index: what the batches' tensors are compared with
+        a, b = 2 * slots * K, 2 * slots * K + 2 * slots
+        self.sum = self.state[:a].view(F32).view(2, slots, K)
+        self.cnt = self.state[a:b].view(2, slots)
+        self.skipped = self.state[b:b + 4 * slots].view(slots, 4)
+        self.status = self.state[-1:]
+        self.table = torch.zeros(total, len(FRAMEWORK_RECORD), device=self.device, dtype=F64)
+        self.slot = torch.zeros(1, device=self.device, dtype=torch.int32)
+        self._slot_host = torch.arange(slots, dtype=torch.int32).pin_memory()      # sources of set_slot's queued one-word copies
+
+    def reset(self):
+        """sums, counters, the table and the status back to zero, the slot word to row 0 (queued; no device read)"""
+        self.state.zero_()
+        self.table.zero_()
+        self.slot.zero_()
+        self.rows = 0
+
+    def set_slot(self, i):
+        """the following add() calls go to row i: a queued copy from pinned memory, no device read"""
+        if isinstance(i, bool) or not isinstance(i, int) or not 0 <= i < self.slots:
+            raise ValueError('FrameworkAccumulator.set_slot: row 0 .. %d (got %r)' % (self.slots - 1, i))
+        self.slot.copy_(self._slot_host[i:i + 1], non_blocking=True)
+
+    def add(self, eval_out, decoded, gt_num_panels, records=None):
+        """one batch: eval_out is stitch_pairs_eval's dict ('counts', 'loss_sum', 'num_stitches'), decoded the placed DecodedPatterns
+        (or a dict with 'num_stitches', 'first_invalid', 'num_panels', 'num_edges', 'place_flags'), gt_num_panels integer [B].
+        records: the fp64 [B, 10] rows to write instead of the next B rows of `.table` (a captured add() writes static rows)."""
+        get = (lambda k: getattr(decoded, k)) if not isinstance(decoded, dict) else decoded.__getitem__
+        try:
+            counts, loss_sum, n_sel = eval_out['counts'], eval_out['loss_sum'], eval_out['num_stitches']
+            dec = {k: get(k) for k in ('num_stitches', 'first_invalid', 'num_panels', 'num_edges', 'place_flags')}
+        except (KeyError, AttributeError) as e:
+            raise ValueError('FrameworkAccumulator.add: %s is missing (eval_out: ops.stitch_pairs_eval\'s dict; decoded: a placed '
+                             'DecodedPatterns)' % e)
+        if not torch.is_tensor(counts) or counts.dim() != 2 or counts.shape[1] != 6 or counts.dtype != torch.int32:
+            raise ValueError('FrameworkAccumulator.add: counts must be int32 [B, 6] (got %s %s)'
+                             % (getattr(counts, 'dtype', type(counts).__name__), tuple(getattr(counts, 'shape', ()))))
+        B = counts.shape[0]
+        ne = dec['num_edges']
+        if B < 1 or ne.dim() != 2 or ne.shape[0] != B or not 1 <= ne.shape[1] <= FRAMEWORK_MAX_PANELS:
+            raise ValueError('FrameworkAccumulator.add: num_edges [B = %d, 1 <= P <= %d] expected (got %s)'
+                             % (B, FRAMEWORK_MAX_PANELS, tuple(ne.shape)))
+        P = ne.shape[1]
+        if not torch.is_tensor(loss_sum) or loss_sum.dtype != F64 or tuple(loss_sum.shape) != (B,):
+            raise ValueError('FrameworkAccumulator.add: loss_sum must be fp64 [%d]' % B)
+        if not torch.is_tensor(gt_num_panels) or gt_num_panels.is_floating_point() or gt_num_panels.dtype == torch.bool \
+                or gt_num_panels.numel() != B:
+            raise ValueError('FrameworkAccumulator.add: gt_num_panels must be an integer [%d] tensor' % B)
+        shapes = {'num_selected': (B,), 'num_stitches': (B,), 'first_invalid': (B,), 'num_panels': (B,), 'num_edges': (B, P),
+                  'place_flags': (B, P)}
+        t = dict(dec, num_selected=n_sel)
+        for k, shape in shapes.items():
+            if not torch.is_tensor(t[k]) or t[k].dtype != torch.int32 or tuple(t[k].shape) != shape:
+                raise ValueError('FrameworkAccumulator.add: %s must be int32 %s (got %s %s)'
+                                 % (k, shape, getattr(t[k], 'dtype', type(t[k]).__name__), tuple(getattr(t[k], 'shape', ()))))
+        own = records is None
+        if own:
+            if self.rows + B > self.total:
+                raise ValueError('FrameworkAccumulator.add: more garments than the %d that total announced' % self.total)
+            records = self.table[self.rows:self.rows + B]
+        elif (not torch.is_tensor(records) or records.dtype != F64 or tuple(records.shape) != (B, len(FRAMEWORK_RECORD))
+              or not records.is_contiguous()):
+            raise ValueError('FrameworkAccumulator.add: records must be a contiguous fp64 [%d, %d] tensor' % (B, len(FRAMEWORK_RECORD)))
+        for v in [counts, loss_sum, gt_num_panels, records] + list(t.values()):
+            if v.device != self.device:
+                if not v.is_cuda:
+                    raise RuntimeError('gpe ops need tensors on the MI355X (got a %s tensor); there is no CPU path' % v.device)
+                raise ValueError('FrameworkAccumulator.add: a tensor lives on %s, the accumulator on %s' % (v.device, self.device))
+        gtp = gt_num_panels.detach().reshape(B).to(torch.int32).contiguous()
+        L.call('gpe_framework_eval_add', counts.contiguous(), loss_sum.contiguous(), t['num_selected'].contiguous(),
+               t['num_stitches'].contiguous(), t['first_invalid'].contiguous(), t['num_panels'].contiguous(), gtp,
+               t['num_edges'].contiguous(), t['place_flags'].contiguous(), B, P, self.sum, self.cnt, self.skipped, records, self.slot,
+               self.slots, self.status)
+        if own:
+            self.rows += B
+
+    def pool(self, groups=None, n_groups=0, table=None):
+        """the records of the garments seen so far (or `table`, fp64 [G, 10]) folded per group and overall, independent of the
+        batching: -> (totals int64 [n_groups + 1, 2, 8] FRAMEWORK_TOTALS, loss fp64 [n_groups + 1, 2], ratios fp32
+        [n_groups + 1, 2, 6] STITCH_EVAL_METRICS) on the device; axis 1 is FRAMEWORK_SETS.  groups: int32 [G] on the device (an id
+        outside 0 .. n_groups-1 belongs to no group), or None with n_groups = 0.  One launch, no host read."""
+        if table is None:
+            if self.rows < 1:
+                raise ValueError('FrameworkAccumulator.pool: no garment has been added')
+            table = self.table[:self.rows]
+        elif (not torch.is_tensor(table) or table.dtype != F64 or table.dim() != 2 or table.shape[1] != len(FRAMEWORK_RECORD)
+              or table.shape[0] < 1 or not table.is_contiguous()):
+            raise ValueError('FrameworkAccumulator.pool: table must be a contiguous fp64 [G, %d] tensor' % len(FRAMEWORK_RECORD))
+        G = table.shape[0]
+        if isinstance(n_groups, bool) or not isinstance(n_groups, int) or not 0 <= n_groups <= 65535:
+            raise ValueError('FrameworkAccumulator.pool: n_groups must be an integer in 0 .. 65535 (got %r)' % (n_groups,))
+        if groups is None:
+            if n_groups:
+                raise ValueError('FrameworkAccumulator.pool: %d groups need a group id per garment' % n_groups)
+        elif (not torch.is_tensor(groups) or groups.dtype != torch.int32 or tuple(groups.shape) != (G,)
+              or groups.device != table.device or not groups.is_contiguous()):
+            raise ValueError('FrameworkAccumulator.pool: groups must be a contiguous int32 [%d] tensor on the device of the table' % G)
+        if not table.is_cuda:
+            raise RuntimeError('gpe ops need tensors on the MI355X (got a %s table); there is no CPU path' % table.device)
+        dev = table.device
+        totals = torch.empty(n_groups + 1, 2, len(FRAMEWORK_TOTALS), device=dev, dtype=torch.int64)
+        loss = torch.empty(n_groups + 1, 2, device=dev, dtype=F64)
+        ratios = torch.empty(n_groups + 1, 2, len(STITCH_EVAL_METRICS), device=dev, dtype=F32)
+        L.call('gpe_framework_eval_pool', table, groups, G, n_groups, totals, loss, ratios)
+        return totals, loss, ratios
+
+    def read(self, along=()):
+        """THE host read -> one dict per row: {'stitch': {key: value}, 'stitch_corr': {key: value}, 'skipped': {reason: int}} with
+        value = np.float32(sum) / np.float32(cnt), None where no garment of the set was counted (the reference's None for an empty
+        list).  `.last_sums` [2, slots, 7] / `.last_counts` [2, slots] / `.last_skipped` [slots, 4] keep what was read.  along:
+        further device tensors of fp32 / int32 / fp64 / int64 to bring over in the same transfer; `.last_along` holds them as numpy
+        arrays of their own dtype and shape, in order."""
+        kinds = {F32: np.float32, torch.int32: np.int32, F64: np.float64, torch.int64: np.int64}
+        along = [t.detach() for t in along]
+        if any(t.dtype not in kinds or t.device != self.state.device for t in along):
+            raise ValueError('FrameworkAccumulator.read: along takes fp32 / int32 / fp64 / int64 tensors on the accumulator\'s device')
+        parts = [self.state] + [t.contiguous().view(torch.int32).reshape(-1) for t in along]
+        host = (torch.cat(parts) if along else self.state).cpu().numpy()
+        edges = np.cumsum([p.numel() for p in parts])
+        self.last_along = [host[a:b].view(kinds[t.dtype]).reshape(tuple(t.shape)) for a, b, t in zip(edges[:-1], edges[1:], along)]
+        return self.parse(host[:edges[0]])
+
+    def parse(self, host):
+        """read()'s result from `.state` as it arrived on the host (int32 numpy): for a caller that brought the state over in a
+        transfer of its own (evaluation.FrameworkEvaluator reads it along with the first stage's accumulator)"""
+        K, S = len(FRAMEWORK_EVAL_KEYS), self.slots
+        host = np.ascontiguousarray(host, dtype=np.int32).reshape(-1)
+        if host.size != self.state.numel():
+            raise ValueError('FrameworkAccumulator.parse: %d words expected (got %d)' % (self.state.numel(), host.size))
+        if host[-1]:
+            raise RuntimeError('FrameworkAccumulator: an add() met a slot word outside 0 .. %d and was dropped' % (S - 1))
+        a, b = 2 * S * K, 2 * S * K + 2 * S
+        sums, cnts, skipped = host[:a].view(np.float32).reshape(2, S, K), host[a:b].reshape(2, S), host[b:b + 4 * S].reshape(S, 4)
+        self.last_sums, self.last_counts, self.last_skipped = sums, cnts, skipped
+        rows = []
+        for s in range(S):
+            row = {name: {k: (np.float32(sums[i, s, j]) / np.float32(cnts[i, s]) if cnts[i, s] else None)
+                          for j, k in enumerate(FRAMEWORK_EVAL_KEYS)} for i, name in enumerate(FRAMEWORK_SETS)}
+            row['skipped'] = {r: int(skipped[s, j]) for j, r in enumerate(FRAMEWORK_SKIP_REASONS)}
+            rows.append(row)
+        return rows
 
 
 def standardize(x, shift, scale):

@@ -43,6 +43,17 @@ class DecodedPatterns:
             self.placed = ops.pattern_place(self.tensors)
         return self
 
+    def label_stitches(self):
+        """the stitches this pattern carries as labels for the edge-pair classifier: -> (stitches int32 [B, 2, S], n_labels int32
+        [B]), both on the device, no host read.  n_labels = first_invalid where a stitch names a missing panel (the stitches before
+        it, as _pred_to_pattern keeps them, nn/data/datasets.py:756-765), num_stitches otherwise.  The ids are panel * L + row — what
+        ops.stitch_pairs_eval takes as gt_stitches, which reads `id % L` as the index in the panel's compact edge list: the
+        reference compares the stored edge id with that index in the same way and does not notice a dropped row (stitch_flags bit
+        1, include/gpe_hip.h; INTEGRATION.md)."""
+        import torch
+        first, nums = self.tensors['first_invalid'], self.tensors['num_stitches']
+        return self.tensors['stitches'], torch.where(first >= 0, first, nums)
+
     def attach_pair_stitches(self, out):
         """the edge-pair classifier's answer (ops.stitch_pairs' dict) on this batch's edges3d, for as_spec(stitches='classifier')"""
         self.pairs = {'pair_stitches': out['stitches'], 'num_pair_stitches': out['num_stitches'], 'pair_scores': out['scores']}
