@@ -23,6 +23,7 @@
 // and the entry points.
 #include "gpe_device.h"
 #include "gpe_redgemm_plan.h"
+#include <limits.h>
 #include <stdlib.h>
 
 // b3 kernel, compile-time switches (A/B builds through scripts/ab_build.sh; run-time flags cost this kernel registers it does not
@@ -1391,10 +1392,16 @@ static int rd_finish(const RdParams& p, const GpeRdPlan& plan, float* G, int ldG
     return GPE_OK;
 }
 
+// the plan of a call under this process's state: rd_run and gpe_redgemm_path both ask here, nowhere else
+static GpeRdPlan rd_plan(const RdParams& p, int vmode, bool want_colsum)
+{
+    return gpe_redgemm_plan(p, vmode, want_colsum, gpe_math_redgemm(), gpe_debug_get(), gpe_rd_switches(), gpe_num_cus());
+}
+
 // fill the plan, switch on the path, finish
 static int rd_run(RdParams& p, int vmode, float* G, int ldG, float* colsum, float* part, int accumulate, hipStream_t s)
 {
-    const GpeRdPlan plan = gpe_redgemm_plan(p, vmode, colsum != nullptr, gpe_math_redgemm(), gpe_debug_get(), gpe_rd_switches(), gpe_num_cus());
+    const GpeRdPlan plan = rd_plan(p, vmode, colsum != nullptr);
     if (plan.path == GPE_RD_NOTHING) return plan.rc;
     p.vec = plan.vec; p.MgPad = plan.MgPad; p.NgPad = plan.NgPad; p.num_tiles = plan.num_tiles;
     p.umagic = plan.umagic; p.vmagic = plan.vmagic; p.pin_tpc = plan.pin_tpc;
@@ -1416,15 +1423,39 @@ static int rd_run(RdParams& p, int vmode, float* G, int ldG, float* colsum, floa
     return rd_finish(p, plan, G, ldG, colsum, accumulate, s);
 }
 
+// the call as received, or false where the entry point refuses it: what gpe_redgemm / gpe_edge_redgemm and gpe_redgemm_path check alike
+// (the outputs — G, its pitch, part — are the entry points' own to check)
+static bool rd_call_dense(RdParams& p, const float* u, long u_so, long u_si, int u_inner, const float* v, long v_so, long v_si, int v_inner,
+                          long rows, int Mg, int Ng)
+{
+    if (!u || !v || rows < 0 || Mg <= 0 || Ng <= 0 || Ng > 256) return false;
+    p.rows = rows; p.Mg = Mg; p.Ng = Ng;
+    p.u = GpeRows{u, u_so, u_si, u_inner};
+    p.v = GpeRows{v, v_so, v_si, v_inner};
+    return true;
+}
+static bool rd_call_edge(RdParams& p, const float* u, int ldu, int v_mode, const float* v, int ldv, const float* pq, int ldpq, bool has_jg,
+                         int B, int N, int k, int Mg, int Ng, bool lazy, bool has_amax_u, bool has_amax_v)
+{
+    if (!u || B <= 0 || N <= 0 || k <= 0 || Mg <= 0 || Ng <= 0 || Ng > 256 || ldu < Mg) return false;
+    if (v_mode == 0 && (!pq || !has_jg || (Ng & 3) || (ldpq & 3))) return false;
+    if ((long)B * N * k >= (1L << 31)) return false;
+    if (v_mode == 1 && (!v || ldv < Ng)) return false;
+    if (lazy && (k != 16 || v_mode != 1 || !has_amax_u || !has_amax_v)) return false;
+    p.rows = (long)B * N * k; p.Mg = Mg; p.Ng = Ng;
+    p.u = GpeRows{u, ldu, 0, 0};
+    p.v = GpeRows{v, ldv, 0, 0};
+    p.pq = pq; p.ldpq = ldpq; p.H = Ng; p.k = k; p.rcp_k = 1.0 / k; p.kmagic = (unsigned)(((1ull << 32) + k - 1) / k);
+    p.pin_clouds = B;
+    return true;
+}
+
 extern "C" int gpe_redgemm(const float* u, long u_so, long u_si, int u_inner, const float* v, long v_so,
                            long v_si, int v_inner, const float* v_shift, long rows, int Mg, int Ng, float* G,
                            int ldg, float* colsum, float* part, int accumulate, void* stream)
 {
-    if (!u || !v || !G || !part || rows < 0 || Mg <= 0 || Ng <= 0 || Ng > 256 || ldg < Ng) return GPE_EINVAL;
     RdParams p = {};
-    p.rows = rows; p.Mg = Mg; p.Ng = Ng;
-    p.u = GpeRows{u, u_so, u_si, u_inner};
-    p.v = GpeRows{v, v_so, v_si, v_inner};
+    if (!G || !part || ldg < Ng || !rd_call_dense(p, u, u_so, u_si, u_inner, v, v_so, v_si, v_inner, rows, Mg, Ng)) return GPE_EINVAL;
     p.v_shift = v_shift;
     return rd_run(p, V_DENSE, G, ldg, colsum, part, accumulate, (hipStream_t)stream);
 }
@@ -1435,35 +1466,62 @@ extern "C" int gpe_edge_redgemm(const float* u, int ldu, int v_mode, const float
                                 const uint32_t* amax_v, void* ws, long ws_bytes, const float* lz_g, int lz_ldg,
                                 const uint8_t* lz_amx, const uint8_t* lz_amn, int lz_ldagg, const float* lz_coef, void* stream)
 {
-    if (!u || !G || !part || B <= 0 || N <= 0 || k <= 0 || Mg <= 0 || Ng <= 0 || Ng > 256 || ldG < Ng || ldu < Mg)
-        return GPE_EINVAL;
-    if (v_mode == 0 && (!pq || !jg || (Ng & 3) || (ldpq & 3))) return GPE_EINVAL;
-    if ((long)B * N * k >= (1L << 31)) return GPE_EINVAL;
-    if (v_mode == 1 && (!v || ldv < Ng)) return GPE_EINVAL;
     RdParams p = {};
-    p.rows = (long)B * N * k; p.Mg = Mg; p.Ng = Ng;
-    p.u = GpeRows{u, ldu, 0, 0};
-    p.v = GpeRows{v, ldv, 0, 0};
-    p.pq = pq; p.ldpq = ldpq; p.H = Ng; p.jg = jg; p.k = k; p.rcp_k = 1.0 / k; p.kmagic = (unsigned)(((1ull << 32) + k - 1) / k); p.v_shift = v_shift;
-    p.pin_clouds = B;
+    if (!G || !part || ldG < Ng || !rd_call_edge(p, u, ldu, v_mode, v, ldv, pq, ldpq, jg != nullptr, B, N, k, Mg, Ng, lz_g != nullptr,
+                                                amax_u != nullptr, amax_v != nullptr))
+        return GPE_EINVAL;
+    p.jg = jg; p.v_shift = v_shift;
     if (lz_g) {
-        if (!lz_amx || !lz_amn || !lz_coef || lz_ldg < Mg || (lz_ldagg & 3) || lz_ldagg < ((Mg + 3) & ~3) || k != 16 || v_mode != 1 ||
-            !amax_u || !amax_v)
-            return GPE_EINVAL;
+        if (!lz_amx || !lz_amn || !lz_coef || lz_ldg < Mg || (lz_ldagg & 3) || lz_ldagg < ((Mg + 3) & ~3)) return GPE_EINVAL;
         p.lz_g = lz_g; p.lz_ldg = lz_ldg; p.lz_amx = lz_amx; p.lz_amn = lz_amn; p.lz_ldagg = lz_ldagg; p.lz_coef = lz_coef;
     }
-    if (gpe_math_redgemm() == 2 && amax_u && p.rows >= gpe_h3_min_rows()) {
-        // f16x3: the operand scales must be known without a pass over an E-row tensor — U (a dz tensor) through the caller's amax
-        // word of it, V through the caller's word (dense: the amax the forward kernel measured; gathered: a bound of
-        // relu(P_i + Q_j), gpe_edge_pq_amax) or, for the gathered operand only, the bound passes run here; else exact fp32
+    const GpeEdgeWs w = gpe_edge_ws(ws, ws_bytes);
+    const GpeRdWords words = gpe_rd_settle_words(gpe_math_redgemm(), p.rows, gpe_h3_min_rows(), amax_u != nullptr, amax_v != nullptr,
+                                                 v_mode == 0, w.h3 != nullptr);
+    if (words.give) {
         p.amax_u = amax_u;
         p.amax_v = amax_v;
-        if (!p.amax_v && v_mode == 0) {
-            const GpeEdgeWs w = gpe_edge_ws(ws, ws_bytes);
-            if (w.h3 && gpe_h3_pq_passes(w.h3, reinterpret_cast<float*>(w.h3 + 2), pq, (long)B * N, Ng, ldpq, (hipStream_t)stream) == GPE_OK)
-                p.amax_v = w.h3;
+        // only the launch of the bound passes stays here: gpe_rd_settle_words decided that they run
+        if (words.passes) {
+            if (gpe_h3_pq_passes(w.h3, reinterpret_cast<float*>(w.h3 + 2), pq, (long)B * N, Ng, ldpq, (hipStream_t)stream) == GPE_OK) p.amax_v = w.h3;
+            else p.amax_u = nullptr;
         }
-        if (!p.amax_v) p.amax_u = nullptr;
     }
     return rd_run(p, v_mode == 0 ? V_GATHER : V_DENSE, G, ldG, colsum, part, 0, (hipStream_t)stream);
+}
+
+// Which kernel a gpe_redgemm (k == 0) or gpe_edge_redgemm (k > 0) call runs, and the numbers of its plan (include/gpe_hip.h).  Host
+// only: the pointers are looked at, never followed; the stand-ins below only have to be non-NULL.
+extern "C" int gpe_redgemm_path(const float* u, long u_so, long u_si, int u_inner, const float* v, long v_so, long v_si, int v_inner,
+                                long rows, int Mg, int Ng, int v_mode, int k, int pin_clouds, int has_amax_u, int has_amax_v,
+                                int has_ws, int lazy, int want_colsum, long* plan_out)
+{
+    static const unsigned word = 0;
+    static const float lz = 0.0f;
+    if (v_mode != 0 && v_mode != 1) return GPE_EINVAL;
+    RdParams p = {};
+    if (k == 0) {
+        if (v_mode != 1 || lazy || !rd_call_dense(p, u, u_so, u_si, u_inner, v, v_so, v_si, v_inner, rows, Mg, Ng)) return GPE_EINVAL;
+    } else {
+        // an edge call: single-level rows, B = pin_clouds equal clouds of rows / (B k) points; a gathered V is described by its [P|Q]
+        // table (v = pq, v_so = ldpq)
+        if (u_inner > 0 || v_inner > 0 || k < 0 || pin_clouds <= 0 || rows <= 0 || rows % ((long)pin_clouds * k) != 0) return GPE_EINVAL;
+        if (u_so > INT_MAX || v_so > INT_MAX || u_so < 0 || v_so < 0 || rows / ((long)pin_clouds * k) > INT_MAX) return GPE_EINVAL;
+        const int N = (int)(rows / ((long)pin_clouds * k));
+        if (!rd_call_edge(p, u, (int)u_so, v_mode, v_mode == 1 ? v : nullptr, (int)v_so, v_mode == 0 ? v : nullptr, (int)v_so, true, pin_clouds,
+                          N, k, Mg, Ng, lazy != 0, has_amax_u != 0, has_amax_v != 0))
+            return GPE_EINVAL;
+        if (lazy) p.lz_g = &lz;
+        const GpeRdWords words = gpe_rd_settle_words(gpe_math_redgemm(), p.rows, gpe_h3_min_rows(), has_amax_u != 0, has_amax_v != 0,
+                                                     v_mode == 0, has_ws != 0);
+        if (words.give) p.amax_u = p.amax_v = &word;
+    }
+    const GpeRdPlan plan = rd_plan(p, v_mode == 0 ? V_GATHER : V_DENSE, want_colsum != 0);
+    if (plan.path == GPE_RD_NOTHING) return plan.rc;
+    if (plan_out) {
+        const long out[17] = {plan.gx, plan.gy, plan.gz, plan.nblk, plan.MgPad, plan.NgPad, plan.MH, plan.NH, plan.MT, plan.vec, plan.vvec,
+                              plan.ql, plan.num_tiles, plan.rows_per_split, plan.pin_tpc, plan.floats, plan.cs};
+        for (int i = 0; i < 17; ++i) plan_out[i] = out[i];
+    }
+    return (int)plan.path;
 }

@@ -2,7 +2,8 @@
 // files (gpe_redgemm.hip, and gpe_gemm_x6.hip for the bf16-pipe TN kernel) share on the host lives here ONCE:
 //   the constants more than one place needs, the measurement switches, the call as received (RdParams), the three "can a 16-byte
 //   loader take these rows" predicates, the edge-shape predicate, the layout of the partial image, gpe_redgemm_plan — the whole
-//   selection ladder as a pure function — and the launchers' declarations.
+//   selection ladder as a pure function —, the settlement of gpe_edge_redgemm's amax words in front of it, and the launchers'
+//   declarations.  gpe_redgemm_path (include/gpe_hip.h) gives the plan's answer for a call at the C ABI.
 // A launcher decides nothing: it turns the plan's numbers into template arguments, sizes its kernel's LDS beside the kernel,
 // launches and checks.  The path, gx and the number of partials decide the fp64 summation order of gpe_redgemm_finish, so they are
 // part of the result's bits (tests/test_gpu_grid_sizes.py): a change to this file is a change to those bits.
@@ -306,6 +307,23 @@ static inline GpeRdPlan gpe_redgemm_plan(const RdParams& c, int vmode, bool want
     else if (pc_ok && math == 1) p.path = GPE_RD_B3_BF16;               // 6
     else if (pc_ok) p.path = GPE_RD_PC;                                 // 7
     return p;                                                           // 8
+}
+
+// ---- gpe_edge_redgemm's amax words, settled in front of the plan -----------------------------------------------------------------
+// f16x3: the operand scales must be known without a pass over an E-row tensor — U (a dz tensor) through the caller's amax word of
+// it, V through the caller's word (dense: the amax the forward kernel measured; gathered: a bound of relu(P_i + Q_j),
+// gpe_edge_pq_amax) or, for the gathered operand only, the bound passes run in the caller's workspace; else exact fp32.
+//   give     the plan sees both words (RdParams::amax_u / amax_v), or neither
+//   passes   V's word is the one gpe_h3_pq_passes writes into the workspace; the entry point launches them (if that launch fails the
+//            plan sees neither word)
+struct GpeRdWords { bool give, passes; };
+static inline GpeRdWords gpe_rd_settle_words(int math, long rows, long min_rows, bool has_u, bool has_v, bool gathered, bool has_ws)
+{
+    GpeRdWords w = {false, false};
+    if (math != 2 || !has_u || rows < min_rows) return w;
+    w.passes = !has_v && gathered && has_ws;
+    w.give = has_v || w.passes;
+    return w;
 }
 
 // ---- the launchers, each beside its kernel ---------------------------------------------------------------------------------------

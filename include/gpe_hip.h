@@ -290,6 +290,27 @@ int gpe_edge_redgemm(const float* u, int ldu, int v_mode, const float* v, int ld
                      const float* lz_coef, void* stream);
 /* amax_u / amax_v: amax words of U and of V (v_mode 0: of relu(P_i+Q_j); NULL there = the bound passes run in `ws`).  f16x3 mode
  * runs the fp16-pipe kernel only when both are known, else the exact fp32 kernel. */
+/* Which kernel a reduce-GEMM call runs, and the numbers of its launch.  Added without a version bump (gpe_abi_version() stays 7): one
+ * host-only query, nothing else changes.  HOST ONLY: the pointers are looked at for NULL and for their 16-byte alignment and never
+ * followed, no HIP call is made beyond the CU count (256 without a GPU, less gpe_reserve_cus_set) and nothing is allocated; the
+ * arithmetic mode, the debug word, the f16x3 size gate and the CU reservation are read as the entry points read them, and both
+ * entry points take their plan from the same function.
+ *   k == 0   a gpe_redgemm call: (u, u_so, u_si, u_inner), (v, v_so, v_si, v_inner), rows, Mg, Ng as there; v_mode must be 1,
+ *            pin_clouds, the has_* flags and lazy are not looked at (lazy must be 0)
+ *   k > 0    a gpe_edge_redgemm call with B = pin_clouds clouds of N = rows / (B k) points (rows must divide): single-level rows
+ *            (u, ldu = u_so); v_mode 1: (v, ldv = v_so); v_mode 0: v stands for the [P|Q] table and v_so for ldpq.  has_amax_u /
+ *            has_amax_v: the caller passes that word; has_ws: a workspace of gpe_edge_ws_bytes(...) bytes; lazy: the lz_* fields
+ * want_colsum: colsum != NULL.  Returns -22 where the entry point refuses the call (its checks of G, ldG, part and of the lz_*
+ * pitches aside), else the rung, in the order of DESIGN.md 5.33:
+ *   1 thin   2 bf16-pipe TN   3 deep   4 b3 f16x3 lazy dz3   5 b3 f16x3   6 b3 bf16x3   7 producer/consumer   8 big-block
+ * plan_out (may be NULL; written only with a rung) receives 17 numbers:
+ *   [0] gx [1] gy [2] gz [3] nblk (partials)  [4] MgPad [5] NgPad  [6] MH [7] NH (big-block instance)  [8] MT (rungs 4 - 8)
+ *   [9] vec [10] vvec (deep) [11] ql (thin)  [12] num_tiles [13] rows_per_split (TN)  [14] pin_tpc
+ *   [15] floats the launch writes from `part` on (never more than gpe_redgemm_ws(Mg, Ng))  [16] partial column sums are written
+ * The thresholds are the library's to change; the codes and the positions in plan_out are not. */
+int gpe_redgemm_path(const float* u, long u_so, long u_si, int u_inner, const float* v, long v_so, long v_si, int v_inner,
+                     long rows, int Mg, int Ng, int v_mode, int k, int pin_clouds, int has_amax_u, int has_amax_v, int has_ws,
+                     int lazy, int want_colsum, long* plan_out);
 
 /* propagate + BN/ReLU backward:  u = A.Wp^T ; dz = (act>0) ? s*u - c1 - (act-mean)*k2 : 0 ; written to dz_out
  * (A dense [E][lda]; coef_out [4][Cout] = {s,c1,k2,mean} of the BatchNorm being crossed; Wp = packed TRANSPOSE of the
