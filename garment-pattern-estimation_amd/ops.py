@@ -6,6 +6,11 @@ to torch math: a missing library or a failing launch raises.
 
 Reference lines restated by each Function are cited in its docstring (paths relative to /root/reference).
 
+This module is the training hot path and the facade: the stitch classifier, the losses, the data samplers and the evaluation live
+in ops_stitch / ops_losses / ops_data / ops_eval and are re-exported at the end of this file, so callers spell everything ops.X.
+Every module-level name that callers REBIND through ops (SIDE_GRADS, SIDE_MIN_EDGES, CAPTURE, HOST_DRAWN, RNN_WS_HOOK, ...) is
+defined here and read only by functions defined here (DESIGN.md "ops modules", tests/test_ops_layout_host.py).
+
 Two per-model services live here as well (both optional; without them every Function behaves like a plain autograd op):
   * PackPlan  — all weight-derived kernel operands of a model (MFMA-packed / transposed / gate-interleaved weights, the
                 P|Q split of the first edge Linear, b_ih + b_hh) are rebuilt by ONE launch when the weights changed,
@@ -26,86 +31,8 @@ import torch
 
 from . import _lib as L
 from . import streams
-
-F32 = torch.float32
-
-
-def _dev_check(t):
-    if not t.is_cuda:
-        raise RuntimeError('gpe ops need tensors on the MI355X (got a %s tensor); there is no CPU path' % t.device)
-    if t.dtype != F32:
-        raise RuntimeError('gpe ops are fp32 (got %s)' % t.dtype)
-
-
-def _rows2d(t):
-    """(tensor, stride_outer, stride_inner, inner) descriptor of a [M, K] tensor with unit inner stride."""
-    assert t.dim() == 2 and (t.shape[1] == 1 or t.stride(1) == 1), (t.shape, t.stride())
-    return (t, t.stride(0), 0, 0)
-
-
-def _rows3d(t):
-    """descriptor of a [R, T, K] tensor flattened to R*T logical rows (row r*T+t)."""
-    assert t.dim() == 3 and (t.shape[2] == 1 or t.stride(2) == 1), (t.shape, t.stride())
-    return (t, t.stride(0), t.stride(1), t.shape[1])
-
-
-def round_up(a, b):
-    return (a + b - 1) // b * b
-
-
-_WS = {}                   # (device index, stream handle) -> uint8 tensor: the scratch of that stream's C-ABI calls
-
-
-def _workspace(nbytes, device):
-    """caller-owned scratch of a C-ABI call (include/gpe_hip.h: `ws`).  One grow-only buffer per (device, stream): launches of one
-    stream are ordered, so consecutive calls may share it, and two streams never do (the library's only rule for workspaces).
-    Re-allocation goes through torch's caching allocator, which keeps the old block alive until the stream has passed it."""
-    key = streams.stream_key(device)
-    buf = _WS.get(key)
-    if buf is None or buf.numel() < nbytes:
-        buf = torch.empty(max(int(nbytes), 1 << 20), device=torch.device('cuda', key[0]), dtype=torch.uint8)
-        _WS[key] = buf
-    return buf
-
-
-_EDGE_WS_BYTES = {}
-
-
-def edge_workspace(B, N, k, ldmax, device):
-    """-> (ws, bytes) for gpe_edge_mlp_fwd / _bwd / gpe_edge_redgemm / gpe_edge_pq_amax calls on B clouds of N points, k
-    neighbours, per-point output pitches <= ldmax floats."""
-    key = (B, N, k, ldmax)
-    n = _EDGE_WS_BYTES.get(key)
-    if n is None:
-        n = L.query('gpe_edge_ws_bytes', B, N, k, ldmax)
-        if n < 0:
-            raise RuntimeError('gpe_edge_ws_bytes failed with code %d' % n)
-        _EDGE_WS_BYTES[key] = n
-    return _workspace(n, device), n
-
-
-def f16x3_words(n, rows, device):
-    """n caller-owned "amax words" (include/gpe_hip.h) when the f16x3 arithmetic will run on `rows`-row edge launches, else None:
-    one uint32 per tensor whose largest magnitude a kernel measures while storing it and a later kernel scales by."""
-    if L.get_math() != 'f16x3' or rows < L.query('gpe_f16x3_min_rows'):
-        return None
-    return torch.zeros(n, device=device, dtype=torch.int32)
-
-
-def _word(words, i):
-    return None if words is None else words[i:i + 1]
-
-
-_TICKETS = {}
-
-
-def _ticket(device):
-    """the last-arriver ticket of gpe_pack_fold: one zeroed uint32 per (device, stream), left zero by every launch."""
-    key = streams.stream_key(device)
-    t = _TICKETS.get(key)
-    if t is None:
-        t = _TICKETS[key] = torch.zeros(1, device=torch.device('cuda', key[0]), dtype=torch.int32)
-    return t
+from ._opbase import (F32, F64, _WS, _dev_check, _rows2d, _rows3d, _stitch_ldw, _ticket, _word, _workspace,  # noqa: F401
+                      edge_workspace, f16x3_words, round_up)
 
 
 def pack_fold(W, bias, stats, ews, ews_n, clear_word):
@@ -1766,273 +1693,8 @@ def dense_mlp(x, mlp, training):
 
 
 # -------------------------------------------------------------------------------------------------
-# stitch recovery from the edge-pair classifier (forward only)
+# attention over the points: sparsemax weights and the pooling they drive (nn/nets.py:225-276)
 # -------------------------------------------------------------------------------------------------
-STITCH_PAIRS_MAX_PANELS, STITCH_PAIRS_MAX_EDGES = 32, 16
-STITCH_PAIRS_ROUTES = ('auto', 'fused', 'rows')
-_STITCH_ROWS_BUDGET = 1 << 19              # pair rows the generic route materialises per dense-MLP call
-
-
-def stitch_pairs_on_menu(mlp):
-    """can csrc/gpe_stitch_pairs.hip's fused kernel run this MLP?  (1 - 4 equally wide Linear layers in front of the output Linear,
-    width <= 256 and a multiple of 4, an even number <= 32 of input features)"""
-    blocks = [mlp[i] for i in range(len(mlp))]
-    n = len(blocks) - 1
-    if not 1 <= n <= 4 or blocks[-1][0].weight.shape[0] != 1:
-        return False
-    H, K0 = blocks[0][0].weight.shape
-    if H > 256 or H % 4 or K0 % 2 or K0 > 32:
-        return False
-    return all(tuple(b[0].weight.shape) == (H, H) for b in blocks[1:-1]) and blocks[-1][0].weight.shape[1] == H
-
-
-def _stitch_ldw(H):
-    nb = (H + 15) // 16
-    nb = 4 if nb <= 4 else 8 if nb <= 8 else 13 if nb <= 13 else 16
-    return nb * 16 if (nb * 16) % 32 == 16 else nb * 16 + 16
-
-
-def _stitch_row_off(e, Lm, E):
-    q, r = divmod(e, Lm)
-    return Lm * q * E - Lm * Lm * (q * (q + 1) // 2) + r * (E - (q + 1) * Lm)
-
-
-_STITCH_STAT_CONSTS = {}     # (device, shift, scale) -> (1 / scale, - shift / scale) on the device, read-only
-
-
-def _stitch_stat_consts(shift, scale, dev):
-    """the two vectors that fold the pair rows' standardisation into the first Linear.  They come from host numbers, and a copy from
-    the host cannot be captured: a call with statistics seen before (a warm-up call, as for every lazily built state) reuses the
-    tensors of the first, so that stitch_pairs is legal inside a stream capture (model.predict_garment)."""
-    key = (dev, tuple(shift), tuple(scale))
-    hit = _STITCH_STAT_CONSTS.get(key)
-    if hit is None:
-        hit = (torch.tensor([1.0 / s for s in scale], device=dev, dtype=F32),
-               torch.tensor([-sh / sc for sh, sc in zip(shift, scale)], device=dev, dtype=F32))
-        if len(_STITCH_STAT_CONSTS) < 16:       # a kept pair is never dropped (another stream may still read it); past 16 sets: as before
-            _STITCH_STAT_CONSTS[key] = hit
-    return hit
-
-
-def _stitch_fused(edges, ne, blocks, shift, scale, table, dense, ev=None):
-    """the store-free route: per-edge projections [A | Bv] of the first Linear (standardisation folded in), then one launch that
-    classifies every pair from them (ev: the workspaces of an evaluating pass, _stitch_eval_ws)"""
-    B, P, Lm, Fe = edges.shape
-    dev = edges.device
-    n = len(blocks) - 1
-    H = blocks[0][0].weight.shape[0]
-    W1, b1 = blocks[0][0].weight, blocks[0][0].bias
-    inv, off = _stitch_stat_consts(shift, scale, dev)
-    ab = torch.empty(B * P * Lm, 2 * H, device=dev, dtype=F32)
-    rows = _rows2d(edges.view(-1, Fe))
-    linear_raw(rows, pack_weight(W1[:, :Fe], col_scale=inv[:Fe]), fold_bias(W1, b1, off), B * P * Lm, H, Fe, (ab, 2 * H, 0, 0))
-    linear_raw(rows, pack_weight(W1[:, Fe:], col_scale=inv[Fe:]), None, B * P * Lm, H, Fe, (ab[:, H:], 2 * H, 0, 0))
-    ldw = _stitch_ldw(H)
-    wpk = torch.zeros((n - 1) * (H + 1) * ldw + H + 4, device=dev, dtype=F32)
-    # f16x3: two-term fp16 planes of the hidden layers' folded weights, one power of two per layer (its amax word)
-    h3 = L.get_math() == 'f16x3' and H <= 224 and n > 1
-    KP = round_up(H, 32)
-    planes = torch.empty((n - 1) * KP * ldw, device=dev, dtype=F32) if h3 else None
-    words = torch.empty(n - 1, device=dev, dtype=torch.int32) if h3 else None
-    st = None
-    for l, blk in enumerate(blocks):
-        bn = blk[2]
-        if l > 0:
-            W, b = blk[0].weight, blk[0].bias
-            if l < n:
-                o = (l - 1) * (H + 1) * ldw
-                L.call('gpe_stitch_pairs_pack', W, W.stride(0), H, H, st[2], wpk[o:], ldw)
-                L.call('gpe_fold_bias', W, W.stride(0), H, H, b, st[3], wpk[o + H * ldw:])
-                if h3:
-                    L.call('gpe_absmax', wpk[o:], ldw, H, ldw, words[l - 1:])
-                    L.call('gpe_stitch_pairs_planes', wpk[o:], H, ldw, words[l - 1:], planes[(l - 1) * KP * ldw:])
-            else:
-                o = (n - 1) * (H + 1) * ldw
-                L.call('gpe_stitch_pairs_pack', W, W.stride(0), 1, H, st[2], wpk[o:], 1)
-                L.call('gpe_fold_bias', W, W.stride(0), 1, H, b, st[3], wpk[o + H:])
-        st = bn_from_running(bn.running_mean, bn.running_var, bn.weight, bn.bias, bn.eps)
-    args = (ab, 2 * H, H, n, wpk, planes, words, st, ne, B, P, Lm, table, dense)
-    if ev is None:
-        L.call('gpe_stitch_pairs_fwd', *args)
-    else:
-        n8 = (P * Lm + 7) // 8                  # a slot per 8 x 8 tile position (include/gpe_hip.h)
-        ev['slots'], ev['group'] = n8 * n8, n8
-        ev['slab'] = torch.zeros(B, n8 * n8, device=dev, dtype=torch.float64)
-        L.call('gpe_stitch_pairs_eval_fwd', *args, ev['mask'], ev['slab'], ev['counters'])
-
-
-def _stitch_rows(edges, ne, mlp, shift, scale, table, dense, ev=None):
-    """the generic route: materialised pair rows of a chunk of i-edges -> the dense-MLP kernels (eval) -> the same epilogue"""
-    import ctypes
-    B, P, Lm, Fe = edges.shape
-    E = P * Lm
-    sh = (ctypes.c_float * (2 * Fe))(*[float(v) for v in shift])
-    sc = (ctypes.c_float * (2 * Fe))(*[float(v) for v in scale])
-    last = (P - 1) * Lm                         # the edges of the last panel slot have no later partner
-    if ev is not None:
-        ev['slots'], ev['group'] = E, Lm        # a slot per i-edge, shared by the chunks
-        ev['slab'] = torch.zeros(B, E, device=edges.device, dtype=torch.float64)
-    c0 = 0
-    while c0 < last:
-        c1 = c0 + 1
-        while (c1 < last and B * (c1 + 1 - c0) <= 65535
-               and B * (_stitch_row_off(c1 + 1, Lm, E) - _stitch_row_off(c0, Lm, E)) <= _STITCH_ROWS_BUDGET):
-            c1 += 1
-        nrows = _stitch_row_off(c1, Lm, E) - _stitch_row_off(c0, Lm, E)
-        rows = torch.empty(B * nrows, 2 * Fe, device=edges.device, dtype=F32)
-        L.call('gpe_stitch_pairs_rows', edges, ne, B, P, Lm, Fe, sh, sc, c0, c1, nrows, rows)
-        y = dense_mlp(rows, mlp, False)
-        if ev is None:
-            L.call('gpe_stitch_pairs_reduce', y, y.stride(0), ne, B, P, Lm, c0, c1, nrows, table, dense)
-        else:
-            L.call('gpe_stitch_pairs_eval_reduce', y, y.stride(0), ne, B, P, Lm, c0, c1, nrows, table, dense, ev['mask'], ev['slab'],
-                   ev['counters'])
-        c0 = c1
-
-
-def _stitch_check(edges3d, num_edges, mlp, f_shift, f_scale, route, gt=None):
-    """the argument checks of stitch_pairs / stitch_pairs_eval, all before any device check -> (blocks, fused)"""
-    if route not in STITCH_PAIRS_ROUTES:
-        raise ValueError('unknown route %r (choose from %s)' % (route, STITCH_PAIRS_ROUTES))
-    if edges3d.dim() != 4:
-        raise ValueError('edges3d must be [B, P, L, Fe] (got %s)' % (tuple(edges3d.shape),))
-    B, P, Lm, Fe = edges3d.shape
-    if P > STITCH_PAIRS_MAX_PANELS or Lm > STITCH_PAIRS_MAX_EDGES or P * Lm < 2 or B < 1:
-        raise ValueError('stitch_pairs handles 1 .. %d panels of 1 .. %d edges (got P = %d, L = %d)'
-                         % (STITCH_PAIRS_MAX_PANELS, STITCH_PAIRS_MAX_EDGES, P, Lm))
-    blocks = [mlp[i] for i in range(len(mlp))]
-    if blocks[0][0].weight.shape[1] != 2 * Fe or len(f_shift) != 2 * Fe or len(f_scale) != 2 * Fe or Fe > 16:
-        raise ValueError('the classifier takes %d features per pair, the statistics have %d / %d, the edges %d each (<= 16)'
-                         % (blocks[0][0].weight.shape[1], len(f_shift), len(f_scale), Fe))
-    if mlp.training:
-        raise RuntimeError('stitch_pairs is a prediction path: call .eval() on the model first (BatchNorm running statistics)')
-    if tuple(num_edges.shape) != (B, P) or num_edges.is_floating_point() or num_edges.device != edges3d.device:
-        raise ValueError('num_edges must be an integer [B, P] tensor on the device of edges3d')
-    if gt is not None:
-        st, nums = gt
-        if (not torch.is_tensor(st) or st.dim() != 3 or tuple(st.shape[:2]) != (B, 2) or st.is_floating_point() or st.is_complex()
-                or st.dtype == torch.bool or st.device != edges3d.device):
-            raise ValueError('gt_stitches must be an integer [B, 2, S] tensor of edge ids panel * L + edge on the device of edges3d')
-        if (not torch.is_tensor(nums) or tuple(nums.shape) != (B,) or nums.is_floating_point() or nums.is_complex()
-                or nums.dtype == torch.bool or nums.device != edges3d.device):
-            raise ValueError('gt_num_stitches must be an integer [B] tensor on the device of edges3d')
-    on_menu = stitch_pairs_on_menu(mlp)
-    if route == 'fused' and not on_menu:
-        raise ValueError("route='fused' needs 1 - 4 hidden layers of one width <= 256 that is a multiple of 4; use 'auto' or 'rows'")
-    return blocks, on_menu and route != 'rows'
-
-
-STITCH_EVAL_METRICS = ('edge_pair_class_loss', 'edge_pair_class_acc', 'stitch_precision', 'stitch_recall', 'selected_precision',
-                       'selected_recall')
-STITCH_EVAL_COUNTS = ('pairs', 'correct', 'true_positives', 'predicted_positives', 'gt_positives', 'selected_tp')
-
-
-def _stitch_eval_ws(gt_stitches, gt_num_stitches, B, P, Lm, dev):
-    """the caller-owned, zeroed workspaces of an evaluating pass (sizes: include/gpe_hip.h) with the label mask filled in"""
-    E, S = P * Lm, gt_stitches.shape[2]
-    ev = {'mask': torch.zeros(B, E, (E + 31) // 32, device=dev, dtype=torch.int32),
-          'counters': torch.zeros(B, 2, device=dev, dtype=torch.int64)}
-    # the kernel ignores ids outside 0 .. E - 1 and clamps the counts itself; wider integers are brought into int32's range first
-    st, nums = _int32(gt_stitches, -1, E), _int32(gt_num_stitches, 0, S)
-    L.call('gpe_stitch_pairs_labels', st if S else None, nums, B, P, Lm, S, ev['mask'])
-    return ev
-
-
-def _stitch_run(edges3d, num_edges, mlp, blocks, fused, f_shift, f_scale, return_logits, gt=None):
-    """classify every pair, select; with gt = (gt_stitches, gt_num_stitches) through the evaluating entry points, then finalise"""
-    B, P, Lm, Fe = edges3d.shape
-    dev = edges3d.device
-    E, S = P * Lm, P * Lm // 2
-    shift, scale = [float(v) for v in f_shift], [float(v) for v in f_scale]
-    with torch.no_grad():
-        edges = edges3d.detach().contiguous()
-        ne = num_edges.to(torch.int32).contiguous()
-        table = torch.zeros(B, E, device=dev, dtype=torch.int64)
-        dense = torch.full((B, E, E), float('nan'), device=dev, dtype=F32) if return_logits else None
-        ev = _stitch_eval_ws(gt[0], gt[1], B, P, Lm, dev) if gt is not None else None
-        if fused:
-            _stitch_fused(edges, ne, blocks, shift, scale, table, dense, ev)
-        else:
-            _stitch_rows(edges, ne, mlp, shift, scale, table, dense, ev)
-        stitches = torch.empty(B, 2, S, device=dev, dtype=torch.int32)
-        nums = torch.empty(B, device=dev, dtype=torch.int32)
-        scores = torch.empty(B, S, device=dev, dtype=F32)
-        L.call('gpe_stitch_select', table, B, P, Lm, stitches, nums, scores)
-        out = {'stitches': stitches, 'num_stitches': nums, 'scores': scores}
-        if return_logits:
-            out['logits'] = dense
-        if ev is not None:
-            loss_sum = torch.empty(B, device=dev, dtype=torch.float64)
-            counts = torch.empty(B, 6, device=dev, dtype=torch.int32)
-            metrics = torch.empty(6, device=dev, dtype=F32)
-            L.call('gpe_stitch_eval_finalize', ev['slab'], ev['slots'], ev['group'], ev['counters'], ev['mask'], stitches, nums, B, P,
-                   Lm, loss_sum, counts, metrics)
-            out.update(metrics={k: metrics[i] for i, k in enumerate(STITCH_EVAL_METRICS)}, counts=counts, loss_sum=loss_sum)
-    return out
-
-
-def stitch_pairs(edges3d, num_edges, mlp, f_shift, f_scale, route='auto', return_logits=False):
-    """Stitches of B garments from the edge-pair classifier `mlp` (net_blocks.MLP([2 Fe, H x n, 1]), eval mode): what the
-    reference does at prediction time with NNSewingPattern.all_edge_pairs + stitches_from_pair_classifier
-    (nn/data/pattern_converter.py:411-499) with the intended indexing of line 432.
-
-    edges3d [B, P, L, Fe] fp32: un-standardised 3D edges per panel slot; num_edges [B, P] int (0 = panel absent); f_shift / f_scale:
-    2 Fe numbers.  -> stitches int32 [B, 2, S] (edge ids panel * L + edge, side 0 = lower panel, ascending (i, j, r, c), zero-padded;
-    S = P * L // 2), num_stitches int32 [B], scores fp32 [B, S] (logits) and, with return_logits, the dense logits [B, P*L, P*L]
-    (NaN where there is no pair).  No host synchronisation.  route: 'fused' (csrc/gpe_stitch_pairs.hip's store-free kernel; ValueError
-    off its menu), 'rows' (materialised rows through the dense-MLP kernels), 'auto' (fused on the menu, rows otherwise)."""
-    blocks, fused = _stitch_check(edges3d, num_edges, mlp, f_shift, f_scale, route)
-    _dev_check(edges3d)
-    return _stitch_run(edges3d, num_edges, mlp, blocks, fused, f_shift, f_scale, return_logits)
-
-
-def stitch_pairs_eval(edges3d, num_edges, mlp, f_shift, f_scale, gt_stitches, gt_num_stitches, route='auto', return_logits=False):
-    """stitch_pairs scored against ground-truth stitches in the same classification pass: the reference's evaluation of this model
-    (GarmentStitchPairsDataset with random_pairs_mode False: the labels of all_edge_pairs, nn/data/pattern_converter.py:458-499, into
-    ComposedLoss, nn/metrics/composed_loss.py:83-126) without a pair row, a logit or a label stored, and without a host read.
-
-    gt_stitches integer [B, 2, S] (S may be 0): edge ids panel * L + edge of both sides, either orientation, the layout of the stitch
-    losses; gt_num_stitches integer [B], clamped to 0 .. S.  Entries with an id outside 0 .. P L - 1 are ignored, duplicates are
-    harmless, and an entry that no enumerated pair matches (same panel, absent edge) counts nowhere.
-    -> the dict of stitch_pairs plus 'metrics' {name: fp32 device scalar} pooled over the call (STITCH_EVAL_METRICS: the loss is the
-    mean over the concatenated pairs; selected_* score the selected stitches; a ratio with denominator 0 is 0), 'counts' int32 [B, 6]
-    (STITCH_EVAL_COUNTS) and 'loss_sum' fp64 [B] (the sum of the BCE-with-logits terms per garment).  Bit-reproducible."""
-    blocks, fused = _stitch_check(edges3d, num_edges, mlp, f_shift, f_scale, route, (gt_stitches, gt_num_stitches))
-    _dev_check(edges3d)
-    return _stitch_run(edges3d, num_edges, mlp, blocks, fused, f_shift, f_scale, return_logits, (gt_stitches, gt_num_stitches))
-
-
-class SparsemaxLossFn(torch.autograd.Function):
-    """entmax.SparsemaxLoss()(x, target) as nn/metrics/composed_loss.py:323-332 calls it: mean over rows of the sparsemax
-    Fenchel-Young loss; gradient (sparsemax(x) - onehot(target)) / rows."""
-
-    @staticmethod
-    def forward(ctx, x, target):
-        _dev_check(x)
-        M, W = x.shape
-        if x.stride(1) != 1:
-            x = x.contiguous()
-        tgt = target.to(torch.int32).contiguous()
-        if tgt.numel() != M:
-            raise ValueError('SparsemaxLoss: %d targets for %d rows' % (tgt.numel(), M))
-        gx = torch.empty(M, W, device=x.device, dtype=F32)
-        part = torch.empty((M + 255) // 256, device=x.device, dtype=torch.float64)
-        loss = torch.empty(1, device=x.device, dtype=F32)
-        bad = torch.zeros(1, device=x.device, dtype=torch.int32)
-        L.call('gpe_sparsemax_loss', x, x.stride(0), tgt, M, W, gx, W, part, loss, bad)
-        if bad.item():
-            raise IndexError('SparsemaxLoss: a segmentation label lies outside [0, %d)' % W)
-        ctx.save_for_backward(gx)
-        return loss[0]
-
-    @staticmethod
-    def backward(ctx, g):
-        gx, = ctx.saved_tensors
-        out = torch.empty_like(gx)
-        L.call('gpe_scale_dev', gx, g.reshape(1).to(F32).contiguous(), out, gx.numel())
-        return out, None
-
-
 class SparsemaxFn(torch.autograd.Function):
     """sparsemax.Sparsemax(dim=1) (nn/nets.py:225)."""
 
@@ -2087,1140 +1749,6 @@ class AttentionPoolFn(torch.autograd.Function):
         gf = torch.empty(B * N, C, device=dev, dtype=F32)
         L.call('gpe_attn_pool_bwd', w, w.stride(0), feat, feat.stride(0), g, ctx.arg, B, N, P, C, mode, gw, P, gf, C)
         return gw, gf, None, None, None
-
-
-# -------------------------------------------------------------------------------------------------
-# loss (the caller-side step right after the path) and its ground-truth matching
-# -------------------------------------------------------------------------------------------------
-LOSS_SHAPE, LOSS_LOOP, LOSS_ROT, LOSS_TR = 1, 2, 4, 8
-
-
-def _view_strides(ol):
-    """(sb, sp, sl) of an outlines view [B,P,L,4] whose last dim is unit-stride (a slice of the [B,P,L,8] output)."""
-    assert ol.dim() == 4 and ol.stride(3) == 1, (ol.shape, ol.stride())
-    return ol.stride(0), ol.stride(1), ol.stride(2)
-
-
-def _row_stride(t, P):
-    """row pitch of a [B,P,c] view of a [B*P, ld] tensor."""
-    assert t.dim() == 3 and t.stride(2) == 1 and t.stride(0) == P * t.stride(1), (t.shape, t.stride())
-    return t.stride(1)
-
-
-class PatternLossFn(torch.autograd.Function):
-    """ComposedPatternLoss._main_losses (nn/metrics/composed_loss.py:294-321) + PanelLoopLoss (nn/metrics/losses.py:19-51)
-    in one forward and one backward launch.  Returns a [5] tensor {total, shape, loop, rotation, translation}; only
-    element 0 carries gradient."""
-
-    @staticmethod
-    def forward(ctx, outlines, rotations, translations, gt_ol, gt_rot, gt_tr, num_edges, flags, pad0, pad1, loop_w):
-        _dev_check(outlines)
-        dev = outlines.device
-        B, P, Lp = outlines.shape[:3]
-        sb, sp, sl = _view_strides(outlines)
-        R = rotations.shape[-1] if rotations is not None else 0
-        T = translations.shape[-1] if translations is not None else 0
-        rs = _row_stride(rotations, P) if rotations is not None else 0
-        ts = _row_stride(translations, P) if translations is not None else 0
-        part = torch.empty(B, 4, device=dev, dtype=torch.float64)
-        loop_sums = torch.empty(B * P, 2, device=dev, dtype=F32)
-        out = torch.empty(5, device=dev, dtype=F32)
-        args = (outlines, sb, sp, sl, rotations, rs, translations, ts, gt_ol, gt_rot, gt_tr, num_edges, B, P, Lp, R, T,
-                flags, float(pad0), float(pad1), float(loop_w))
-        L.call('gpe_pattern_loss_fwd', *args, part, loop_sums, out)
-        ctx.args = args
-        ctx.loop_sums = loop_sums
-        ctx.shapes = (B, P, Lp, R, T)
-        ctx.need = (rotations is not None and rotations.requires_grad,
-                    translations is not None and translations.requires_grad)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        B, P, Lp, R, T = ctx.shapes
-        dev = g.device
-        g = g.contiguous()
-        g_ol = torch.empty(B, P, Lp, 4, device=dev, dtype=F32)
-        g_rot = torch.empty(B, P, R, device=dev, dtype=F32) if ctx.need[0] else None
-        g_tr = torch.empty(B, P, T, device=dev, dtype=F32) if ctx.need[1] else None
-        # g[0] is the upstream gradient of `total` (a device scalar: no host sync)
-        L.call('gpe_pattern_loss_bwd', *ctx.args, ctx.loop_sums, g, g_ol, g_rot, g_tr)
-        return g_ol, g_rot, g_tr, None, None, None, None, None, None, None, None
-
-
-STITCH_MAIN, STITCH_HARDNET, STITCH_FREE, STITCH_SUP = 1, 2, 4, 8
-
-
-class StitchLossFn(torch.autograd.Function):
-    """ComposedPatternLoss._stitch_losses (nn/metrics/composed_loss.py:336-362): PatternStitchLoss (nn/metrics/losses.py:54-180,
-    both negative-term variants), the supervised stitch-tag MSE and the free-edge BCE-with-logits in one forward and one
-    backward launch.  Returns a [5] tensor {total, similarity, negative, supervised, free}; only element 0 carries gradient.
-    stitch_tags [B,P,L,D] and free_logits [B,P,L] are the strided views of the panel decoder's output."""
-
-    @staticmethod
-    def forward(ctx, stitch_tags, free_logits, stitches, nums, gt_mask, gt_tags, flags, margin, sup_w):
-        ref = stitch_tags if stitch_tags is not None else free_logits
-        _dev_check(ref)
-        dev = ref.device
-        B, P, Lp = ref.shape[:3]
-        D = stitch_tags.shape[3] if stitch_tags is not None else 0
-        ts = _view_strides(stitch_tags) if stitch_tags is not None else (0, 0, 0)
-        ms = (free_logits.stride(0), free_logits.stride(1), free_logits.stride(2)) if free_logits is not None else (0, 0, 0)
-        S = stitches.shape[2] if stitches is not None else 0
-        part = torch.empty(B, 6, device=dev, dtype=torch.float64)
-        out = torch.empty(5, device=dev, dtype=F32)
-        args = (stitch_tags, ts[0], ts[1], ts[2], D, free_logits, ms[0], ms[1], ms[2], stitches, nums, S, gt_mask, gt_tags,
-                B, P, Lp, flags, float(margin), float(sup_w))
-        L.call('gpe_stitch_loss_fwd', *args, part, out)
-        ctx.args, ctx.part, ctx.shape = args, part, (B, P, Lp, D)
-        ctx.need = (stitch_tags is not None and bool(flags & (STITCH_MAIN | STITCH_SUP)),
-                    free_logits is not None and bool(flags & STITCH_FREE))
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        B, P, Lp, D = ctx.shape
-        dev = g.device
-        g = g.contiguous()
-        g_tags = torch.empty(B, P, Lp, D, device=dev, dtype=F32) if ctx.need[0] else None
-        g_mask = torch.empty(B, P, Lp, device=dev, dtype=F32) if ctx.need[1] else None
-        L.call('gpe_stitch_loss_bwd', *ctx.args, ctx.part, g, g_tags, g_mask)
-        return g_tags, g_mask, None, None, None, None, None, None, None
-
-
-PAIR_LOSS_METRICS = ('edge_pair_class_loss', 'edge_pair_class_acc', 'stitch_precision', 'stitch_recall')
-PAIR_LOSS_COUNTS = ('pairs', 'correct', 'true_positives', 'predicted_positives', 'gt_positives')
-PAIR_LOSS_SLOTS = 64          # partial sums of gpe_pair_loss_fwd: part of the result's bits, so a constant and not a device property
-
-
-def _pair_labels(labels, M):
-    """-> (flat labels as the kernel reads them, kind): bool as a uint8 view, uint8 and fp32 as they are, anything else cast once"""
-    if labels.numel() != M:
-        raise ValueError('pair_class_loss: %d labels for %d logits' % (labels.numel(), M))
-    y = labels.reshape(-1)
-    if y.dtype == torch.bool:
-        return y.contiguous().view(torch.uint8), 0
-    if y.dtype == torch.uint8:
-        return y.contiguous(), 0
-    return (y if y.dtype == F32 else y.to(F32)).contiguous(), 1
-
-
-class PairClassLossFn(torch.autograd.Function):
-    """ComposedLoss (nn/metrics/composed_loss.py:83-126) on the logits of a batch of pair rows: BCEWithLogitsLoss and the counters
-    behind edge_pair_class_acc / stitch_precision / stitch_recall in one forward launch, the gradient in one backward launch, no
-    host read.  Returns (out [4] fp32 in the order of PAIR_LOSS_METRICS, counts [5] int32 in the order of PAIR_LOSS_COUNTS); only
-    out[0] carries gradient.  Nothing the backward reads is overwritten: a second backward over the same graph gives the same."""
-
-    @staticmethod
-    def forward(ctx, logits, labels):
-        _dev_check(logits)
-        if not labels.is_cuda:
-            raise RuntimeError('gpe ops need tensors on the MI355X (got %s labels); there is no CPU path' % labels.device)
-        dev = logits.device
-        x = logits.reshape(-1).contiguous()
-        M = x.numel()
-        y, kind = _pair_labels(labels, M)
-        part = torch.empty(PAIR_LOSS_SLOTS * 4, device=dev, dtype=torch.int64)
-        out = torch.empty(4, device=dev, dtype=F32)
-        counts = torch.empty(5, device=dev, dtype=torch.int32)
-        L.call('gpe_pair_loss_fwd', x, y, kind, M, PAIR_LOSS_SLOTS, part, _ticket(dev), out, counts)
-        ctx.rows = (x, y, kind, M)
-        ctx.shape = logits.shape
-        ctx.mark_non_differentiable(counts)
-        return out, counts
-
-    @staticmethod
-    def backward(ctx, g, _g_counts):
-        x, y, kind, M = ctx.rows
-        gx = torch.empty(M, device=x.device, dtype=F32)
-        # g[0] is the upstream gradient of the loss (a device scalar: no host sync); the ratios carry none
-        L.call('gpe_pair_loss_bwd', x, y, kind, M, g.contiguous(), gx)
-        return gx.view(ctx.shape), None
-
-
-def pair_class_loss(logits, labels, return_counts=False):
-    """-> out [4] = (edge_pair_class_loss, edge_pair_class_acc, stitch_precision, stitch_recall) of fp32 device logits against
-    labels of the same number of elements (bool / uint8 / fp32 read in place, other types cast once on the device); a ratio with
-    an empty denominator is 0.  return_counts: -> (out, counts [5] int32 = rows, correct, true positives, predicted positives,
-    ground-truth positives)."""
-    out, counts = PairClassLossFn.apply(logits, labels)
-    return (out, counts) if return_counts else out
-
-
-STITCH_SAMPLE_MAX_EDGES, STITCH_SAMPLE_MAX_ROWS = 512, 4096     # P * L and rows per garment of csrc/gpe_stitch_sample.hip
-
-
-def _int_tensor(t, shape, name, dev):
-    if (not torch.is_tensor(t) or tuple(t.shape) != shape or t.is_floating_point() or t.is_complex() or t.dtype == torch.bool
-            or t.device != dev):
-        raise ValueError('%s must be an integer %s tensor on the device of edges3d' % (name, list(shape)))
-
-
-def _int32(t, lo, hi):
-    """an integer tensor as the kernels read it: int32 as it is (they clamp themselves), wider ones brought into range first"""
-    t = t.detach()
-    if t.dtype != torch.int32:
-        t = t.to(torch.int64).clamp(lo, hi).to(torch.int32)
-    return t.contiguous()
-
-
-def stitch_sample_resident(edges3d, num_edges, gt_stitches, gt_num_stitches):
-    """the resident set of stitch_pairs_sample, checked, with wider integer tensors brought into int32 once:
-    edges3d [G, P, L, Fe] fp32, num_edges [G, P], gt_stitches [G, 2, S] (edge ids panel * L + edge), gt_num_stitches [G]"""
-    if not torch.is_tensor(edges3d) or edges3d.dim() != 4:
-        raise ValueError('edges3d must be [G, P, L, Fe] (got %s)' % (tuple(getattr(edges3d, 'shape', ())),))
-    G, P, Lm, Fe = edges3d.shape
-    if G < 1 or P < 1 or Lm < 1 or P * Lm > STITCH_SAMPLE_MAX_EDGES or not 1 <= Fe <= 16:
-        raise ValueError('stitch_pairs_sample handles garments of 1 .. %d edge slots of 1 .. 16 features (got G = %d, P = %d, L = %d, '
-                         'Fe = %d)' % (STITCH_SAMPLE_MAX_EDGES, G, P, Lm, Fe))
-    dev = edges3d.device
-    _int_tensor(num_edges, (G, P), 'num_edges', dev)
-    if not torch.is_tensor(gt_stitches) or gt_stitches.dim() != 3:
-        raise ValueError('gt_stitches must be an integer [G, 2, S] tensor of edge ids panel * L + edge on the device of edges3d')
-    S = gt_stitches.shape[2]
-    _int_tensor(gt_stitches, (G, 2, S), 'gt_stitches', dev)
-    _int_tensor(gt_num_stitches, (G,), 'gt_num_stitches', dev)
-    _dev_check(edges3d)
-    return (edges3d.detach().contiguous(), _int32(num_edges, 0, Lm), _int32(gt_stitches, -1, P * Lm), _int32(gt_num_stitches, 0, S))
-
-
-def stitch_sample_state(seed, draw, device):
-    """{seed, draw} of stitch_pairs_sample as an int64 [2] device tensor (the bit patterns of two unsigned 64-bit numbers)"""
-    signed = [v - (1 << 64) if v >= 1 << 63 else v for v in (int(seed) % (1 << 64), int(draw) % (1 << 64))]
-    return torch.tensor(signed, dtype=torch.int64).to(device)
-
-
-def stitch_pairs_sample(edges3d, num_edges, gt_stitches, gt_num_stitches, index, n_stitched, n_non_stitched, f_shift, f_scale,
-                        state, ticket, shuffle_pairs=True, shuffle_pairs_order=True):
-    """Training pair rows of B garments drawn on the device: what NNSewingPattern.stitches_as_3D_pairs(n_stitched, n_non_stitched,
-    shuffle_pairs, shuffle_pairs_order) (nn/data/pattern_converter.py:321-409) followed by FeatureStandartization gives per garment,
-    in one launch of csrc/gpe_stitch_sample.hip and with no host read (semantics and random numbers: include/gpe_hip.h).
-
-    The resident set as stitch_sample_resident takes it; index integer [B]: the garment of every batch slot; f_shift / f_scale: 2 Fe
-    numbers; state int64 [2] = {seed, draw} on the device (stitch_sample_state), advanced by the launch; ticket: one zeroed int32 of
-    the caller's, left zero.  -> rows fp32 [B, R, 2 Fe] (R = n_stitched + n_non_stitched), labels bool [B, R] (a view of the bytes
-    ops.pair_class_loss reads in place), status int32 [B] (>= 0 rows that gave up, -1 more valid stitches than n_stitched, -2 index
-    outside 0 .. G - 1; such a slot is all zeros)."""
-    edges, ne, gt, nums = stitch_sample_resident(edges3d, num_edges, gt_stitches, gt_num_stitches)
-    G, P, Lm, Fe = edges.shape
-    dev = edges.device
-    n_stitched, n_non_stitched = int(n_stitched), int(n_non_stitched)
-    R = n_stitched + n_non_stitched
-    if n_stitched < 0 or n_non_stitched < 0 or not 1 <= R <= STITCH_SAMPLE_MAX_ROWS:
-        raise ValueError('stitch_pairs_sample draws 1 .. %d rows per garment (got %d + %d)' % (STITCH_SAMPLE_MAX_ROWS, n_stitched, n_non_stitched))
-    if len(f_shift) != 2 * Fe or len(f_scale) != 2 * Fe:
-        raise ValueError('the statistics have %d / %d numbers, the pair rows %d features' % (len(f_shift), len(f_scale), 2 * Fe))
-    if shuffle_pairs and Fe != 8:
-        raise ValueError('shuffle_pairs reverses edges of the layout [start xyz | end xyz | cx cy]: Fe must be 8 (got %d)' % Fe)
-    if not torch.is_tensor(index) or index.dim() != 1 or index.numel() < 1:
-        raise ValueError('index must be an integer [B] tensor, B >= 1')
-    B = index.numel()
-    _int_tensor(index, (B,), 'index', dev)
-    if (not torch.is_tensor(state) or state.dtype != torch.int64 or tuple(state.shape) != (2,) or state.device != dev
-            or not state.is_contiguous()):
-        raise ValueError('state must be a contiguous int64 [2] tensor {seed, draw} on the device of edges3d')
-    if not torch.is_tensor(ticket) or ticket.dtype != torch.int32 or ticket.numel() != 1 or ticket.device != dev:
-        raise ValueError('ticket must be one zeroed int32 on the device of edges3d')
-    import ctypes
-    sh = (ctypes.c_float * (2 * Fe))(*[float(v) for v in f_shift])
-    sc = (ctypes.c_float * (2 * Fe))(*[float(v) for v in f_scale])
-    rows = torch.empty(B, R, 2 * Fe, device=dev, dtype=F32)
-    labels = torch.empty(B, R, device=dev, dtype=torch.uint8)
-    status = torch.empty(B, device=dev, dtype=torch.int32)
-    L.call('gpe_stitch_sample', edges, ne, gt if gt.numel() else None, nums, G, P, Lm, Fe, gt.shape[2], _int32(index, -1, G), B,
-           n_stitched, n_non_stitched, (1 if shuffle_pairs else 0) | (2 if shuffle_pairs_order else 0), sh, sc, state, ticket, rows,
-           labels, status)
-    return rows, labels.view(torch.bool), status
-
-
-class MeshResident:
-    """the meshes of a data set as mesh_points_sample reads them (built by mesh_resident), ragged over G garments: verts4 fp32
-    [sum V, 4] = {x, y, z, the bits of the int32 class id}, faces int32 [sum F, 3] (indices local to the garment), vert_off / face_off
-    int32 [G + 1], face_cdf int32 [sum F] holding the uint32 thresholds of the face choice; has_unlabelled: some vertex carries -1"""
-
-    def __init__(self, verts4, faces, vert_off, face_off, face_cdf, has_unlabelled):
-        self.verts4, self.faces, self.vert_off, self.face_off, self.face_cdf = verts4, faces, vert_off, face_off, face_cdf
-        self.G = vert_off.numel() - 1
-        self.has_unlabelled = bool(has_unlabelled)
-        self.device = verts4.device
-
-    @property
-    def verts(self):
-        return self.verts4[:, :3]
-
-    @property
-    def vert_label(self):
-        return self.verts4.view(torch.int32)[:, 3]
-
-
-def mesh_face_thresholds(verts, faces):
-    """the integer thresholds of the area-proportional face choice of one garment (verts fp32 [V, 3], faces int [F, 3]) -> uint32
-    [F]: T[f] = floor(2^31 C_f / C_total), C the sequential float64 cumulative sum of area = 0.5 |(B - A) x (C - A)| from the fp32
-    vertices, and T[f] = 2^31 exactly from the last face of positive area onwards; all zeros for a garment without such a face"""
-    v = np.asarray(verts, dtype=np.float32).astype(np.float64)
-    f = np.asarray(faces, dtype=np.int64)
-    a, e1, e2 = v[f[:, 0]], v[f[:, 1]] - v[f[:, 0]], v[f[:, 2]] - v[f[:, 0]]
-    cx = e1[:, 1] * e2[:, 2] - e1[:, 2] * e2[:, 1]
-    cy = e1[:, 2] * e2[:, 0] - e1[:, 0] * e2[:, 2]
-    cz = e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0]
-    area = 0.5 * np.sqrt(cx * cx + cy * cy + cz * cz)
-    cum = np.cumsum(area)
-    out = np.zeros(len(f), dtype=np.uint32)
-    positive = np.nonzero(area > 0)[0]
-    if len(positive):
-        out[:] = np.floor(2.0 ** 31 * (cum / cum[-1])).astype(np.uint32)
-        out[positive[-1]:] = 1 << 31
-    return out
-
-
-def mesh_resident(meshes, device='cuda'):
-    """Packs the meshes of a data set for mesh_points_sample (setup, not per step): meshes is a list of (verts [V, 3] float, faces
-    [F, 3] integer with indices into that garment's vertices, labels [V] integer: the class id of every vertex as the caller's
-    PanelClasses map gives it, -1 for a `stitch` / `None` vertex) as arrays or CPU tensors -> MeshResident on `device`.  A face index
-    outside 0 .. V - 1, a label below -1 and a coordinate that is not finite are ValueErrors."""
-    if isinstance(meshes, MeshResident):
-        return meshes
-    meshes = list(meshes)
-    if not meshes:
-        raise ValueError('mesh_resident needs at least one mesh')
-    v4, fs, cdf, voff, foff = [], [], [], [0], [0]
-    for g, mesh in enumerate(meshes):
-        if len(mesh) != 3:
-            raise ValueError('mesh %d must be (verts, faces, labels)' % g)
-        as_np = lambda t: t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
-        verts, faces, labels = [as_np(t) for t in mesh]
-        if verts.ndim != 2 or verts.shape[1] != 3 or verts.dtype.kind != 'f':
-            raise ValueError('mesh %d: verts must be a float [V, 3] array (got %s %s)' % (g, verts.dtype, verts.shape))
-        V = verts.shape[0]
-        if faces.ndim != 2 or faces.shape[1] != 3 or faces.dtype.kind not in 'iu':
-            raise ValueError('mesh %d: faces must be an integer [F, 3] array (got %s %s)' % (g, faces.dtype, faces.shape))
-        if labels.shape != (V,) or labels.dtype.kind not in 'iu':
-            raise ValueError('mesh %d: labels must be an integer [%d] array (got %s %s)' % (g, V, labels.dtype, labels.shape))
-        verts = verts.astype(np.float32)
-        if not np.isfinite(verts).all():
-            raise ValueError('mesh %d has a vertex coordinate that is not finite' % g)
-        faces, labels = faces.astype(np.int64), labels.astype(np.int64)
-        if faces.size and (faces.min() < 0 or faces.max() >= V):
-            raise ValueError('mesh %d: a face names vertex %d, outside 0 .. %d' % (g, faces.min() if faces.min() < 0 else faces.max(), V - 1))
-        if labels.size and (labels.min() < -1 or labels.max() >= 1 << 31):
-            raise ValueError('mesh %d: labels are class ids >= 0, or -1 for a stitch / None vertex' % g)
-        packed = np.empty((V, 4), dtype=np.float32)
-        packed[:, :3] = verts
-        packed.view(np.int32)[:, 3] = labels
-        v4.append(packed)
-        fs.append(faces.astype(np.int32))
-        cdf.append(mesh_face_thresholds(verts, faces))
-        voff.append(voff[-1] + V)
-        foff.append(foff[-1] + faces.shape[0])
-    if voff[-1] >= 1 << 31 or foff[-1] >= 1 << 31:
-        raise ValueError('the resident set holds %d vertices and %d faces: the offsets are int32' % (voff[-1], foff[-1]))
-    v4 = np.concatenate(v4)
-    to = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
-    return MeshResident(to(v4), to(np.concatenate(fs).reshape(-1, 3)), to(np.asarray(voff, dtype=np.int32)),
-                        to(np.asarray(foff, dtype=np.int32)), to(np.concatenate(cdf).view(np.int32)),
-                        bool((v4[:, 3].view(np.int32) < 0).any()))
-
-
-MESH_SAMPLE_MAX_POINTS, MESH_SAMPLE_MAX_BATCH = (1 << 28) - 1, (1 << 24) - 1    # the counter fields of csrc/gpe_mesh_sample.hip
-
-
-def mesh_points_buffers(resident, B, N):
-    """the outputs and the workspace of mesh_points_sample for B garments of N points: (features, segmentation, status, ws or None).
-    A caller that draws many batches into one place (the statistics fit) allocates them once and passes `out=`; the leading slices
-    [t[:b] for t in ...] serve a smaller last batch."""
-    dev = resident.device
-    return (torch.empty(B, N, 3, device=dev, dtype=F32), torch.empty(B, N, device=dev, dtype=torch.int64),
-            torch.empty(B, device=dev, dtype=torch.int32),
-            torch.empty(B, N, 4, device=dev, dtype=F32) if resident.has_unlabelled else None)
-
-
-def mesh_points_sample(resident, index, mesh_samples, state, ticket, point_noise_w=0.0, f_shift=None, f_scale=None, out=None):
-    """The input point clouds of B garments and their segmentation labels drawn on the device: what
-    Garment3DPatternFullDataset._get_sample_info (nn/data/datasets.py: _sample_points, _point_classes_from_mesh,
-    FeatureStandartization) gives per garment, in at most two launches of csrc/gpe_mesh_sample.hip and with no host read (semantics
-    and random numbers: include/gpe_hip.h).
-
-    resident: mesh_resident(...) on the device; index integer [B]: the garment of every batch slot; f_shift / f_scale: 3 numbers
-    each or both None; state int64 [2] = {seed, draw} on the device (stitch_sample_state), advanced by the call; ticket: one zeroed
-    int32 of the caller's, left zero; out: mesh_points_buffers(resident, B, N) to draw into instead of new tensors.
-    -> features fp32 [B, N, 3] (N = mesh_samples), segmentation int64 [B, N], status int32 [B]
-    (>= 0 points that fell back to label 0 for want of a labelled point in their cloud, -1 a garment without a face of positive
-    area, -2 index outside 0 .. G - 1; such a slot is all zeros)."""
-    if not isinstance(resident, MeshResident):
-        raise ValueError('resident must come from ops.mesh_resident (got %s)' % type(resident).__name__)
-    dev = resident.device
-    N = int(mesh_samples)
-    if not 1 <= N <= MESH_SAMPLE_MAX_POINTS:
-        raise ValueError('mesh_points_sample draws 1 .. 2^28 - 1 points per garment (got %d)' % N)
-    if (f_shift is None) != (f_scale is None) or (f_shift is not None and (len(f_shift) != 3 or len(f_scale) != 3)):
-        raise ValueError('the statistics are 3 shifts and 3 scales, or neither')
-    if not torch.is_tensor(index) or index.dim() != 1 or not 1 <= index.numel() <= MESH_SAMPLE_MAX_BATCH:
-        raise ValueError('index must be an integer [B] tensor, 1 <= B < 2^24')
-    B = index.numel()
-    if B * ((N + 511) // 512) >= 1 << 31:
-        raise ValueError('B * ceil(N / 512) must stay below 2^31 (got B = %d, N = %d)' % (B, N))
-    if index.is_floating_point() or index.is_complex() or index.dtype == torch.bool or index.device != dev:
-        raise ValueError('index must be an integer [%d] tensor on the device of the resident set' % B)
-    if (not torch.is_tensor(state) or state.dtype != torch.int64 or tuple(state.shape) != (2,) or state.device != dev
-            or not state.is_contiguous()):
-        raise ValueError('state must be a contiguous int64 [2] tensor {seed, draw} on the device of the resident set')
-    if not torch.is_tensor(ticket) or ticket.dtype != torch.int32 or ticket.numel() != 1 or ticket.device != dev:
-        raise ValueError('ticket must be one zeroed int32 on the device of the resident set')
-    _dev_check(resident.verts4)
-    import ctypes
-    sh = (ctypes.c_float * 3)(*[float(v) for v in f_shift]) if f_shift is not None else None
-    sc = (ctypes.c_float * 3)(*[float(v) for v in f_scale]) if f_scale is not None else None
-    features, seg, status, ws = out if out is not None else mesh_points_buffers(resident, B, N)
-    if out is not None and (
-            features.shape != (B, N, 3) or features.dtype != F32 or seg.shape != (B, N) or seg.dtype != torch.int64
-            or status.shape != (B,) or status.dtype != torch.int32 or (ws is None) != (not resident.has_unlabelled)
-            or (ws is not None and (ws.shape != (B, N, 4) or ws.dtype != F32))
-            or any(t.device != dev or not t.is_contiguous() for t in out if t is not None)):
-        raise ValueError('out must be mesh_points_buffers(resident, %d, %d) (or leading slices of a larger set)' % (B, N))
-    L.call('gpe_mesh_points_sample', resident.verts4, resident.faces, resident.vert_off, resident.face_off, resident.face_cdf,
-           resident.G, _int32(index, -1, resident.G), B, N, float(point_noise_w), sh, sc, 1 if resident.has_unlabelled else 0, ws,
-           state, ticket, features, seg, status)
-    return features, seg, status
-
-
-def stitch_renumber(stitches, nums, P, Lp, perm=None, lead=None, num_edges=None):
-    """composed_loss.py:592-620 (`perm`: the panel-order permutation) and :727-755 (`lead` / `num_edges`: the panel-origin
-    shift) applied to the ground-truth stitches [B,2,S] int64 -> a new tensor."""
-    B, _, S = stitches.shape
-    out = torch.empty_like(stitches)
-    L.call('gpe_stitch_renumber', stitches, nums, B, S, P, Lp, perm, lead, num_edges, out)
-    return out
-
-
-def panel_shift(feat, lead, num_edges):
-    """composed_loss.py:705-725 `_per_panel_shift` on per-edge ground truth [B,P,L] or [B,P,L,D] (fp32) -> a new tensor."""
-    _dev_check(feat)
-    feat = feat.contiguous()
-    Lp = feat.shape[2]
-    D = feat.shape[3] if feat.dim() == 4 else 1
-    out = torch.empty_like(feat)
-    L.call('gpe_panel_shift', feat, D, lead, num_edges, feat.shape[0] * feat.shape[1], Lp, out)
-    return out
-
-
-def origin_match(outlines, gt_ol, num_edges):
-    """composed_loss.py:656-703 `_batch_edge_order_match`: -> (gt outlines with every panel's edge loop shifted to the
-    origin that best matches the prediction, leading edge per panel int32 [B*P])."""
-    _dev_check(outlines)
-    B, P, Lp, D = gt_ol.shape
-    sb, sp, sl = _view_strides(outlines)
-    out = torch.empty_like(gt_ol)
-    lead = torch.empty(B * P, device=gt_ol.device, dtype=torch.int32)
-    L.call('gpe_origin_match', outlines.detach(), sb, sp, sl, gt_ol, D, num_edges, B, P, Lp, out, lead)
-    return out, lead
-
-
-def order_match(pred_feat, gt_feat):
-    """composed_loss.py:530-570 `_panel_order_match` (the greedy assignment): -> int64 [B, P] permutation of GT panels,
-    and a device flag that is non-zero if the matching left a finite distance behind (the reference raises then)."""
-    _dev_check(pred_feat)
-    B, P, D = pred_feat.shape
-    perm = torch.empty(B, P, device=pred_feat.device, dtype=torch.int64)
-    fail = torch.zeros(1, device=pred_feat.device, dtype=torch.int32)
-    L.call('gpe_order_match', pred_feat.contiguous(), gt_feat.contiguous(), B, P, D, perm, fail)
-    return perm, fail
-
-
-QM_DISCRETE, QM_SHAPE, QM_ROT, QM_TR, QM_STITCH, QM_FREE, QM_TAG_STATS = 1, 2, 4, 8, 16, 32, 64
-QUALITY_KEYS = ('num_panels_accuracy', 'num_edges_accuracy', 'corr_num_edges_accuracy', 'panel_shape_l2',
-                'corr_panel_shape_l2', 'rotation_l2', 'corr_rotation_l2', 'translation_l2', 'corr_translation_l2',
-                'stitch_precision', 'stitch_recall', 'corr_stitch_precision', 'corr_stitch_recall', 'free_edge_acc')
-QUALITY_WS_DOUBLES = 16          # include/gpe_hip.h: `part` holds B * 16 doubles
-
-
-def quality_stats(ol_stats, rot_stats=None, tr_stats=None, tag_stats=None):
-    """The 72-float host array `stats_host` of the quality entry points (include/gpe_hip.h), from the {'shift', 'scale'} stats
-    of the outlines / rotations / translations / stitch tags.  The pad vector, its isclose tolerance and the loop-closure
-    threshold are formed with torch fp32 arithmetic, as nn/metrics/metrics.py:107-109 and torch.isclose form them."""
-    import ctypes
-    v = [0.0] * 72
-    sh = torch.tensor(ol_stats['shift'], dtype=F32)
-    sc = torch.tensor(ol_stats['scale'], dtype=F32)
-    pad = -sh / sc
-    tol = 0.07 + (1e-5 * pad).abs()                 # torch.isclose(atol=0.07, rtol=1e-5) against the pad vector
-    thr = torch.tensor([3, 3]) / sc[:2]             # 3 cm per coordinate
-    v[0:4], v[4:8], v[8:12], v[12:16], v[16:18] = sh.tolist(), sc.tolist(), pad.tolist(), tol.tolist(), thr.tolist()
-    for base, st in ((24, rot_stats), (40, tr_stats), (56, tag_stats)):
-        if st is not None:
-            s_, c_ = [float(x) for x in st['shift']], [float(x) for x in st['scale']]
-            if len(s_) > 8:
-                raise ValueError('quality metrics support feature widths <= 8 (got %d)' % len(s_))
-            v[base:base + len(s_)], v[base + 8:base + 8 + len(c_)] = s_, c_
-    return (ctypes.c_float * 72)(*v)
-
-
-def quality_metrics(flags, stats, B, P, Lp, outlines=None, gt_outlines=None, num_edges=None, num_panels=None, rotations=None,
-                    gt_rotations=None, translations=None, gt_translations=None, stitch_tags=None, free_logits=None,
-                    stitches=None, nums=None, gt_free_mask=None, part=None):
-    """ComposedPatternLoss quality metrics (nn/metrics/composed_loss.py:365-424) in <= 3 launches, no host read:
-    -> (out fp32 [14] in the order of QUALITY_KEYS, counts int32 [4]: contributors of the corr_ slots, include/gpe_hip.h).
-    `flags` selects the components (QM_*), `stats` is quality_stats(...).  Predictions are the strided views of the decoders'
-    outputs; ground truth is what the loss matched (order / origin), any dtype (converted on the device).
-    `part`: a caller-owned workspace for the per-pattern records, fp64 [B, 16] — B rows of a larger table that quality_pool folds
-    later with the same flags; the default is a private one."""
-    ref = outlines if outlines is not None else free_logits
-    _dev_check(ref)
-    dev = ref.device
-    if part is None:
-        part = torch.empty(B * QUALITY_WS_DOUBLES, device=dev, dtype=torch.float64)
-    else:
-        _quality_table(part, 'quality_metrics: part', B)
-        if part.device != dev:
-            raise ValueError('quality_metrics: part lives on %s, the predictions on %s' % (part.device, dev))
-    out = torch.empty(len(QUALITY_KEYS), device=dev, dtype=F32)
-    counts = torch.empty(4, device=dev, dtype=torch.int32)
-    main = flags & (QM_DISCRETE | QM_SHAPE | QM_ROT | QM_TR)
-    if main:
-        need_ol = flags & (QM_DISCRETE | QM_SHAPE)
-        ol = outlines.detach() if need_ol else None
-        sb, sp, sl = _view_strides(ol) if need_ol else (0, 0, 0)
-        gto = gt_outlines.float().contiguous() if flags & QM_SHAPE else None
-        ne = num_edges.reshape(-1).to(torch.int32).contiguous() if need_ol else None
-        npn = num_panels.reshape(-1).to(torch.int32).contiguous() if flags & QM_DISCRETE else None
-        rot = rotations.detach() if flags & QM_ROT else None
-        tr = translations.detach() if flags & QM_TR else None
-        R = rot.shape[-1] if rot is not None else 0
-        T = tr.shape[-1] if tr is not None else 0
-        for t in (ol, rot, tr):
-            if t is not None:
-                _dev_check(t)
-        L.call('gpe_quality_panels', ol, sb, sp, sl, gto, ne, npn,
-               rot, _row_stride(rot, P) if rot is not None else 0,
-               gt_rotations.float().contiguous() if rot is not None else None, R,
-               tr, _row_stride(tr, P) if tr is not None else 0,
-               gt_translations.float().contiguous() if tr is not None else None, T,
-               B, P, Lp, main, stats, part)
-    st_flags = flags & (QM_STITCH | QM_FREE | QM_TAG_STATS)
-    if st_flags & (QM_STITCH | QM_FREE):
-        lg = free_logits.detach()
-        _dev_check(lg)
-        tags = stitch_tags.detach() if flags & QM_STITCH else None
-        if tags is not None:
-            _dev_check(tags)
-        ts = _view_strides(tags) if tags is not None else (0, 0, 0)
-        L.call('gpe_quality_stitches', tags, ts[0], ts[1], ts[2], tags.shape[3] if tags is not None else 0,
-               lg, lg.stride(0), lg.stride(1), lg.stride(2),
-               stitches.long().contiguous() if tags is not None else None,
-               nums.reshape(-1).long().contiguous() if tags is not None else None,
-               stitches.shape[-1] if tags is not None else 0,
-               gt_free_mask.float().contiguous() if flags & QM_FREE else None, B, P, Lp, st_flags, stats, part)
-    L.call('gpe_quality_finalize', part, B, P, Lp, flags, out, counts)
-    return out, counts
-
-
-def _quality_table(t, what, rows=None):
-    if (not torch.is_tensor(t) or t.dtype != torch.float64 or t.dim() != 2 or t.shape[1] != QUALITY_WS_DOUBLES or t.shape[0] < 1
-            or not t.is_contiguous() or (rows is not None and t.shape[0] != rows)):
-        raise ValueError('%s must be a contiguous fp64 [%s, %d] tensor (got %s %s)'
-                         % (what, 'G' if rows is None else rows, QUALITY_WS_DOUBLES, getattr(t, 'dtype', type(t).__name__),
-                            tuple(getattr(t, 'shape', ()))))
-    if not t.is_cuda:
-        raise RuntimeError('gpe ops need tensors on the MI355X (got a %s table); there is no CPU path' % t.device)
-
-
-def quality_pool(table, group, n_groups, P, Lp, flags):
-    """The per-garment records of a whole data set (the `part` rows quality_metrics wrote, fp64 [G, 16]) folded per group and
-    overall: -> (out fp32 [n_groups + 1, 14], counts int32 [n_groups + 1, 4]).  Row g is bit for bit what quality_metrics returns
-    for the garments of group g alone, in table order, as one batch; the last row covers all garments.  group: int32 [G] on the
-    device (an id outside 0 .. n_groups-1 belongs to no group), or None with n_groups = 0.  One launch (include/gpe_hip_eval.h
-    gpe_eval_pool), no host read."""
-    _quality_table(table, 'quality_pool: table')
-    G = table.shape[0]
-    if isinstance(n_groups, bool) or not isinstance(n_groups, int) or not 0 <= n_groups <= 65535:
-        raise ValueError('quality_pool: n_groups must be an integer in 0 .. 65535 (got %r)' % (n_groups,))
-    if group is None:
-        if n_groups:
-            raise ValueError('quality_pool: %d groups need a group id per garment' % n_groups)
-    elif (not torch.is_tensor(group) or group.dtype != torch.int32 or tuple(group.shape) != (G,) or group.device != table.device
-          or not group.is_contiguous()):
-        raise ValueError('quality_pool: group must be a contiguous int32 [%d] tensor on the device of the table' % G)
-    out = torch.empty(n_groups + 1, len(QUALITY_KEYS), device=table.device, dtype=F32)
-    counts = torch.empty(n_groups + 1, 4, device=table.device, dtype=torch.int32)
-    L.call('gpe_eval_pool', table, group, G, n_groups, int(P), int(Lp), int(flags), out, counts)
-    return out, counts
-
-
-# QUALITY_KEYS index -> the contributor count (of the int32 [4] counts) that must be positive for the key to have a value; the other
-# keys always have one (corr_num_edges_accuracy included: the reference averages its 0 / 0 NaN in).  metrics._main_quality_metrics /
-# _stitch_quality_metrics apply these rules on the host, EvalAccumulator and Evaluator.pooled on the device / after the one read.
-QUALITY_GATES = {'corr_panel_shape_l2': 1, 'corr_rotation_l2': 0, 'corr_translation_l2': 0, 'corr_stitch_precision': 2,
-                 'corr_stitch_recall': 2}
-EVAL_MAX_KEYS, EVAL_MAX_SOURCES = 64, 4
-
-
-class EvalAccumulator:
-    """The reference's evaluation rule (nn/metrics/eval_utils.py:35-76: per key the mean of the per-batch values, a batch whose value is
-    None skipped) kept on the device: one launch per batch (include/gpe_hip_eval.h gpe_eval_add), ONE host read at the end.
-
-        acc = EvalAccumulator([('full_loss', 3, 0), ('pattern_loss', 0, 1), ('corr_rotation_l2', 2, 6)], {'corr_rotation_l2': 0})
-        for ...: acc.add(loss_vec, None, quality_vec, misc_vec, counts=counts)
-        result = acc.read()[0]             # {'full_loss': np.float32, ..., 'corr_rotation_l2': np.float32 or None}
-
-    keys: (name, source, index) per key, in the order of the result dict: the value of `name` in a batch is sources[source][index].
-    gates: {name: j} — the key is counted in a batch iff counts[j] > 0 (counts: quality_metrics' int32 [4]); other keys always.
-    slots: rows of accumulators (one per data folder); `.slot` is the device word that names the row the next add() goes to, set by
-    set_slot(i) as a queued copy — a captured add() serves every row."""
-
-    def __init__(self, keys, gates=None, slots=1, device='cuda'):
-        import ctypes
-        keys, gates = [tuple(k) for k in keys], dict(gates or {})
-        if not 1 <= len(keys) <= EVAL_MAX_KEYS:
-            raise ValueError('EvalAccumulator: 1 .. %d keys (got %d)' % (EVAL_MAX_KEYS, len(keys)))
-        if isinstance(slots, bool) or not isinstance(slots, int) or slots < 1:
-            raise ValueError('EvalAccumulator: slots must be a positive integer (got %r)' % (slots,))
-        names = [k[0] for k in keys]
-        if len(set(names)) != len(names) or set(gates) - set(names):
-            raise ValueError('EvalAccumulator: key names must be distinct and every gate must name a key')
-        packed = []
-        for name, src, idx in keys:
-            g = gates.get(name)
-            if not (0 <= src < EVAL_MAX_SOURCES and 0 <= idx < 256 and (g is None or 0 <= g < 4)):
-                raise ValueError('EvalAccumulator: key %r: source 0 .. 3, index 0 .. 255, gate 0 .. 3 (got %r, %r, %r)' % (name, src, idx, g))
-            packed.append(idx | (src << 8) | ((0 if g is None else g + 1) << 16))
-        self.device = torch.device(device)
-        if self.device.type != 'cuda':
-            raise RuntimeError('gpe ops need tensors on the MI355X (got device %s); there is no CPU path' % self.device)
-        self.keys, self.names, self.gated, self.slots = keys, names, bool(gates), slots
-        self.n_sources = 1 + max(k[1] for k in keys)
-        self._need = [1 + max([k[2] for k in keys if k[1] == s], default=-1) for s in range(self.n_sources)]
-        self._packed = (ctypes.c_int32 * len(packed))(*packed)
-        K = len(keys)
-        # one allocation, one read: sum [slots, K] as its fp32 bits | cnt [slots, K] | batches [slots] | status [1]
-        self.state = torch.zeros(2 * slots * K + slots + 1, device=self.device, dtype=torch.int32)
-        self.sum = self.state[:slots * K].view(F32).view(slots, K)
-        self.cnt = self.state[slots * K:2 * slots * K].view(slots, K)
-        self.batches = self.state[2 * slots * K:2 * slots * K + slots]
-        self.status = self.state[-1:]
-        self.slot = torch.zeros(1, device=self.device, dtype=torch.int32)
-        self._slot_host = torch.arange(slots, dtype=torch.int32).pin_memory()      # sources of set_slot's queued one-word copies
-
-    def reset(self):
-        """sums, counts, batches and the status back to zero, the slot word to row 0 (queued; no device read)"""
-        self.state.zero_()
-        self.slot.zero_()
-
-    def set_slot(self, i):
-        """the following add() calls go to row i: a queued copy from pinned memory, no device read"""
-        if isinstance(i, bool) or not isinstance(i, int) or not 0 <= i < self.slots:
-            raise ValueError('EvalAccumulator.set_slot: row 0 .. %d (got %r)' % (self.slots - 1, i))
-        self.slot.copy_(self._slot_host[i:i + 1], non_blocking=True)
-
-    def add(self, *sources, counts=None):
-        """one batch: sources[s] is the fp32 device vector the keys of source s index (None where no key refers to it)"""
-        if len(sources) > EVAL_MAX_SOURCES or len(sources) < self.n_sources:
-            raise ValueError('EvalAccumulator.add: %d .. %d source vectors (got %d)' % (self.n_sources, EVAL_MAX_SOURCES, len(sources)))
-        args = []
-        for s in range(EVAL_MAX_SOURCES):
-            t = sources[s] if s < len(sources) else None
-            need = self._need[s] if s < self.n_sources else 0
-            if t is None:
-                if need:
-                    raise ValueError('EvalAccumulator.add: source %d is None but keys refer to it' % s)
-                args += [None, 0]
-                continue
-            if not torch.is_tensor(t) or t.dtype != F32 or t.dim() != 1 or not t.is_contiguous() or t.numel() < need or t.numel() > 256:
-                raise ValueError('EvalAccumulator.add: source %d must be a contiguous fp32 vector of %d .. 256 values (got %s %s)'
-                                 % (s, need, getattr(t, 'dtype', type(t).__name__), tuple(getattr(t, 'shape', ()))))
-            _dev_check(t)
-            args += [t.detach(), t.numel()]
-        if self.gated and counts is None:
-            raise ValueError('EvalAccumulator.add: gated keys need the contributor counts')
-        if counts is not None and (counts.dtype != torch.int32 or counts.numel() != 4 or not counts.is_contiguous() or not counts.is_cuda):
-            raise ValueError('EvalAccumulator.add: counts must be a contiguous int32 [4] device tensor')
-        L.call('gpe_eval_add', *args, len(sources), counts, self._packed, len(self.keys), self.sum, self.cnt, self.batches, self.slot,
-               self.slots, self.status)
-
-    def read(self, along=()):
-        """THE host read -> one dict per row: np.float32(sum) / np.float32(cnt) per key, None where the key was never counted (the
-        reference's None for an empty list).  `.last_sums` / `.last_counts` / `.last_batches` keep what was read.  along: further
-        device tensors of fp32 / int32 to bring over in the same transfer; `.last_along` holds them as numpy arrays of their own
-        dtype and shape, in order."""
-        along = [t.detach() for t in along]
-        if any(t.dtype not in (F32, torch.int32) or t.device != self.state.device for t in along):
-            raise ValueError('EvalAccumulator.read: along takes fp32 / int32 tensors on the accumulator\'s device')
-        parts = [self.state] + [t.contiguous().view(torch.int32).reshape(-1) for t in along]
-        host = (torch.cat(parts) if along else self.state).cpu().numpy()
-        edges = np.cumsum([p.numel() for p in parts])
-        self.last_along = [host[a:b].view(np.float32 if t.dtype == F32 else np.int32).reshape(tuple(t.shape))
-                           for a, b, t in zip(edges[:-1], edges[1:], along)]
-        return self.parse(host[:edges[0]])
-
-    def parse(self, host):
-        """read()'s result from `.state` as it arrived on the host (int32 numpy): for a caller that brought the state over in a
-        transfer of its own (evaluation.FrameworkEvaluator reads it along with the second stage's accumulator)"""
-        K, S = len(self.keys), self.slots
-        if host[-1]:
-            raise RuntimeError('EvalAccumulator: an add() met a slot word outside 0 .. %d and was dropped' % (S - 1))
-        sums = host[:S * K].view(np.float32).reshape(S, K)
-        cnts = host[S * K:2 * S * K].reshape(S, K)
-        self.last_sums, self.last_counts, self.last_batches = sums, cnts, host[2 * S * K:2 * S * K + S]
-        return [{n: (np.float32(sums[s, k]) / np.float32(cnts[s, k]) if cnts[s, k] else None) for k, n in enumerate(self.names)}
-                for s in range(S)]
-
-
-# -------------------------------------------------------------------------------------------------
-# a prediction decoded to a sewing pattern (csrc/gpe_pattern_decode.hip)
-# -------------------------------------------------------------------------------------------------
-PATTERN_DECODE_KEYS = ('num_edges', 'edge_slot', 'num_verts', 'closed', 'new_panel_id', 'num_panels', 'vertices', 'curvature',
-                       'rotations', 'translations', 'curved', 'stitches', 'num_stitches', 'stitch_flags', 'first_invalid')
-PATTERN_MAX_EDGES, PATTERN_MAX_WIDTH = 1024, 8          # include/gpe_hip.h gpe_pattern_decode: P * L, and R / T / D
-
-
-def _pattern_decode_stats(data_stats, widths, explicit_stitch_tags):
-    """the 64-double host array `stats_host` of gpe_pattern_decode from data_config['standardize'] (Python floats are doubles: the
-    statistics reach the kernel as the reference's numpy sees them)"""
-    import ctypes
-    v = [0.0] * 64
-    for base, key in ((0, 'outlines'), (16, 'rotations'), (32, 'translations'), (48, 'stitch_tags')):
-        if key == 'stitch_tags' and not explicit_stitch_tags:
-            continue
-        sh = [float(x) for x in data_stats['gt_shift'][key]]
-        sc = [float(x) for x in data_stats['gt_scale'][key]]
-        if len(sh) != widths[key] or len(sc) != widths[key]:
-            raise ValueError('pattern_decode: %d statistics for %r of width %d' % (len(sh), key, widths[key]))
-        v[base:base + len(sh)], v[base + 8:base + 8 + len(sc)] = sh, sc
-    return (ctypes.c_double * 64)(*v)
-
-
-def _edge_views(stitch_tags, free_edges_mask, name):
-    """checks of the tag / logit views shared by pattern_decode and tags_to_stitches -> (B, P, L, D)"""
-    _dev_check(stitch_tags)
-    _dev_check(free_edges_mask)
-    if stitch_tags.dim() != 4 or free_edges_mask.shape != stitch_tags.shape[:3]:
-        raise ValueError('%s: stitch_tags [B,P,L,D] and free_edges_mask [B,P,L] expected (got %s, %s)'
-                         % (name, tuple(stitch_tags.shape), tuple(free_edges_mask.shape)))
-    B, P, Lp, D = stitch_tags.shape
-    if not (1 <= P * Lp <= PATTERN_MAX_EDGES) or not (1 <= D <= PATTERN_MAX_WIDTH) or B < 1:
-        raise ValueError('%s: 1 <= P * L <= %d edge slots and a tag width of 1 .. %d are supported (got P = %d, L = %d, D = %d)'
-                         % (name, PATTERN_MAX_EDGES, PATTERN_MAX_WIDTH, P, Lp, D))
-    return B, P, Lp, D
-
-
-def tags_to_stitches(stitch_tags, free_edges_mask):
-    """Garment3DPatternFullDataset.tags_to_stitches (nn/data/datasets.py:917-968) for a batch, one launch, no host read:
-    stitch_tags [B,P,L,D] and the free-edge logits [B,P,L] (strided views are fine) -> (stitches int32 [B,2,S] of pattern-level
-    edge ids in the order the reference appends them, zero tails; num_stitches int32 [B]) with S = P * L // 2."""
-    B, P, Lp, D = _edge_views(stitch_tags, free_edges_mask, 'tags_to_stitches')
-    tags, lg = stitch_tags.detach(), free_edges_mask.detach()
-    dev = tags.device
-    S = P * Lp // 2
-    stitches = torch.empty(B, 2, S, device=dev, dtype=torch.int32)
-    nums = torch.empty(B, device=dev, dtype=torch.int32)
-    L.call('gpe_tags_to_stitches', tags, *_view_strides(tags), D, lg, lg.stride(0), lg.stride(1), lg.stride(2), B, P, Lp,
-           stitches if S else None, nums)
-    return stitches, nums
-
-
-def pattern_decode(preds, data_stats, explicit_stitch_tags=False, stitches=None, num_stitches=None):
-    """Garment3DPatternFullDataset._pred_to_pattern (nn/data/datasets.py:731-767) up to the pattern's numbers, for a batch, one launch,
-    no host read: un-standardise in fp64, drop padding rows and empty panels, walk the edge loops to vertices, pair the stitch tags
-    (or take `stitches` [B,2,S'] with optional `num_stitches` [B], any integer dtype, instead) and check every stitch against the
-    panels it names.  `preds` is a model's output dict (strided views are fine), `data_stats` is data_config['standardize'].
-    -> dict of device tensors, PATTERN_DECODE_KEYS (layouts: include/gpe_hip.h gpe_pattern_decode)."""
-    ol, rot, tr = preds['outlines'].detach(), preds['rotations'].detach(), preds['translations'].detach()
-    for t in (ol, rot, tr):
-        _dev_check(t)
-    if ol.dim() != 4 or ol.shape[3] != 4:
-        raise ValueError('pattern_decode: outlines [B,P,L,4] expected (got %s)' % (tuple(ol.shape),))
-    B, P, Lp = ol.shape[:3]
-    R, T = rot.shape[-1], tr.shape[-1]
-    if not (1 <= P * Lp <= PATTERN_MAX_EDGES) or not (1 <= R <= PATTERN_MAX_WIDTH) or not (1 <= T <= PATTERN_MAX_WIDTH) or B < 1:
-        raise ValueError('pattern_decode: 1 <= P * L <= %d edge slots and rotation / translation widths of 1 .. %d are supported '
-                         '(got P = %d, L = %d, R = %d, T = %d)' % (PATTERN_MAX_EDGES, PATTERN_MAX_WIDTH, P, Lp, R, T))
-    dev = ol.device
-    widths = {'outlines': 4, 'rotations': R, 'translations': T}
-    if stitches is None:
-        tags, lg = preds['stitch_tags'].detach(), preds['free_edges_mask'].detach()
-        if _edge_views(tags, lg, 'pattern_decode')[:3] != (B, P, Lp):
-            raise ValueError('pattern_decode: stitch_tags %s do not match outlines %s' % (tuple(tags.shape), tuple(ol.shape)))
-        widths['stitch_tags'] = tags.shape[3]
-        t_args = (tags, *_view_strides(tags), tags.shape[3], lg, lg.stride(0), lg.stride(1), lg.stride(2), None, None)
-        S = P * Lp // 2
-    else:
-        if not stitches.is_cuda:
-            raise RuntimeError('gpe ops need tensors on the MI355X (got %s stitches); there is no CPU path' % stitches.device)
-        if stitches.dim() != 3 or stitches.shape[0] != B or stitches.shape[1] != 2 or stitches.shape[2] < 1 or \
-                stitches.dtype.is_floating_point:
-            raise ValueError('pattern_decode: stitches of integer dtype [B,2,S >= 1] expected (got %s %s)'
-                             % (stitches.dtype, tuple(stitches.shape)))
-        S = stitches.shape[2]
-        given = stitches.to(torch.int32).contiguous()
-        nums = num_stitches.to(dev).reshape(B).to(torch.int32).contiguous() if num_stitches is not None else None
-        explicit_stitch_tags = False
-        t_args = (None, 0, 0, 0, 0, None, 0, 0, 0, given, nums)
-    stats = _pattern_decode_stats(data_stats, widths, explicit_stitch_tags)
-    i32 = lambda *shape: torch.empty(*shape, device=dev, dtype=torch.int32)                       # noqa: E731
-    f64 = lambda *shape: torch.empty(*shape, device=dev, dtype=torch.float64)                     # noqa: E731
-    o = {'num_edges': i32(B, P), 'edge_slot': i32(B, P, Lp), 'num_verts': i32(B, P), 'closed': i32(B, P), 'new_panel_id': i32(B, P),
-         'num_panels': i32(B), 'vertices': f64(B, P, Lp + 1, 2), 'curvature': f64(B, P, Lp, 2), 'rotations': f64(B, P, R),
-         'translations': f64(B, P, T), 'curved': i32(B, P, Lp), 'stitches': i32(B, 2, S), 'num_stitches': i32(B),
-         'stitch_flags': i32(B, S), 'first_invalid': i32(B)}
-    L.call('gpe_pattern_decode', ol, *_view_strides(ol), rot, _row_stride(rot, P), R, tr, _row_stride(tr, P), T, *t_args,
-           B, P, Lp, S, 1 if explicit_stitch_tags else 0, stats,
-           *[o[k] if o[k].numel() else None for k in PATTERN_DECODE_KEYS])
-    return o
-
-
-# the panels of a decoded prediction placed in 3D (csrc/gpe_pattern_place.hip)
-PATTERN_PLACE_KEYS = ('rot_matrix', 'translation', 'top_mid', 'vertices3d', 'edges3d', 'place_flags')
-PATTERN_PLACE_INPUTS = ('num_edges', 'num_verts', 'vertices', 'curvature', 'curved', 'rotations', 'translations')
-PLACE_BAD_QUAT = 1                                      # include/gpe_hip_place.h GPE_PLACE_BAD_QUAT
-
-
-def pattern_place(decoded):
-    """The step between the two prediction stages (NNSewingPattern._3D_edges_per_panel, nn/data/pattern_converter.py:517-552, and the
-    inverse of the universal translation, :281-288) for a batch, one launch, no host read: `decoded` is pattern_decode's dict (or
-    anything with its PATTERN_PLACE_INPUTS).  Per non-empty panel, in fp64: the rotation matrix of the normalised quaternion, the
-    bounding-box side midpoint that lies highest in 3D (`top_mid`), the translation of the panel's origin, the vertices in 3D, and
-    the compact fp32 edge rows `edges3d` [B,P,L,8] that stitch_pairs takes with `num_edges`.
-    -> dict of device tensors, PATTERN_PLACE_KEYS (layouts: include/gpe_hip_place.h gpe_pattern_place)."""
-    t = {k: decoded[k] for k in PATTERN_PLACE_INPUTS}
-    for v in t.values():
-        if not v.is_cuda:
-            raise RuntimeError('gpe ops need tensors on the MI355X (got a %s tensor); there is no CPU path' % v.device)
-    if t['curved'].dim() != 3:
-        raise ValueError('pattern_place: curved [B,P,L] expected (got %s)' % (tuple(t['curved'].shape),))
-    B, P, Lp = t['curved'].shape
-    if t['rotations'].shape[-1] != 4 or t['translations'].shape[-1] != 3:
-        raise ValueError('pattern_place: quaternions (rotation width 4) and 3D translations (width 3) are placed (got widths %d, %d)'
-                         % (t['rotations'].shape[-1], t['translations'].shape[-1]))
-    if not (1 <= P * Lp <= PATTERN_MAX_EDGES) or B < 1:
-        raise ValueError('pattern_place: 1 <= P * L <= %d edge slots are supported (got P = %d, L = %d)' % (PATTERN_MAX_EDGES, P, Lp))
-    shapes = {'num_edges': (B, P), 'num_verts': (B, P), 'vertices': (B, P, Lp + 1, 2), 'curvature': (B, P, Lp, 2),
-              'curved': (B, P, Lp), 'rotations': (B, P, 4), 'translations': (B, P, 3)}
-    for k, shape in shapes.items():
-        want = torch.int32 if k in ('num_edges', 'num_verts', 'curved') else F64
-        if tuple(t[k].shape) != shape or t[k].dtype != want:
-            raise ValueError('pattern_place: %s of %s %s expected (got %s %s)' % (k, want, shape, t[k].dtype, tuple(t[k].shape)))
-        t[k] = t[k].detach().contiguous()
-    dev = t['curved'].device
-    o = {'rot_matrix': torch.empty(B, P, 3, 3, device=dev, dtype=F64), 'translation': torch.empty(B, P, 3, device=dev, dtype=F64),
-         'top_mid': torch.empty(B, P, device=dev, dtype=torch.int32),
-         'vertices3d': torch.empty(B, P, Lp + 1, 3, device=dev, dtype=F64),
-         'edges3d': torch.empty(B, P, Lp, 8, device=dev, dtype=F32), 'place_flags': torch.empty(B, P, device=dev, dtype=torch.int32)}
-    L.call('gpe_pattern_place', *[t[k] for k in PATTERN_PLACE_INPUTS], B, P, Lp, *[o[k] for k in PATTERN_PLACE_KEYS])
-    return o
-
-
-# the edge-pair classifier scored on predicted patterns over a whole set (csrc/gpe_framework_eval.hip)
-FRAMEWORK_EVAL_KEYS = ('full_loss', 'edge_pair_class_loss', 'edge_pair_class_acc', 'stitch_precision', 'stitch_recall',
-                       'selected_precision', 'selected_recall')              # include/gpe_hip_framework.h, in the kernel's order
-FRAMEWORK_SKIP_REASONS = ('bad_rotation', 'no_stitches', 'no_pairs', 'wrong_panel_count')       # states 1, 2, 3; counted but not corr
-FRAMEWORK_SETS = ('stitch', 'stitch_corr')
-FRAMEWORK_RECORD = ('state', 'corr', 'loss_sum') + STITCH_EVAL_COUNTS + ('num_selected',)
-FRAMEWORK_TOTALS = STITCH_EVAL_COUNTS + ('num_selected', 'garments')
-FRAMEWORK_MAX_PANELS = 64
-
-
-class FrameworkAccumulator:
-    """Step 3 of the reference's on_test_set.py -st ... -corr kept on the device: which garments of a batch count
-    (GarmentStitchPairsDataset._clean_datapoint_list, nn/data/datasets.py:1134-1159), their per-garment values folded as
-    _eval_metrics_per_loader folds batches of one garment (nn/metrics/eval_utils.py:35-76), for all counted garments ('stitch') and
-    for those with the right number of panels ('stitch_corr').  One launch per batch (include/gpe_hip_framework.h
-    gpe_framework_eval_add), ONE host read at the end.  It mirrors EvalAccumulator:
-
-        acc = FrameworkAccumulator(slots=len(folders), total=garments, device='cuda')
-        for ...: acc.add(stitch_pairs_eval's dict, DecodedPatterns after place(), gt_num_panels)
-        totals, loss, ratios = acc.pool(groups, n_groups)        # device tensors, batch-independent
-        rows = acc.read()                                        # [{'stitch': {...}, 'stitch_corr': {...}, 'skipped': {...}}] per slot
-
-    `.table` fp64 [total, 10] keeps one record per garment in visiting order (FRAMEWORK_RECORD); `.rows` counts the garments seen."""
-
-    def __init__(self, slots=1, total=1, device='cuda'):
-        if isinstance(slots, bool) or not isinstance(slots, int) or slots < 1:
-            raise ValueError('FrameworkAccumulator: slots must be a positive integer (got %r)' % (slots,))
-        if isinstance(total, bool) or not isinstance(total, int) or not 1 <= total <= 0x7fffffff:
-            raise ValueError('FrameworkAccumulator: total must be the number of garments of the pass, 1 .. 2^31 - 1 (got %r)' % (total,))
-        self.device = torch.device(device)
-        if self.device.type != 'cuda':
-            raise RuntimeError('gpe ops need tensors on the MI355X (got device %s); there is no CPU path' % self.device)
-        K = len(FRAMEWORK_EVAL_KEYS)
-        self.slots, self.total, self.rows = slots, total, 0
-        # one allocation, one read: sum [2, slots, K] as its fp32 bits | cnt [2, slots] | skipped [slots, 4] | status [1]
-        self.state = torch.zeros(2 * slots * K + 2 * slots + 4 * slots + 1, device=self.device, dtype=torch.int32)
-        self.device = self.state.device                        # with its index: what the batches' tensors are compared with
-        a, b = 2 * slots * K, 2 * slots * K + 2 * slots
-        self.sum = self.state[:a].view(F32).view(2, slots, K)
-        self.cnt = self.state[a:b].view(2, slots)
-        self.skipped = self.state[b:b + 4 * slots].view(slots, 4)
-        self.status = self.state[-1:]
-        self.table = torch.zeros(total, len(FRAMEWORK_RECORD), device=self.device, dtype=F64)
-        self.slot = torch.zeros(1, device=self.device, dtype=torch.int32)
-        self._slot_host = torch.arange(slots, dtype=torch.int32).pin_memory()      # sources of set_slot's queued one-word copies
-
-    def reset(self):
-        """sums, counters, the table and the status back to zero, the slot word to row 0 (queued; no device read)"""
-        self.state.zero_()
-        self.table.zero_()
-        self.slot.zero_()
-        self.rows = 0
-
-    def set_slot(self, i):
-        """the following add() calls go to row i: a queued copy from pinned memory, no device read"""
-        if isinstance(i, bool) or not isinstance(i, int) or not 0 <= i < self.slots:
-            raise ValueError('FrameworkAccumulator.set_slot: row 0 .. %d (got %r)' % (self.slots - 1, i))
-        self.slot.copy_(self._slot_host[i:i + 1], non_blocking=True)
-
-    def add(self, eval_out, decoded, gt_num_panels, records=None):
-        """one batch: eval_out is stitch_pairs_eval's dict ('counts', 'loss_sum', 'num_stitches'), decoded the placed DecodedPatterns
-        (or a dict with 'num_stitches', 'first_invalid', 'num_panels', 'num_edges', 'place_flags'), gt_num_panels integer [B].
-        records: the fp64 [B, 10] rows to write instead of the next B rows of `.table` (a captured add() writes static rows)."""
-        get = (lambda k: getattr(decoded, k)) if not isinstance(decoded, dict) else decoded.__getitem__
-        try:
-            counts, loss_sum, n_sel = eval_out['counts'], eval_out['loss_sum'], eval_out['num_stitches']
-            dec = {k: get(k) for k in ('num_stitches', 'first_invalid', 'num_panels', 'num_edges', 'place_flags')}
-        except (KeyError, AttributeError) as e:
-            raise ValueError('FrameworkAccumulator.add: %s is missing (eval_out: ops.stitch_pairs_eval\'s dict; decoded: a placed '
-                             'DecodedPatterns)' % e)
-        if not torch.is_tensor(counts) or counts.dim() != 2 or counts.shape[1] != 6 or counts.dtype != torch.int32:
-            raise ValueError('FrameworkAccumulator.add: counts must be int32 [B, 6] (got %s %s)'
-                             % (getattr(counts, 'dtype', type(counts).__name__), tuple(getattr(counts, 'shape', ()))))
-        B = counts.shape[0]
-        ne = dec['num_edges']
-        if B < 1 or ne.dim() != 2 or ne.shape[0] != B or not 1 <= ne.shape[1] <= FRAMEWORK_MAX_PANELS:
-            raise ValueError('FrameworkAccumulator.add: num_edges [B = %d, 1 <= P <= %d] expected (got %s)'
-                             % (B, FRAMEWORK_MAX_PANELS, tuple(ne.shape)))
-        P = ne.shape[1]
-        if not torch.is_tensor(loss_sum) or loss_sum.dtype != F64 or tuple(loss_sum.shape) != (B,):
-            raise ValueError('FrameworkAccumulator.add: loss_sum must be fp64 [%d]' % B)
-        if not torch.is_tensor(gt_num_panels) or gt_num_panels.is_floating_point() or gt_num_panels.dtype == torch.bool \
-                or gt_num_panels.numel() != B:
-            raise ValueError('FrameworkAccumulator.add: gt_num_panels must be an integer [%d] tensor' % B)
-        shapes = {'num_selected': (B,), 'num_stitches': (B,), 'first_invalid': (B,), 'num_panels': (B,), 'num_edges': (B, P),
-                  'place_flags': (B, P)}
-        t = dict(dec, num_selected=n_sel)
-        for k, shape in shapes.items():
-            if not torch.is_tensor(t[k]) or t[k].dtype != torch.int32 or tuple(t[k].shape) != shape:
-                raise ValueError('FrameworkAccumulator.add: %s must be int32 %s (got %s %s)'
-                                 % (k, shape, getattr(t[k], 'dtype', type(t[k]).__name__), tuple(getattr(t[k], 'shape', ()))))
-        own = records is None
-        if own:
-            if self.rows + B > self.total:
-                raise ValueError('FrameworkAccumulator.add: more garments than the %d that total announced' % self.total)
-            records = self.table[self.rows:self.rows + B]
-        elif (not torch.is_tensor(records) or records.dtype != F64 or tuple(records.shape) != (B, len(FRAMEWORK_RECORD))
-              or not records.is_contiguous()):
-            raise ValueError('FrameworkAccumulator.add: records must be a contiguous fp64 [%d, %d] tensor' % (B, len(FRAMEWORK_RECORD)))
-        for v in [counts, loss_sum, gt_num_panels, records] + list(t.values()):
-            if v.device != self.device:
-                if not v.is_cuda:
-                    raise RuntimeError('gpe ops need tensors on the MI355X (got a %s tensor); there is no CPU path' % v.device)
-                raise ValueError('FrameworkAccumulator.add: a tensor lives on %s, the accumulator on %s' % (v.device, self.device))
-        gtp = gt_num_panels.detach().reshape(B).to(torch.int32).contiguous()
-        L.call('gpe_framework_eval_add', counts.contiguous(), loss_sum.contiguous(), t['num_selected'].contiguous(),
-               t['num_stitches'].contiguous(), t['first_invalid'].contiguous(), t['num_panels'].contiguous(), gtp,
-               t['num_edges'].contiguous(), t['place_flags'].contiguous(), B, P, self.sum, self.cnt, self.skipped, records, self.slot,
-               self.slots, self.status)
-        if own:
-            self.rows += B
-
-    def pool(self, groups=None, n_groups=0, table=None):
-        """the records of the garments seen so far (or `table`, fp64 [G, 10]) folded per group and overall, independent of the
-        batching: -> (totals int64 [n_groups + 1, 2, 8] FRAMEWORK_TOTALS, loss fp64 [n_groups + 1, 2], ratios fp32
-        [n_groups + 1, 2, 6] STITCH_EVAL_METRICS) on the device; axis 1 is FRAMEWORK_SETS.  groups: int32 [G] on the device (an id
-        outside 0 .. n_groups-1 belongs to no group), or None with n_groups = 0.  One launch, no host read."""
-        if table is None:
-            if self.rows < 1:
-                raise ValueError('FrameworkAccumulator.pool: no garment has been added')
-            table = self.table[:self.rows]
-        elif (not torch.is_tensor(table) or table.dtype != F64 or table.dim() != 2 or table.shape[1] != len(FRAMEWORK_RECORD)
-              or table.shape[0] < 1 or not table.is_contiguous()):
-            raise ValueError('FrameworkAccumulator.pool: table must be a contiguous fp64 [G, %d] tensor' % len(FRAMEWORK_RECORD))
-        G = table.shape[0]
-        if isinstance(n_groups, bool) or not isinstance(n_groups, int) or not 0 <= n_groups <= 65535:
-            raise ValueError('FrameworkAccumulator.pool: n_groups must be an integer in 0 .. 65535 (got %r)' % (n_groups,))
-        if groups is None:
-            if n_groups:
-                raise ValueError('FrameworkAccumulator.pool: %d groups need a group id per garment' % n_groups)
-        elif (not torch.is_tensor(groups) or groups.dtype != torch.int32 or tuple(groups.shape) != (G,)
-              or groups.device != table.device or not groups.is_contiguous()):
-            raise ValueError('FrameworkAccumulator.pool: groups must be a contiguous int32 [%d] tensor on the device of the table' % G)
-        if not table.is_cuda:
-            raise RuntimeError('gpe ops need tensors on the MI355X (got a %s table); there is no CPU path' % table.device)
-        dev = table.device
-        totals = torch.empty(n_groups + 1, 2, len(FRAMEWORK_TOTALS), device=dev, dtype=torch.int64)
-        loss = torch.empty(n_groups + 1, 2, device=dev, dtype=F64)
-        ratios = torch.empty(n_groups + 1, 2, len(STITCH_EVAL_METRICS), device=dev, dtype=F32)
-        L.call('gpe_framework_eval_pool', table, groups, G, n_groups, totals, loss, ratios)
-        return totals, loss, ratios
-
-    def read(self, along=()):
-        """THE host read -> one dict per row: {'stitch': {key: value}, 'stitch_corr': {key: value}, 'skipped': {reason: int}} with
-        value = np.float32(sum) / np.float32(cnt), None where no garment of the set was counted (the reference's None for an empty
-        list).  `.last_sums` [2, slots, 7] / `.last_counts` [2, slots] / `.last_skipped` [slots, 4] keep what was read.  along:
-        further device tensors of fp32 / int32 / fp64 / int64 to bring over in the same transfer; `.last_along` holds them as numpy
-        arrays of their own dtype and shape, in order."""
-        kinds = {F32: np.float32, torch.int32: np.int32, F64: np.float64, torch.int64: np.int64}
-        along = [t.detach() for t in along]
-        if any(t.dtype not in kinds or t.device != self.state.device for t in along):
-            raise ValueError('FrameworkAccumulator.read: along takes fp32 / int32 / fp64 / int64 tensors on the accumulator\'s device')
-        parts = [self.state] + [t.contiguous().view(torch.int32).reshape(-1) for t in along]
-        host = (torch.cat(parts) if along else self.state).cpu().numpy()
-        edges = np.cumsum([p.numel() for p in parts])
-        self.last_along = [host[a:b].view(kinds[t.dtype]).reshape(tuple(t.shape)) for a, b, t in zip(edges[:-1], edges[1:], along)]
-        return self.parse(host[:edges[0]])
-
-    def parse(self, host):
-        """read()'s result from `.state` as it arrived on the host (int32 numpy): for a caller that brought the state over in a
-        transfer of its own (evaluation.FrameworkEvaluator reads it along with the first stage's accumulator)"""
-        K, S = len(FRAMEWORK_EVAL_KEYS), self.slots
-        host = np.ascontiguousarray(host, dtype=np.int32).reshape(-1)
-        if host.size != self.state.numel():
-            raise ValueError('FrameworkAccumulator.parse: %d words expected (got %d)' % (self.state.numel(), host.size))
-        if host[-1]:
-            raise RuntimeError('FrameworkAccumulator: an add() met a slot word outside 0 .. %d and was dropped' % (S - 1))
-        a, b = 2 * S * K, 2 * S * K + 2 * S
-        sums, cnts, skipped = host[:a].view(np.float32).reshape(2, S, K), host[a:b].reshape(2, S), host[b:b + 4 * S].reshape(S, 4)
-        self.last_sums, self.last_counts, self.last_skipped = sums, cnts, skipped
-        rows = []
-        for s in range(S):
-            row = {name: {k: (np.float32(sums[i, s, j]) / np.float32(cnts[i, s]) if cnts[i, s] else None)
-                          for j, k in enumerate(FRAMEWORK_EVAL_KEYS)} for i, name in enumerate(FRAMEWORK_SETS)}
-            row['skipped'] = {r: int(skipped[s, j]) for j, r in enumerate(FRAMEWORK_SKIP_REASONS)}
-            rows.append(row)
-        return rows
-
-
-def standardize(x, shift, scale):
-    """nn/data/transforms.py:35-50 FeatureStandartization on the device: (x - shift) / scale per column."""
-    import ctypes
-    _dev_check(x)
-    x = x.contiguous()
-    C = x.shape[-1]
-    sh = (ctypes.c_float * C)(*[float(v) for v in shift])
-    sc = (ctypes.c_float * C)(*[float(v) for v in scale])
-    out = torch.empty_like(x)
-    L.call('gpe_standardize', x, x.numel() // C, C, sh, sc, out)
-    return out
-
-
-# -------------------------------------------------------------------------------------------------
-# Fitting the standardisation statistics (GarmentBaseDataset._get_distribution_stats / _get_norm_stats, nn/data/datasets.py:534-568)
-# -------------------------------------------------------------------------------------------------
-FIT_LEAF, FIT_MAX_C = 512, 16                    # rows per leaf and columns of csrc/gpe_fit_stats.hip
-FIT_STATUS_EMPTY, FIT_STATUS_NONFINITE = 1, 2    # status bits of the result block (include/gpe_hip_fit.h)
-F64 = torch.float64
-
-
-def fit_leaves(sets, rows_per_set):
-    """the records a part image of `sets` sets of `rows_per_set` rows holds (host only)"""
-    n = L.query('gpe_fit_leaves', int(sets), int(rows_per_set))
-    if n < 0:
-        raise ValueError('fit_leaves: sets and rows_per_set must be positive and their leaves fit 63 bits (got %r, %r)'
-                         % (sets, rows_per_set))
-    return n
-
-
-def _fit_columns(C):
-    if isinstance(C, bool) or not isinstance(C, int) or not 1 <= C <= FIT_MAX_C:
-        raise ValueError('the statistics fit handles 1 .. %d columns (got %r)' % (FIT_MAX_C, C))
-    return C
-
-
-def fit_part(x, part, leaf0=0, padded=False):
-    """One record of 1 + 4 C doubles per leaf (512 rows of one set) of x fp32 [S, N, C], written into the caller's part image (fp64
-    [leaves, 1 + 4 C]) from record leaf0 on: n, then per column mean, squared deviations, min, max over the rows kept (padded: rows
-    with |x| <= 1e-5 in every column are dropped, the reference's _unpad).  One launch of csrc/gpe_fit_stats.hip, no host read."""
-    if not torch.is_tensor(x) or x.dim() != 3:
-        raise ValueError('fit_part: x must be [S, N, C] (got %s)' % (tuple(getattr(x, 'shape', ())),))
-    _dev_check(x)
-    S, N, C = x.shape
-    _fit_columns(C)
-    if not x.is_contiguous():
-        raise ValueError('fit_part: x must be contiguous')
-    if (not torch.is_tensor(part) or part.dtype != F64 or part.dim() != 2 or part.shape[1] != 1 + 4 * C or part.device != x.device
-            or not part.is_contiguous()):
-        raise ValueError('fit_part: part must be a contiguous fp64 [leaves, %d] tensor on the device of x' % (1 + 4 * C))
-    leaves = fit_leaves(S, N)
-    if not 0 <= int(leaf0) <= part.shape[0] - leaves:
-        raise ValueError('fit_part: the %d leaves of x from record %d on do not fit a part image of %d' % (leaves, leaf0, part.shape[0]))
-    L.call('gpe_fit_part', x.detach(), S, N, C, 1 if padded else 0, int(leaf0), part.shape[0], part)
-    return part
-
-
-def fit_finish(part, out=None):
-    """Merges the records of a part image (fit_part) in a fixed order -> the result block, fp64 [2 + 5 C] on the device: n, status,
-    mean [C], std [C], min [C], max [C], norm_scale [C] (include/gpe_hip_fit.h).  One launch, no host read."""
-    if not torch.is_tensor(part) or part.dtype != F64 or part.dim() != 2 or part.shape[0] < 1 or (part.shape[1] - 1) % 4 or not part.is_contiguous():
-        raise ValueError('fit_finish: part must be a contiguous fp64 [leaves, 1 + 4 C] tensor')
-    if not part.is_cuda:
-        raise RuntimeError('gpe ops need tensors on the MI355X (got a %s part image); there is no CPU path' % part.device)
-    C = _fit_columns((part.shape[1] - 1) // 4)
-    if out is None:
-        out = torch.empty(2 + 5 * C, device=part.device, dtype=F64)
-    elif out.dtype != F64 or tuple(out.shape) != (2 + 5 * C,) or out.device != part.device or not out.is_contiguous():
-        raise ValueError('fit_finish: out must be a contiguous fp64 [%d] tensor on the device of part' % (2 + 5 * C))
-    L.call('gpe_fit_finish', part, part.shape[0], C, out)
-    return out
-
-
-def fit_read(result):
-    """the result block of fit_finish on the host (ONE device read), rounded to fp32 once like the reference's fp32 results ->
-    {'n': int, 'status': int, 'mean' / 'std' / 'min' / 'max' / 'norm_scale': fp32 numpy [C]}; ValueError when no row was left"""
-    r = result.detach().cpu().numpy()
-    C = (r.size - 2) // 5
-    status = int(r[1])
-    if status & FIT_STATUS_EMPTY:
-        raise ValueError('the statistics fit found no row (every row was dropped as padding)')
-    keys = ('mean', 'std', 'min', 'max', 'norm_scale')
-    out = {k: r[2 + i * C:2 + (i + 1) * C].astype(np.float32) for i, k in enumerate(keys)}
-    out.update(n=int(r[0]), status=status)
-    return out
-
-
-class FitAccumulator:
-    """The statistics of a data set that is handed in as chunks of whole sets:
-
-        acc = FitAccumulator(3, G, 2000, 'cuda')
-        for chunk in ...: acc.add(points)            # fp32 [g, 2000, 3] on the device, consecutive sets
-        stats = acc.read()                           # {'n', 'mean', 'std', 'min', 'max', 'norm_scale', 'status'}
-
-    The part image depends on (sets, rows_per_set) and the data alone, so the result is bit-identical for every chunking, grid size
-    and CU reservation.  Nothing reads the host before read()."""
-
-    def __init__(self, C, sets, rows_per_set, device, padded=False):
-        self.C = _fit_columns(C)
-        for name, v in (('sets', sets), ('rows_per_set', rows_per_set)):
-            if isinstance(v, bool) or not isinstance(v, int) or v < 1:
-                raise ValueError('FitAccumulator: %s must be a positive integer (got %r)' % (name, v))
-        self.sets, self.rows_per_set, self.padded = sets, rows_per_set, bool(padded)
-        self.device = torch.device(device)
-        if self.device.type != 'cuda':
-            raise RuntimeError('gpe ops need tensors on the MI355X (got device %s); there is no CPU path' % self.device)
-        self.leaves = fit_leaves(sets, rows_per_set)
-        self.part = torch.empty(self.leaves, 1 + 4 * self.C, device=self.device, dtype=F64)
-        self.added, self.result = 0, None
-
-    def add(self, x):
-        """x: fp32 [g, rows_per_set, C] on the device: the next g sets"""
-        if (not torch.is_tensor(x) or x.dim() != 3 or x.shape[0] < 1 or tuple(x.shape[1:]) != (self.rows_per_set, self.C)
-                or x.dtype != F32):
-            raise ValueError('FitAccumulator.add: fp32 [g >= 1, %d, %d] expected (got %s %s)'
-                             % (self.rows_per_set, self.C, getattr(x, 'dtype', type(x).__name__), tuple(getattr(x, 'shape', ()))))
-        if x.device != self.part.device:
-            raise ValueError('FitAccumulator.add: x lives on %s, the accumulator on %s' % (x.device, self.part.device))
-        if self.added + x.shape[0] > self.sets:
-            raise ValueError('FitAccumulator.add: %d sets after %d, but %d were announced' % (x.shape[0], self.added, self.sets))
-        fit_part(x.contiguous(), self.part, self.added * (self.leaves // self.sets), self.padded)
-        self.added += x.shape[0]
-        self.result = None
-
-    def finish(self):
-        """-> the result block on the device (fit_finish); every announced set must have been added"""
-        if self.added != self.sets:
-            raise ValueError('FitAccumulator.finish: %d of the %d announced sets were added' % (self.added, self.sets))
-        if self.result is None:
-            self.result = fit_finish(self.part)
-        return self.result
-
-    def read(self):
-        """-> fit_read(finish()): the one host read"""
-        return fit_read(self.finish())
 
 
 # -------------------------------------------------------------------------------------------------
@@ -3298,3 +1826,15 @@ class RaggedMaxFn(torch.autograd.Function):
         gx = torch.empty(E, C, device=gy.device, dtype=F32)
         L.call('gpe_ragged_max_bwd', gy, C, off, arg, seg, E, C, gx, C)
         return gx, None, None, None
+
+
+# -------------------------------------------------------------------------------------------------
+# The leaf modules, re-exported: callers keep spelling ops.X
+# -------------------------------------------------------------------------------------------------
+# ops_stitch imports names of this module, so these lines close a cycle.  It is safe only because they come last and because the
+# package's __init__ imports ops before any leaf: whichever leaf is asked for first, __init__ runs first, and this module is complete
+# when ops_stitch starts.  Keep both orders.  Each leaf's __all__ makes the star exact; nothing here is lazy.
+from .ops_stitch import *  # noqa: E402,F401,F403
+from .ops_losses import *  # noqa: E402,F401,F403
+from .ops_data import *  # noqa: E402,F401,F403
+from .ops_eval import *  # noqa: E402,F401,F403
