@@ -409,47 +409,68 @@ long gpe_rnn_persist_ws_bytes(int gates, int L, int T, int Bn, int H, int bwd)
     return ps_ws_layout(L, T, pl).total();
 }
 
-int gpe_rnn_persist_fwd(const GpeRnnSeq& q)
+// plan step of the forward: every check, the plan, the LDS image and the parameter struct (pointers are copied, never followed)
+static bool ps_fwd_plan(const GpeRnnSeq& q, PsFwdParams& p, GpeRnnPlan& pl, GpeRnnWs& lay, size_t& lds)
+{
+    if (!ps_plan(q.G, q.L, q.T, q.Bn, q.H, false, pl)) return false;
+    lay = ps_ws_layout(q.L, q.T, pl);
+    if (!lay.fits(q.ws, q.ws_bytes, 8)) return false;
+    if ((long)q.Bn * q.hs_sb * 4 >= (1L << 31) || (q.hs_sb & 3) || (q.hs_st & 3) || (((uintptr_t)q.hs) & 15)) return false;
+    pl.KP = q.f16 ? gpe_round_up(q.H, 32) : gpe_round_up(q.H, 16);
+    lds = (size_t)(q.L > 1 ? 2 : 1) * pl.KP * 256 + 4 * 16 * PS_LDC * 4;
+    if (lds > GPE_RNN_LDS_CAP) return false;
+    if (!gpe_rnn_fill_fwd(p, q, pl)) return false;
+    p.flags = (unsigned*)q.ws; p.trace = lay.trace_at(q.ws);
+    return true;
+}
+
+int gpe_rnn_persist_fwd(const GpeRnnSeq& q, GpeRnnPath* plan_only)
 {
     GpeRnnPlan pl;
-    if (!ps_plan(q.G, q.L, q.T, q.Bn, q.H, false, pl)) return GPE_RNN_NOT_MINE;
-    const GpeRnnWs lay = ps_ws_layout(q.L, q.T, pl);
-    if (!lay.fits(q.ws, q.ws_bytes, 8)) return GPE_RNN_NOT_MINE;
-    if ((long)q.Bn * q.hs_sb * 4 >= (1L << 31) || (q.hs_sb & 3) || (q.hs_st & 3) || (((uintptr_t)q.hs) & 15)) return GPE_RNN_NOT_MINE;
-    const int KP = q.f16 ? gpe_round_up(q.H, 32) : gpe_round_up(q.H, 16);
-    const size_t lds = (size_t)(q.L > 1 ? 2 : 1) * KP * 256 + 4 * 16 * PS_LDC * 4;
-    if (lds > GPE_RNN_LDS_CAP) return GPE_RNN_NOT_MINE;
+    GpeRnnWs lay;
+    size_t lds;
     PsFwdParams p = {};
-    if (!gpe_rnn_fill_fwd(p, q, pl)) return GPE_RNN_NOT_MINE;
-    p.flags = (unsigned*)q.ws; p.trace = lay.trace_at(q.ws);
+    if (!ps_fwd_plan(q, p, pl, lay, lds)) return GPE_RNN_NOT_MINE;
+    if (plan_only) { plan_only->persistent(pl, q.f16, pl.KP, lds, lay.total()); return GPE_RNN_LAUNCHED; }
     if (hipMemsetAsync(q.ws, 0, (size_t)lay.total(), q.s) != hipSuccess) return GPE_ELAUNCH;
     return gpe_rnn_for_bool(q.f16, [&](auto h3) {
         return gpe_rnn_launch<gpe_rnn_persist_fwd_kernel<decltype(h3)::value>, GPE_RNN_LDS_CAP>(dim3(pl.grid), 256, lds, q.s, p);
     });
 }
 
-int gpe_rnn_persist_bwd(const GpeRnnSeqBwd& q)
+// ... and of the backward
+static bool ps_bwd_plan(const GpeRnnSeqBwd& q, PsBwdParams& p, GpeRnnPlan& pl, GpeRnnWs& lay, size_t& lds)
 {
-    GpeRnnPlan pl;
-    if (!ps_plan(q.G, q.L, q.T, q.Bn, q.H, true, pl)) return GPE_RNN_NOT_MINE;
-    const GpeRnnWs lay = ps_ws_layout(q.L, q.T, pl);
-    if (!lay.fits(q.part, lay.total(), 8)) return GPE_RNN_NOT_MINE;           // (gpe_rnn_seq_bwd_ws covers this layout)
+    if (!ps_plan(q.G, q.L, q.T, q.Bn, q.H, true, pl)) return false;
+    lay = ps_ws_layout(q.L, q.T, pl);
+    if (!lay.fits(q.part, lay.total(), 8)) return false;                      // (gpe_rnn_seq_bwd_ws covers this layout)
     if ((long)q.Bn * q.dg_sb * 4 >= (1L << 31) || (q.dg_sb & 3) || (q.dg_st & 3) || (((uintptr_t)q.dgx) & 15) || (q.dg_sl & 3))
-        return GPE_RNN_NOT_MINE;
+        return false;
     // padded K (= 4H) extent of the transposed packs
     const int K = 4 * q.H, KP = q.f16 ? gpe_round_up(K, 32) : (int)(gpe_packed_size(q.H, K) / gpe_round_up(q.H, 16));
-    if (KP < K || KP > 1024 || (KP & (q.f16 ? 31 : 15))) return GPE_RNN_NOT_MINE;
-    const size_t lds = (size_t)(q.L > 1 ? 2 : 1) * KP * 64 + 4 * 16 * PS_LDB * 4;
-    if (lds > GPE_RNN_LDS_CAP) return GPE_RNN_NOT_MINE;
-    PsBwdParams p = {};
+    if (KP < K || KP > 1024 || (KP & (q.f16 ? 31 : 15))) return false;
+    pl.KP = KP;
+    lds = (size_t)(q.L > 1 ? 2 : 1) * KP * 64 + 4 * 16 * PS_LDB * 4;
+    if (lds > GPE_RNN_LDS_CAP) return false;
     p.L = q.L; p.T = q.T; p.Bn = q.Bn; p.H = q.H; p.NB = pl.NB; p.RG = pl.RG; p.NRT = pl.NRT; p.KP = KP;
     p.dtop = q.dtop; p.dt_sb = q.dt_sb; p.dt_st = q.dt_st; p.d_hN = q.d_hN; p.d_cN = q.d_cN;
     if (!gpe_rnn_fill_tables(p, q.L, 1, q.f16 ? q.whh_tpl : q.whh_t, q.f16 ? q.wih_tpl : q.wih_t, q.whh_amax, q.wih_amax, q.f16))
-        return GPE_RNN_NOT_MINE;
+        return false;
     p.cs = q.cs; p.cs_sl = q.cs_sl; p.cs_st = q.cs_st;
     p.saved = q.saved; p.sv_sl = q.sv_sl; p.sv_st = q.sv_st;
     p.dgx = q.dgx; p.dg_sl = q.dg_sl; p.dg_sb = q.dg_sb; p.dg_st = q.dg_st;
     p.carry = q.carry; p.flags = (unsigned*)q.part; p.trace = lay.trace_at(q.part);
+    return true;
+}
+
+int gpe_rnn_persist_bwd(const GpeRnnSeqBwd& q, GpeRnnPath* plan_only)
+{
+    GpeRnnPlan pl;
+    GpeRnnWs lay;
+    size_t lds;
+    PsBwdParams p = {};
+    if (!ps_bwd_plan(q, p, pl, lay, lds)) return GPE_RNN_NOT_MINE;
+    if (plan_only) { plan_only->persistent(pl, q.f16, pl.KP, lds, (lay.total() + 3) / 4); return GPE_RNN_LAUNCHED; }
     if (hipMemsetAsync(q.part, 0, (size_t)lay.total(), q.s) != hipSuccess) return GPE_ELAUNCH;
     return gpe_rnn_for_bool(q.f16, [&](auto h3) {
         return gpe_rnn_launch<gpe_rnn_persist_bwd_kernel<decltype(h3)::value>, GPE_RNN_LDS_CAP>(dim3(pl.grid), 256, lds, q.s, p);

@@ -167,7 +167,9 @@ __device__ __forceinline__ void pm_fwd_body(const PmFwdParams& p, const int l, c
     int al_g[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) al_g[q] = ((q * H) & 3) == 0 ? 16 : (((q * H) & 1) == 0 ? 8 : 4);      // rows are 4 H floats: 16-byte aligned
-    const bool hs_quad = unit0 + 4 <= (int)p.hs_st;                         // the quad lies inside the padded state row
+    // one 16-byte store where all four units exist; the ragged last quad goes out unit by unit: the pad columns of a state row are
+    // the caller's (include/gpe_hip.h) — storing the quad's zeros there was found by tests/test_gpu_rnn.py's pad sentinels
+    const bool hs_quad = nvalid == 4;
     unsigned* const flags_l = p.flags + (long)l * (T + 1) * NRT * PM_FS;
     const unsigned* const flags_dn = p.flags + (long)(l - 1) * (T + 1) * NRT * PM_FS;
     const unsigned need = (unsigned)p.NB;
@@ -408,24 +410,34 @@ long gpe_rnn_pm_ws_bytes(int gates, int L, int T, int Bn, int H, int bwd)
     return pm_ws_layout(L, T, pl).total();
 }
 
-int gpe_rnn_pm_fwd(const GpeRnnSeq& q)
+// plan step: every check, the plan, the LDS image and the parameter struct (pointers are copied, never followed)
+static bool pm_fwd_plan(const GpeRnnSeq& q, PmFwdParams& p, GpeRnnPlan& pl, GpeRnnWs& lay, size_t& lds)
 {
-    GpeRnnPlan pl;
-    if (!q.f16 || !pm_plan(q.G, q.L, q.T, q.Bn, q.H, pl)) return GPE_RNN_NOT_MINE;       // the weights are read as fp16 planes
-    const GpeRnnWs lay = pm_ws_layout(q.L, q.T, pl);
-    if (!lay.fits(q.ws, q.ws_bytes, 16)) return GPE_RNN_NOT_MINE;
+    if (!q.f16 || !pm_plan(q.G, q.L, q.T, q.Bn, q.H, pl)) return false;                 // the weights are read as fp16 planes
+    lay = pm_ws_layout(q.L, q.T, pl);
+    if (!lay.fits(q.ws, q.ws_bytes, 16)) return false;
     if (16L * pl.NRT * pl.KP * 4 >= (1L << 31) || (q.hs_sb & 3) || (q.hs_st & 3) || (q.hs_sl & 3) || (((uintptr_t)q.hs) & 15))
-        return GPE_RNN_NOT_MINE;
+        return false;
     // LDS: the weight slices, behind them 16 KB of cell states; a layer-0 workgroup (one slice) also keeps 64 KB of addends there
     const size_t keep0 = (size_t)16 * 1024 * 5, keepn = (size_t)16 * 1024 + 256;
-    size_t lds = (size_t)pl.KP * 256 + keep0;
+    lds = (size_t)pl.KP * 256 + keep0;
     if (q.L > 1 && (size_t)2 * pl.KP * 256 + keepn > lds) lds = (size_t)2 * pl.KP * 256 + keepn;
-    if (lds > GPE_RNN_LDS_CAP) return GPE_RNN_NOT_MINE;
-    if (gpe_cdiv(gpe_cdiv(pl.NRT, pl.RG), PM_NW) > PM_MAXQ) return GPE_RNN_NOT_MINE;
-    PmFwdParams p = {};
+    if (lds > GPE_RNN_LDS_CAP) return false;
+    if (gpe_cdiv(gpe_cdiv(pl.NRT, pl.RG), PM_NW) > PM_MAXQ) return false;
     p.KP = pl.KP;
-    if (!gpe_rnn_fill_fwd(p, q, pl)) return GPE_RNN_NOT_MINE;       // (q.f16 holds: every amax word is checked)
+    if (!gpe_rnn_fill_fwd(p, q, pl)) return false;                  // (q.f16 holds: every amax word is checked)
     p.flags = (unsigned*)q.ws; p.hsplit = lay.planes_at(q.ws); p.trace = lay.trace_at(q.ws);
+    return true;
+}
+
+int gpe_rnn_pm_fwd(const GpeRnnSeq& q, GpeRnnPath* plan_only)
+{
+    GpeRnnPlan pl;
+    GpeRnnWs lay;
+    size_t lds;
+    PmFwdParams p = {};
+    if (!pm_fwd_plan(q, p, pl, lay, lds)) return GPE_RNN_NOT_MINE;
+    if (plan_only) { plan_only->persistent(pl, true, pl.KP, lds, lay.total()); return GPE_RNN_LAUNCHED; }
     if (hipMemsetAsync(q.ws, 0, (size_t)lay.flags, q.s) != hipSuccess) return GPE_ELAUNCH;
     if (lay.trace && hipMemsetAsync(p.trace, 0, (size_t)lay.trace, q.s) != hipSuccess) return GPE_ELAUNCH;
     return gpe_rnn_launch<gpe_rnn_pm_fwd_kernel, GPE_RNN_LDS_CAP>(dim3(pl.grid), 64 * PM_NW, lds, q.s, p);

@@ -120,15 +120,29 @@ template <class P> static inline bool gpe_rnn_fill_fwd(P& p, const GpeRnnSeq& q,
     return gpe_rnn_fill_tables(p, q.L, 0, q.whh, q.wih, q.whh_amax, q.wih_amax, q.f16, q.bias, p.bias);
 }
 
-// ---- the families
+// ---- the numbers of a launch, as a family's PLAN STEP settles them (the checks, the plan, the LDS image) before its launch step
+// runs; gpe_rnn_seq_fwd_path / gpe_rnn_seq_bwd_path (gpe_rnn_seq.hip) export them in this order.  A field a family does not have is 0
+struct GpeRnnPath {
+    long f16, NB, NRT, per, rgmax, RG, KP, grid, lds;      // grid: workgroups of the (largest) launch
+    long ws_used;                                          // forward: bytes behind ws, backward: floats behind part the launch touches
+    long ks, split, jslabs, nz, fuse, Hp, groups;          // the diagonals: K slab width, <= 32-row split mode, ..., most groups per diagonal
+    void persistent(const GpeRnnPlan& pl, bool h3, int kp, size_t lds_bytes, long used)
+    {
+        f16 = h3; NB = pl.NB; NRT = pl.NRT; per = pl.per; rgmax = pl.rgmax; RG = pl.RG; KP = kp; grid = pl.grid; lds = (long)lds_bytes;
+        ws_used = used;
+    }
+};
+#define GPE_RNN_PATH_LEN 17
+
+// ---- the families.  With `plan_only` a family runs its plan step alone: it answers as it would, fills *plan_only and launches nothing
 long gpe_rnn_persist_ws_bytes(int gates, int L, int T, int Bn, int H, int bwd);      // 0: this stack does not run there
-int gpe_rnn_persist_fwd(const GpeRnnSeq& q);
-int gpe_rnn_persist_bwd(const GpeRnnSeqBwd& q);                                      // its workspace is q.part
+int gpe_rnn_persist_fwd(const GpeRnnSeq& q, GpeRnnPath* plan_only = nullptr);
+int gpe_rnn_persist_bwd(const GpeRnnSeqBwd& q, GpeRnnPath* plan_only = nullptr);     // its workspace is q.part
 long gpe_rnn_pm_ws_bytes(int gates, int L, int T, int Bn, int H, int bwd);
-int gpe_rnn_pm_fwd(const GpeRnnSeq& q);
+int gpe_rnn_pm_fwd(const GpeRnnSeq& q, GpeRnnPath* plan_only = nullptr);
 long gpe_rnn_wave_bwd_ws_floats(int gates, int L, int T, int Bn, int H);
-int gpe_rnn_wave_fwd(const GpeRnnSeq& q);
-int gpe_rnn_wave_bwd(const GpeRnnSeqBwd& q);
+int gpe_rnn_wave_fwd(const GpeRnnSeq& q, GpeRnnPath* plan_only = nullptr);
+int gpe_rnn_wave_bwd(const GpeRnnSeqBwd& q, GpeRnnPath* plan_only = nullptr);
 
 // ---- the diagonal walk: cell (l, t) needs (l, t - 1) and (l - 1, t), so the cells of anti-diagonal d = l + t are independent.
 // Calls f(d, l0, l_top) for every group of at most WV_MAXCELL cells l0 <= l <= l_top, t = d - l, diagonals ascending (forward) or

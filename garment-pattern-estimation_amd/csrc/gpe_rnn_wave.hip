@@ -348,31 +348,58 @@ static int wv_ks()
     return ks;
 }
 
-template <int G>
-static int wv_fwd_launch(const WvFwdParams& p, bool h3, hipStream_t s)
+// does the last (or only) 64-row tile run the wave-pair K split of wv_mma?
+static int wv_split_mode(int Bn) { return Bn - RG_BM * (gpe_cdiv(Bn, RG_BM) - 1) <= 32; }
+// cells of the largest launch and launches of the longest diagonal (gpe_rnn_walk_diagonals)
+static void wv_groups(int L, int T, int& ncell_max, int& groups)
+{
+    const int longest = L < T ? L : T;
+    ncell_max = longest < WV_MAXCELL ? longest : WV_MAXCELL;
+    groups = gpe_cdiv(longest, WV_MAXCELL);
+}
+
+// plan step of the forward: slab width, padded slab extent and LDS image of every launch of the walk
+struct WvFwdPlan { int ks, kp_max; size_t lds; };
+static int wv_fwd_plan(const GpeRnnSeq& q, WvFwdPlan& w, GpeRnnPath* out)
 {
     // a single row tile (the pattern decoders) is a pure latency chain: the wide slab halves its barrier pairs
     // (a 96-wide slab — 50 KB, three workgroups per CU, the 576-workgroup panel diagonal in one round — measured slower:
     // 686 vs 641 us per panel-decoder forward; three slabs per segment instead of two)
-    const bool wide = wv_ks() == 256 || p.Bn <= RG_BM;
+    const bool wide = wv_ks() == 256 || q.Bn <= RG_BM;
+    w.ks = wide ? 256 : 128;
+    w.kp_max = gpe_round_up(q.H < w.ks ? q.H : w.ks, q.f16 ? 32 : 16);
+    const int lda = w.kp_max + 4, ldc = 16 * 2 * q.G + 4;
+    w.lds = ((size_t)RG_BM * (lda > ldc ? lda : ldc) + (size_t)w.kp_max * 16 * q.G) * sizeof(float);
+    if (w.lds > GPE_RNN_LDS_CAP) return GPE_EINVAL;
+    if (out) {
+        int ncell_max, groups;
+        wv_groups(q.L, q.T, ncell_max, groups);
+        out->f16 = q.f16; out->KP = w.kp_max; out->lds = (long)w.lds; out->ks = w.ks; out->split = wv_split_mode(q.Bn);
+        out->grid = (long)gpe_cdiv(q.Bn, RG_BM) * gpe_cdiv(q.H, 16) * ncell_max; out->groups = groups;
+    }
+    return GPE_RNN_LAUNCHED;
+}
+
+template <int G>
+static int wv_fwd_launch(const WvFwdParams& p, bool h3, const WvFwdPlan& w, hipStream_t s)
+{
     return gpe_rnn_for_bool(h3, [&](auto h3c) {
-        return gpe_rnn_for_ks(wide ? 256 : 128, [&](auto ksc) {
+        return gpe_rnn_for_ks(w.ks, [&](auto ksc) {
             constexpr bool H3 = decltype(h3c)::value;
             constexpr int KS = decltype(ksc)::value;
-            const int kp_max = gpe_round_up(p.H < KS ? p.H : KS, H3 ? 32 : 16);
-            const int lda = kp_max + 4, ldc = 16 * 2 * G + 4;
-            const size_t lds = ((size_t)RG_BM * (lda > ldc ? lda : ldc) + (size_t)kp_max * 16 * G) * sizeof(float);
-            if (lds > GPE_RNN_LDS_CAP) return GPE_EINVAL;
             return gpe_rnn_launch<gpe_rnn_wave_fwd_kernel<G, KS, H3>, GPE_RNN_LDS_CAP>(
-                dim3(gpe_cdiv(p.Bn, RG_BM), gpe_cdiv(p.H, 16), p.ncell), 256, lds, s, p);
+                dim3(gpe_cdiv(p.Bn, RG_BM), gpe_cdiv(p.H, 16), p.ncell), 256, w.lds, s, p);
         });
     });
 }
 
 // one fused launch per group of a diagonal's cells; takes every stack
-int gpe_rnn_wave_fwd(const GpeRnnSeq& q)
+int gpe_rnn_wave_fwd(const GpeRnnSeq& q, GpeRnnPath* plan_only)
 {
     const int G = q.G;
+    WvFwdPlan w;
+    const int rcp = wv_fwd_plan(q, w, plan_only);
+    if (rcp < 0 || plan_only) return rcp;
     return gpe_rnn_walk_diagonals(q.L, q.T, false, [&](int d, int l0, int l_top) {
         WvFwdParams p = {};
         p.Bn = q.Bn; p.H = q.H; p.Npad = 16 * G * gpe_cdiv(q.H, 16);
@@ -407,7 +434,7 @@ int gpe_rnn_wave_fwd(const GpeRnnSeq& q)
             c.h_stride = q.hs_sb;
         }
         p.ncell = n;
-        return (G == 4) ? wv_fwd_launch<4>(p, q.f16, q.s) : wv_fwd_launch<3>(p, q.f16, q.s);
+        return (G == 4) ? wv_fwd_launch<4>(p, q.f16, w, q.s) : wv_fwd_launch<3>(p, q.f16, w, q.s);
     });
 }
 
@@ -631,9 +658,12 @@ long gpe_rnn_wave_bwd_ws_floats(int gates, int L, int T, int Bn, int H)
 
 // two launches per group of a diagonal's cells (split-K products, pointwise cell backward); takes every stack.  On return
 // carry slot 0 holds dc_0 / the z-gated dh_0 of every layer
-int gpe_rnn_wave_bwd(const GpeRnnSeqBwd& q)
+//
+// plan step: slab width, slabs per workgroup, partial images, the fused mode and where its counters start, the LDS image
+struct WvBwdPlan { int KS, jslabs, nz, fuse, Hp, gxr, gyc, ncell_max; long cnt_off, cnt_per_launch; size_t lds; };
+static void wv_bwd_plan(const GpeRnnSeqBwd& q, WvBwdPlan& w, GpeRnnPath* out)
 {
-    const int G = q.G, L = q.L, T = q.T, Bn = q.Bn, H = q.H, K = G * H;
+    const int G = q.G, L = q.L, Bn = q.Bn, H = q.H, K = G * H;
     const int KS = wv_ks();
     // big batches: four slabs per workgroup (a 3-cell panel diagonal: 2304 single-slab workgroups in 4.5 rounds -> 480 in one,
     // a quarter of the partial images; measured 804 / 717 / 621 / 689 us per backward at 1 / 2 / 4 / 8 slabs); a single row
@@ -642,7 +672,6 @@ int gpe_rnn_wave_bwd(const GpeRnnSeqBwd& q)
     int jslabs = (Bn > 3 * RG_BM) ? (gpe_cdiv(K, KS) < 4 ? gpe_cdiv(K, KS) : 4) : 1;
     if (dbg_bj > 0 && Bn > 3 * RG_BM) jslabs = dbg_bj < gpe_cdiv(K, KS) ? dbg_bj : gpe_cdiv(K, KS);
     const int nz = gpe_cdiv(gpe_cdiv(K, KS), jslabs);
-    const long BH = (long)Bn * H;
     // LSTM, gpe_debug_set(65536): the pointwise cell backward runs in the split-K launch itself (the last partial of an output block
     // to arrive does it): one launch per diagonal instead of two.  Built, bit-compatible (same tests), and
     // MEASURED SLOWER — cfg 2, one session, twice each: gpe_rnn_seq_bwd 0.838 ms with two launches, 1.115 / 1.117 ms fused (step
@@ -654,11 +683,30 @@ int gpe_rnn_wave_bwd(const GpeRnnSeqBwd& q)
     const long BHp = (long)Bn * Hp;
     const int gxr = gpe_cdiv(Bn, RG_BM), gyc = gpe_cdiv(H, 64);
     const int ncell_max = L < WV_MAXCELL ? L : WV_MAXCELL;
-    unsigned* cnt_base = reinterpret_cast<unsigned*>(q.part + (((long)ncell_max * 2 * nz * BHp + 15) & ~15L));
-    const long cnt_per_launch = (long)WV_MAXCELL * gxr * gyc;
+    w = {KS, jslabs, nz, fuse, Hp, gxr, gyc, ncell_max, ((long)ncell_max * 2 * nz * BHp + 15) & ~15L, (long)WV_MAXCELL * gxr * gyc,
+         ((size_t)RG_BM * (KS + 4) + (size_t)KS * 64) * sizeof(float)};
+    if (out) {
+        int cells, groups;
+        wv_groups(L, q.T, cells, groups);
+        out->ks = KS; out->split = wv_split_mode(Bn); out->jslabs = jslabs; out->nz = nz; out->fuse = fuse; out->Hp = Hp;
+        out->groups = groups; out->lds = (long)w.lds; out->grid = (long)gxr * gyc * cells * 2 * nz;
+        out->ws_used = fuse ? w.cnt_off + (q.T + L) * w.cnt_per_launch : (long)ncell_max * 2 * nz * BHp;
+    }
+}
+
+int gpe_rnn_wave_bwd(const GpeRnnSeqBwd& q, GpeRnnPath* plan_only)
+{
+    WvBwdPlan w;
+    wv_bwd_plan(q, w, plan_only);
+    if (plan_only) return GPE_RNN_LAUNCHED;
+    const int G = q.G, L = q.L, T = q.T, Bn = q.Bn, H = q.H, K = G * H;
+    const int KS = w.KS, jslabs = w.jslabs, nz = w.nz, fuse = w.fuse, Hp = w.Hp, gxr = w.gxr, gyc = w.gyc;
+    const long BH = (long)Bn * H, BHp = (long)Bn * Hp;
+    unsigned* cnt_base = reinterpret_cast<unsigned*>(q.part + w.cnt_off);
+    const long cnt_per_launch = w.cnt_per_launch;
     int launch_no = 0;
     if (fuse && hipMemsetAsync(cnt_base, 0, (size_t)(T + L) * cnt_per_launch * sizeof(unsigned), q.s) != hipSuccess) return GPE_ELAUNCH;
-    const size_t lds = ((size_t)RG_BM * (KS + 4) + (size_t)KS * 64) * sizeof(float);
+    const size_t lds = w.lds;
     return gpe_rnn_walk_diagonals(L, T, true, [&](int d, int l0, int l_top) {
         WvBwdParams p = {};
         p.Bn = Bn; p.H = H; p.K = K; p.Kpad_n = gpe_round_up(H, 16); p.nz = nz; p.jslabs = jslabs;

@@ -395,13 +395,34 @@ int gpe_gru_cell_bwd(const float* dh_out, long dho_stride, const float* dh_rec, 
  *           every step, the decoders' case)
  * whh / wih / bias / bhn are HOST arrays of L device pointers: gate-interleaved packed W_hh_l; gate-interleaved packed W_ih_l
  * (entry 0 unused); the addend row [gates*H] of layers > 0 (LSTM b_ih + b_hh; GRU b_ih + [b_hr | b_hz | 0]; entry 0 unused);
- * GRU b_hn [H] per layer (NULL for LSTM). */
+ * GRU b_hn [H] per layer (NULL for LSTM).
+ * Alignment: hs (and dgx / dgh of gpe_rnn_seq_bwd) must be 16-byte aligned and hs_sl (dg_sl) a multiple of 4 floats like the
+ * other pitches: every family fetches rows in 16-byte pieces.  The persistent families check both and decline; the entry points do
+ * NOT (they check hs_sb, hs_st / dg_sb, dg_st only) and the diagonal launches then fetch misaligned pieces: the caller's error.
+ * What is read and written of a state row (hs_st may exceed H; a row's pad columns are H .. hs_st - 1).  No element outside columns
+ * 0 .. H - 1 of slots 0 .. T ever enters the arithmetic: whatever else a fetch brings in is replaced by zero (a select, not a
+ * product) before any use, so pad columns, gaps and slots not yet produced need not be zero and may hold any bit pattern, NaN
+ * included.  What the fetches LOAD beyond that, family by family:
+ *   diagonal launches        16-byte pieces that start below column H: columns H .. round_up(H, 4) - 1 of the row
+ *   persistent, K split      whole k-steps of a row: columns H .. round_up(H, 16) - 1 (fp16 pipe: round_up(H, 32) - 1) counted on from
+ *                            the row's slot — past hs_st these are the row's NEXT slots, which another workgroup may be writing, the
+ *                            gap behind the row or the next row — as far as they lie inside the buffer descriptor of the slot (from
+ *                            the slot of row 0 to column round_up(H, 4) of the slot of row Bn - 1; beyond it the load returns zero).
+ *                            Loaded and discarded, never values
+ *   persistent, multi-tile   columns 0 .. H - 1 of slot 0 only (later states travel through the workspace)
+ * NOTHING outside columns 0 .. H - 1 of slots 1 .. T is written: slot 0, every pad column and every gap come back as they were.
+ * The same holds for cs (slot 0 read, slots 1 .. T written, [Bn][H] dense inside a slot) and saved (each [Bn][4H] dense), and in
+ * gpe_rnn_seq_bwd for the dgx / dgh rows: only columns 0 .. gates*H - 1 are values or written; the diagonal launches load up to
+ * round_up(gates*H, 4), the K-split kernel whole k-steps up to KP (plan_out[6]) inside its descriptor, both discarded.  The
+ * backward reads of hs only columns 0 .. H - 1 of slots 0 .. T - 1 (GRU only). */
 int gpe_rnn_seq_fwd(int gates, int L, int T, int Bn, int H, const float* xproj0, long xp0_sb, long xp0_st,
                     const void* const* whh, const void* const* wih, const void* const* bias, const void* const* bhn,
                     float* hs, long hs_sl, long hs_sb, long hs_st, float* cs, long cs_sl, long cs_st, float* saved,
                     long sv_sl, long sv_st, const void* const* whh_pl, const void* const* wih_pl,
                     const void* const* whh_amax, const void* const* wih_amax, void* ws, long ws_bytes, void* stream);
-/* ws: gpe_rnn_seq_fwd_ws bytes of scratch (4-byte aligned; may be NULL when the query answers 0).  An LSTM stack of <= 256
+/* ws: gpe_rnn_seq_fwd_ws bytes of scratch (may be NULL when the query answers 0; the K-split persistent kernels take it 8-byte
+ * aligned, the multi-tile one 16-byte aligned — a workspace that is missing, shorter or less aligned is no error: the next family
+ * of DESIGN.md 5.28 runs, which gpe_rnn_seq_fwd_path shows).  An LSTM stack of <= 256
  * units whose 16-row tiles fit the chip (layers x ceil(H/16) x row tiles <= compute units: the pattern decoder, 32 rows x 2
  * layers) then runs as ONE persistent launch (gpe_rnn_persist.hip): every workgroup keeps its weight slices in LDS for all T
  * steps and cells hand their state rows on through arrival counters in `ws` (zeroed in-call) instead of kernel boundaries.
@@ -430,6 +451,29 @@ int gpe_rnn_seq_bwd(int gates, int L, int T, int Bn, int H, const float* dtop, l
  * TRANSPOSED fp16 plane packs (gpe_pack_multi kind 10) of W_hh_l / W_ih_l and their amax words — used by the persistent
  * backward launch (same eligibility as the forward's) in f16x3 mode: the dG rows are normalised per wave by the largest
  * magnitude the wave loaded, three fp16 MFMAs per product, fp32 accumulate.  Absent: exact fp32. */
+/* Which kernel family a recurrence call runs, and the numbers of its launch.  Added without a version bump (gpe_abi_version() stays
+ * 7): two host-only queries, nothing else changes.  HOST ONLY: hs / ws / dgx / part are looked at for NULL and for their alignment
+ * and never followed, no HIP call is made beyond the CU count (256 without a GPU, less gpe_reserve_cus_set) and nothing is launched;
+ * the arithmetic mode, the debug word and the CU reservation are read as the entry points read them, and the entry points decide by
+ * the same plan steps.  The operand tables are described by what the families look at:
+ *   packs      the alignment in bytes the worst fp32 pack in use has (forward: the gate packs; backward: the transposed packs):
+ *              16 = every pack there and aligned, 8 = one is misaligned, 0 = one is missing
+ *   planes     the same for the fp16 plane packs (forward kind 8, backward kind 10) with their amax words; 0 = the tables are
+ *              incomplete, so that the exact kernels run in every arithmetic mode
+ *   bias_rows  forward: 1 = the bias row of every layer > 0 is there
+ * Every other pointer of the entry point counts as present.  Returns -22 where the entry point refuses the call, else the family:
+ *   1 persistent, K split over the waves   2 persistent, waves own row tiles (forward)   3 diagonal launches
+ * plan_out (may be NULL; written only with a family) receives 17 numbers; one a family does not have is 0:
+ *   [0] fp16 pipe  [1] NB  [2] NRT  [3] per (workgroups of a row group)  [4] rgmax  [5] RG  [6] KP (diagonals forward: the padded
+ *   slab extent)  [7] grid (diagonals: workgroups of the largest launch)  [8] LDS bytes  [9] what the launch touches of the
+ *   workspace: bytes behind ws (forward), floats behind part (backward) — never more than gpe_rnn_seq_fwd_ws / _bwd_ws
+ *   diagonals: [10] K slab width (128 / 256)  [11] the last 64-row tile holds <= 32 rows (wave-pair K split)  [12] jslabs  [13] nz
+ *   [14] fuse  [15] Hp (pitch of the partial images)  [16] the most launches (groups of <= 4 cells) a diagonal takes
+ * The policies are the library's to change; the codes and the positions in plan_out are not. */
+int gpe_rnn_seq_fwd_path(int gates, int L, int T, int Bn, int H, const float* hs, long hs_sl, long hs_sb, long hs_st, int packs,
+                         int planes, int bias_rows, const void* ws, long ws_bytes, long* plan_out);
+int gpe_rnn_seq_bwd_path(int gates, int L, int T, int Bn, int H, const float* dgx, long dg_sl, long dg_sb, long dg_st,
+                         const float* part, int packs, int planes, long* plan_out);
 
 /* ---- attention variant (GarmentSegmentPattern3D, nn/nets.py:187-299) ------------------------------------------ */
 /* sparsemax.Sparsemax(dim=1) over rows of width W <= 32 (nn/nets.py:225): forward and backward */
