@@ -16,6 +16,8 @@
 #include "../../include/gpe_hip_place.h"
 // ... and the two-stage evaluation pass (the classifier scored on predicted patterns), bound through _lib.FRAMEWORK_HEADERS
 #include "../../include/gpe_hip_framework.h"
+// ... and the epoch feed (the balanced batch schedule and the per-step gather), bound through _lib.FEED_HEADERS
+#include "../../include/gpe_hip_feed.h"
 
 #define GPE_OK 0
 #define GPE_EINVAL (-22)

@@ -1,6 +1,6 @@
-"""Input data on the device: point clouds drawn from resident meshes (mesh_resident, mesh_points_sample), standardisation and the
-fit of its statistics (fit_part .. FitAccumulator).  Reached as ops.X: ops.py re-exports every name of __all__.  The sampler of the
-stitch classifier's training rows is in ops_stitch, with the classifier."""
+"""Input data on the device: point clouds drawn from resident meshes (mesh_resident, mesh_points_sample), standardisation, the fit of
+its statistics (fit_part .. FitAccumulator) and the epoch feed (batch_schedule_draw, feed_jobs, feed_next).  Reached as ops.X: ops.py
+re-exports every name of __all__.  The sampler of the stitch classifier's training rows is in ops_stitch, with the classifier."""
 import numpy as np
 import torch
 
@@ -8,8 +8,8 @@ from . import _lib as L
 from ._opbase import F32, F64, _dev_check, _int32
 
 __all__ = ['MeshResident', 'mesh_face_thresholds', 'mesh_resident', 'MESH_SAMPLE_MAX_POINTS', 'MESH_SAMPLE_MAX_BATCH',
-           'mesh_points_buffers', 'mesh_points_sample', 'standardize', 'FIT_LEAF', 'FIT_MAX_C', 'FIT_STATUS_EMPTY',
-           'FIT_STATUS_NONFINITE', 'fit_leaves', 'fit_part', 'fit_finish', 'fit_read', 'FitAccumulator']
+           'mesh_points_buffers', 'mesh_points_sample', 'standardize', 'FIT_LEAF', 'FIT_MAX_C', 'FIT_STATUS_EMPTY', 'FIT_STATUS_NONFINITE',
+           'fit_leaves', 'fit_part', 'fit_finish', 'fit_read', 'FitAccumulator', 'batch_schedule_draw', 'feed_jobs', 'feed_next']
 
 
 class MeshResident:
@@ -296,3 +296,29 @@ class FitAccumulator:
     def read(self):
         """-> fit_read(finish()): the one host read"""
         return fit_read(self.finish())
+
+
+def batch_schedule_draw(class_off, ids, quota, class_off_host, quota_host, B, drop_last, state, ws, table, batch_len):
+    """One epoch's balanced batch schedule into table int32 [rows, B] and batch_len int32 [rows] (include/gpe_hip_feed.h): three launches,
+    no host read.  class_off / quota: int32 on the device, with numpy int32 copies for the argument checks; state {seed, epoch} advances"""
+    L.call('gpe_batch_schedule_draw', class_off, ids, quota, class_off_host.ctypes.data, quota_host.ctypes.data, quota.numel(),
+           ids.numel(), int(B), 1 if drop_last else 0, state, ws, ws.numel(), table, batch_len)
+
+
+def feed_jobs(tables, outputs):
+    """the job array of feed_next: resident tables [G, ...] and their outputs [B, ...], contiguous device tensors whose rows are a
+    multiple of 4 bytes, 16 at the most -> (jobs int64 [T, 3] on the device, the bytes of the widest row); checked by gpe_feed_jobs"""
+    import ctypes
+    T, nb = len(tables), [t[0].numel() * t.element_size() for t in tables]
+    bad = any(not (t.is_contiguous() and o.is_contiguous() and o[0].numel() * o.element_size() == n) for t, o, n in zip(tables, outputs, nb))
+    jobs, ptrs = np.zeros((T, 3), dtype=np.int64), lambda ts: (ctypes.c_void_p * T)(*[t.data_ptr() for t in ts])
+    if bad or L.lib().gpe_feed_jobs(T, ptrs(tables), ptrs(outputs), (ctypes.c_long * T)(*nb), jobs.ctypes.data) != 0:
+        raise ValueError('feed_jobs: 1 .. 16 contiguous tables, rows a multiple of 4 bytes and as wide as their outputs\' (%d: %s)' % (T, nb))
+    return torch.from_numpy(jobs).to(tables[0].device), max(nb)
+
+
+def feed_next(table, cursor, G, jobs, max_row_bytes, index_out, status):
+    """The next batch (two launches, legal in a capture): index_out int32 [B] = row cursor % rows of table; every job's output row b =
+    its resident row index_out[b]; cursor int64 [1] advanced; status int32 [1] = the entries outside 0 .. G - 1 (zero rows)"""
+    L.call('gpe_feed_next', table, table.shape[0], table.shape[1], cursor, int(G), jobs, 0 if jobs is None else jobs.shape[0],
+           int(max_row_bytes), index_out, status)

@@ -11,10 +11,16 @@ nn/data/datasets.py:985-1132): the data set's 3D edges and stitches stay in HBM 
 MeshPointSampler is the input side of the encoder / decoder step (Garment3DPatternFullDataset._get_sample_info): the data set's
 meshes stay in HBM and every step's point clouds and segmentation labels are drawn there.
 
+BalancedBatchSchedule and EpochFeeder make an epoch self-feeding (DatasetWrapper.new_loaders' BalancedBatchSampler,
+nn/data/wrapper.py:78-89, nn/data/utils.py:16-92): which garments form every batch is drawn on the device once per epoch, the
+garments' ground truth stays in HBM, and each step takes its index and ground-truth rows from there without a tensor from the host.
+
 The statistics both samplers standardise with are fitted on the device as well (fit_feature_stats of either sampler,
 fit_pattern_standardization for the ground truth: the reference's standardize(training), nn/data/datasets.py:596-645, 1018-1041)."""
+import numpy as np
 import torch
 
+from . import _lib as L
 from . import ops
 from . import streams
 
@@ -267,3 +273,167 @@ class MeshPointSampler:
         if install:
             self.f_shift, self.f_scale = [float(v) for v in stats['f_shift']], [float(v) for v in stats['f_scale']]
         return stats
+
+
+def balanced_quotas(sizes, batch_size):
+    """the garments of every type in a balanced batch, in the reference's own expression (nn/data/utils.py:48): int((len_c / G) *
+    batch_size), evaluated in double.  It is not len_c * batch_size // G: 13 of 23 garments at batch_size = 23 give 12."""
+    G = sum(sizes)
+    return [int((n / G) * batch_size) for n in sizes]
+
+
+class BalancedBatchSchedule:
+    """The batches of a training epoch drawn on the device: what BalancedBatchSampler (nn/data/utils.py:16-92) yields, restated as
+    a function of (seed, epoch, class lists, quotas, batch_size, drop_last) alone (include/gpe_hip_feed.h).  Every batch holds the
+    quota of every garment type (balanced_quotas), the free slots take garments of types chosen uniformly among those that still
+    have some, the slots of a batch are shuffled, and no garment appears twice in an epoch.
+
+    ids_by_type: {type: integer sequence or tensor of garment ids}, as the reference's constructor takes it; more types than
+    batch_size is the same NotImplementedError; len() is the same number of batches.
+
+        schedule = BalancedBatchSchedule(ids_by_type, 30)
+        schedule.draw()                     # three launches, no host read: the next epoch's table
+        rows = schedule.host_table()        # the one host read, for logging and tests
+
+    `.table` int32 [len(), batch_size] (a kept remainder is padded with -1), `.batch_len` int32 [len()], `.state` int64 [2] =
+    {seed, epoch} (every draw() advances epoch by one on the device) and `.cursor` int64 [1] (the row ops.feed_next takes next) are
+    static device tensors.  reseed(seed, epoch) restarts the sequence."""
+
+    def __init__(self, ids_by_type, batch_size, drop_last=True, seed=0, device='cuda'):
+        if len(ids_by_type) > batch_size:
+            raise NotImplementedError('BalancedBatchSchedule: creating batches that are smaller than the number of garment types '
+                                      'is not implemented (%d types, batch_size = %d)' % (len(ids_by_type), batch_size))
+        lists = [np.asarray(v.detach().cpu() if torch.is_tensor(v) else v).reshape(-1) for v in ids_by_type.values()]
+        if not lists or any(l.size and l.dtype.kind not in 'iu' for l in lists):
+            raise ValueError('ids_by_type must map at least one type to integer garment ids')
+        lists = [l.astype(np.int64) for l in lists]
+        sizes = [int(l.size) for l in lists]
+        G = sum(sizes)
+        self.class_names = list(ids_by_type.keys())
+        self.batch_size, self.data_size = int(batch_size), G
+        rows = L.query('gpe_batch_schedule_rows', G, self.batch_size, 1 if drop_last else 0)
+        if rows < 0:
+            raise ValueError('BalancedBatchSchedule handles 1 .. 2^20 garments in batches of 1 .. 1024 (got %d, batch_size = %d)'
+                             % (G, batch_size))
+        if rows == 0:
+            raise ValueError('the %d garments do not fill one batch of %d and drop_last leaves none' % (G, batch_size))
+        ids = np.concatenate(lists)
+        if ids.min() < 0 or ids.max() >= 1 << 31:
+            raise ValueError('garment ids are integers in 0 .. 2^31 - 1')
+        self.num_full_batches = G // self.batch_size
+        self.drop_last = bool(drop_last) or G % self.batch_size == 0
+        self.quotas = balanced_quotas(sizes, self.batch_size)
+        if sum(self.quotas) > self.batch_size:
+            raise ValueError('the per-type batch lengths %s exceed batch_size = %d' % (self.quotas, batch_size))
+        self.device = torch.device(device)
+        if self.device.type != 'cuda':
+            raise RuntimeError('gpe ops need tensors on the MI355X (got device %s); there is no CPU path' % self.device)
+        self._class_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
+        self._quota = np.asarray(self.quotas, dtype=np.int32)
+        to = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)          # noqa: E731
+        self.class_off, self.ids, self.quota = to(self._class_off), to(ids.astype(np.int32)), to(self._quota)
+        self.table = torch.full((rows, self.batch_size), -1, device=self.device, dtype=torch.int32)
+        self.batch_len = torch.zeros(rows, device=self.device, dtype=torch.int32)
+        self.state = ops.stitch_sample_state(seed, 0, self.device)
+        self.cursor = torch.zeros(1, device=self.device, dtype=torch.int64)
+        self.ws = torch.empty(L.query('gpe_batch_schedule_ws_bytes', G), device=self.device, dtype=torch.uint8)
+
+    def __len__(self):
+        return self.num_full_batches + (not self.drop_last)
+
+    def reseed(self, seed, epoch=0):
+        """the next draw() uses (seed, epoch); a copy queued on the current stream, no device read"""
+        self.state.copy_(ops.stitch_sample_state(seed, epoch, 'cpu'), non_blocking=False)
+
+    def draw(self):
+        """queues the next epoch's table on the current stream (three launches); no host read"""
+        ops.batch_schedule_draw(self.class_off, self.ids, self.quota, self._class_off, self._quota, self.batch_size, self.drop_last,
+                                self.state, self.ws, self.table, self.batch_len)
+
+    def host_table(self):
+        """-> the table of the last draw() as a CPU int32 [len(), batch_size] tensor (-1 pads a kept remainder): the one host read"""
+        return self.table.cpu()
+
+
+class EpochFeeder:
+    """The inputs of every step of an epoch taken from device memory: the next row of a BalancedBatchSchedule becomes the step's
+    index, the ground truth of its garments is gathered from resident tables (ops.feed_next, two launches), and the sampler draws
+    the batch's clouds or pair rows from that index.  Nothing comes from the host, so a captured step feeds itself at every replay:
+
+        feeder = EpochFeeder(schedule, sampler, ground_truth)
+        sg = graph.StepGraph(lambda: model.loss(model(feeder.next()[0]), feeder.last_gt)[0], opt)
+        for epoch in ...:
+            feeder.begin_epoch()
+            for _ in range(len(feeder)):
+                loss = sg.step()
+
+    ground_truth: {name: tensor [G, ...]} whose leading dimension is the garment (outlines, num_edges, rotations, translations,
+    num_panels, empty_panels_mask, num_stitches, stitches, free_edges_mask, stitch_tags, or whatever the caller's loss reads), 16
+    at the most.  They are made resident and contiguous once and stored as given: whether to standardise them is the caller's
+    choice.  A table whose rows are not a multiple of 4 bytes (a bool mask of 23 panels) is kept with padded rows, and its batch is a
+    strided view of the padded output.
+
+    next() -> (features, gt) for a MeshPointSampler, gt = the gathered batch with the sampler's `segmentation` added, or (rows,
+    labels) for a StitchPairSampler; `.last_gt` is the gathered batch either way, `.index` the int32 [B] index (the dtype the
+    samplers take without a conversion launch) and `.status` int32 [1] the entries of the last row outside 0 .. G - 1, whose
+    ground-truth rows are zeros.  Every output of the feeder is a static buffer that the next call overwrites.
+    begin_epoch() draws the schedule and zeroes the cursor on the current stream; len() is the steps per epoch.  A schedule that
+    keeps a short last row is a ValueError: a captured step has one shape."""
+
+    def __init__(self, schedule, sampler, ground_truth=None):
+        if len(schedule) != schedule.num_full_batches:
+            raise ValueError('EpochFeeder needs a schedule of full batches (drop_last=True): the last of these %d rows holds %d of '
+                             '%d garments, and a captured step has one shape' % (len(schedule), schedule.data_size % schedule.batch_size,
+                                                                                  schedule.batch_size))
+        self.schedule, self.sampler = schedule, sampler
+        self.device, B = schedule.device, schedule.batch_size
+        ground_truth = dict(ground_truth or {})
+        G = None
+        for k, t in ground_truth.items():
+            if not torch.is_tensor(t) or t.dim() < 1 or t.shape[0] < 1 or t[0].numel() < 1:
+                raise ValueError('ground_truth[%r] must be a tensor whose leading dimension is the garment' % (k,))
+            G = t.shape[0] if G is None else G
+            if t.shape[0] != G:
+                raise ValueError('the ground-truth tensors hold %d and %d garments' % (G, t.shape[0]))
+        if G is None:                                     # no table: the set is the sampler's
+            G = sampler.resident.G if hasattr(sampler, 'resident') else sampler.edges3d.shape[0]
+        self.G = int(G)
+        self.resident, self.gt, outputs = {}, {}, []
+        for k, t in ground_truth.items():
+            t = t.detach().to(self.device).contiguous()
+            nb = t[0].numel() * t.element_size()
+            if nb % 4 == 0:
+                out = torch.zeros((B,) + tuple(t.shape[1:]), device=self.device, dtype=t.dtype)
+                self.gt[k] = out
+            else:                                         # rows padded to 4 bytes; the batch is a view of the padded output
+                pad = torch.zeros(self.G, (nb + 3) // 4 * 4, device=self.device, dtype=torch.uint8)
+                pad[:, :nb] = t.reshape(self.G, -1).view(torch.uint8)
+                out = torch.zeros(B, pad.shape[1], device=self.device, dtype=torch.uint8)
+                self.gt[k] = out[:, :nb].view(t.dtype).view((B,) + tuple(t.shape[1:]))
+                t = pad
+            self.resident[k] = t
+            outputs.append(out)
+        self.jobs, self.max_row_bytes = ops.feed_jobs(list(self.resident.values()), outputs) if outputs else (None, 0)
+        self.outputs = outputs
+        self.index = torch.full((B,), -1, device=self.device, dtype=torch.int32)
+        self.status = torch.zeros(1, device=self.device, dtype=torch.int32)
+        self.last_gt = self.gt
+
+    def __len__(self):
+        return self.schedule.num_full_batches
+
+    def begin_epoch(self):
+        """draws the next epoch's schedule and zeroes the cursor, on the current stream; no host read"""
+        self.schedule.draw()
+        self.schedule.cursor.zero_()
+
+    def next(self):
+        """the next batch: see the class"""
+        ops.feed_next(self.schedule.table, self.schedule.cursor, self.G, self.jobs, self.max_row_bytes, self.index, self.status)
+        out = self.sampler.sample(self.index)
+        if isinstance(self.sampler, StitchPairSampler):
+            self.last_gt = self.gt
+            return out
+        features, segmentation = out
+        self.last_gt = dict(self.gt, segmentation=segmentation)
+        return features, self.last_gt
