@@ -1,6 +1,6 @@
 // The guarded Adam step (include/gpe_hip_ext.h): the global L2 norm of the gradient arena and its per-segment norms in one pass,
 // the clip factor, the skip flag (non-finite norm / an fp16 activation word at its limit) and two counters in a 32-byte device
-// block, and a copy of the Adam kernel of gpe_train.hip that scales the gradient by the factor and leaves p, m, v alone when the
+// block, and a copy of the Adam kernel of gpe_adam.hip that scales the gradient by the factor and leaves p, m, v alone when the
 // flag is set.  Nothing is read on the host, so the whole of it can sit inside a captured step.
 //   torch.nn.utils.clip_grad_norm_ + torch.optim.Adam (nn/trainer.py:162-185; the reference itself only notices a NaN loss at the
 //   end of an epoch, nn/trainer.py:220)
@@ -213,7 +213,7 @@ extern "C" int gpe_grad_norm_finish(const double* part, const long* seg_slot, in
 }
 
 // =====================================================================================================================
-// gpe_adam_kernel (gpe_train.hip) under the guard block.  That kernel is compiled with the default floating-point contraction, and
+// gpe_adam_kernel (gpe_adam.hip) under the guard block.  That kernel is compiled with the default floating-point contraction, and
 // what the compiler fused there is part of its result; the roundings are therefore PINNED here — contraction off, every fused
 // multiply-add written out — to the ones its gfx950 code performs:
 //   gr = fma(gs, g, wd * p)        m = fma(b1, m, (1 - b1) * gr)        sq = ((1 - b2) * gr) * gr

@@ -170,6 +170,11 @@ __device__ __forceinline__ void gpe_lstm_cell_bwd(float ig, float fg, float gg, 
     carry_out = dc * fg;
 }
 
+// ---- sparsemax row width ------------------------------------------------------------------------------------------------------
+// sparsemax over rows of width W <= 32: one row per lane, the row sorted in registers by a fully unrolled odd-even transposition
+// network of this many entries (gpe_pool.hip: forward; gpe_loss.hip: the sparsemax loss runs the same sort)
+#define SPX_W 32
+
 // ---- weight slice -> LDS ----------------------------------------------------------------------------------------------------
 // copy columns [c0, c0 + CW) of every 16-byte-piece group of a packed weight into LDS with NTHR threads: piece (group, c) of the
 // pack sits at (group * Npad + c0 + c) * 16 bytes

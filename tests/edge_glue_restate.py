@@ -1,4 +1,4 @@
-"""Test infrastructure: the EdgeConv glue kernels (csrc/gpe_pointwise.hip, gpe_train.hip, gpe_rowgemm.hip) restated one by one.
+"""Test infrastructure: the EdgeConv glue kernels (csrc/gpe_edge_glue.hip, gpe_bn.hip, gpe_rowgemm.hip) restated one by one.
 
 For every kernel: a case builder (`build_<kernel>`: the exact host buffers of one call, at their padded pitches, NaN where the
 kernel must not read, a sentinel where it must not write), a plain fp64 reference written from the formula in include/gpe_hip.h

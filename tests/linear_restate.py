@@ -1,5 +1,5 @@
 """Test infrastructure: the dense Linear kernels (csrc/gpe_rowgemm.hip, gpe_smallgemm.hip, gpe_gemm_x6.hip) and the weight packer
-(csrc/gpe_pointwise.hip) restated rung by rung, in the shape of tests/edge_glue_restate.py.
+(csrc/gpe_pack.hip) restated rung by rung, in the shape of tests/edge_glue_restate.py.
 
 gpe_linear is a ladder (include/gpe_hip.h gpe_linear_path names the rungs): the bf16-pipe kernel (100, f16x3 mode only), the K <= 8
 streaming-store kernel (200), the single-stage kernel with 16- or 64-column blocks (301, 304) and the streaming kernel with 16 NT

@@ -1,4 +1,4 @@
-"""Test infrastructure: the six loss-side entry points (csrc/gpe_train.hip: gpe_pattern_loss_fwd / _bwd; csrc/gpe_stitch.hip:
+"""Test infrastructure: the six loss-side entry points (csrc/gpe_loss.hip: gpe_pattern_loss_fwd / _bwd; csrc/gpe_stitch.hip:
 gpe_stitch_loss_fwd / _bwd, gpe_stitch_renumber, gpe_panel_shift) restated one by one.
 
 For every entry point: a case builder (`build(kernel, spec)`: the exact host buffers of one call; predictions are views into

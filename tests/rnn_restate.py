@@ -145,7 +145,7 @@ def bwd_ws(gates, L, T, Bn, H, st, have_device=False):
 
 
 def pack_kpad(K):
-    """K extent of a plain packed weight (csrc/gpe_pointwise.hip gpe_pack_kpad)"""
+    """K extent of a plain packed weight (csrc/gpe_pack.hip gpe_pack_kpad)"""
     k16 = rup(K, 16)
     return 160 if 96 < k16 < 160 else 208 if 160 < k16 < 208 else k16
 
