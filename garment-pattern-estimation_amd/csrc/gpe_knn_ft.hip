@@ -246,8 +246,11 @@ __global__ __launch_bounds__(64 * NW) void gpe_knn_ft_kernel(const _Float16* __r
             const float4 np = *reinterpret_cast<const float4*>(&npS[tp * KNN_TC + 16 * mt + 4 * g]);
             const float4 is = *reinterpret_cast<const float4*>(&isS[tp * KNN_TC + 16 * mt + 4 * g]);
             float4 d;
-            d.x = __builtin_fmaf(fq * is.x, acc[mt][0], nq + np.x); d.y = __builtin_fmaf(fq * is.y, acc[mt][1], nq + np.y);
-            d.z = __builtin_fmaf(fq * is.z, acc[mt][2], nq + np.z); d.w = __builtin_fmaf(fq * is.w, acc[mt][3], nq + np.w);
+            // the candidate's scale goes to the product sum first: fq * is underflows to 0 once both rows lie below about 2^-49, which
+            // left d~ = |q|^2 + |p|^2 for every pair (data kind `tiny`).  is * acc is a power-of-two scaling: exact unless
+            // acc has cancelled so far that the result is subnormal, and what is lost then is below 2^-149, far inside E
+            d.x = __builtin_fmaf(fq, is.x * acc[mt][0], nq + np.x); d.y = __builtin_fmaf(fq, is.y * acc[mt][1], nq + np.y);
+            d.z = __builtin_fmaf(fq, is.z * acc[mt][2], nq + np.z); d.w = __builtin_fmaf(fq, is.w * acc[mt][3], nq + np.w);
             d.x = d.x > 0.f ? d.x : 0.f; d.y = d.y > 0.f ? d.y : 0.f; d.z = d.z > 0.f ? d.z : 0.f; d.w = d.w > 0.f ? d.w : 0.f;
             if (tail) {                                   // candidates past the cloud never qualify
                 const int cb = c0 + 16 * mt + 4 * g;

@@ -1,4 +1,4 @@
-// Which graph-search kernel runs (gpe_knn / gpe_knn_ws_bytes): host code only.  What the three kernel files
+// Which graph-search kernel runs (gpe_knn / gpe_knn_ws_bytes / gpe_knn_path): host code only.  What the three kernel files
 // (gpe_knn.hip, gpe_knn3.hip, gpe_knn_ft.hip) and the entry points (gpe_knn_search.hip) share on the host lives here ONCE:
 //   the constants more than one file needs, the measurement switches, the call as received, the workspace layout,
 //   gpe_knn_plan — the whole selection ladder as a pure function — and the launchers' declarations.
@@ -93,13 +93,14 @@ static inline GpeKnnWs gpe_knn_ws_layout(int B, int N, int C)
 static inline size_t gpe_knn_split_bytes(int B, int N, int nsplit, int k) { return (size_t)B * N * nsplit * k * sizeof(unsigned long long); }
 
 // ---- the plan ------------------------------------------------------------------------------------------------------------
-enum GpeKnnPath {
-    GPE_KNN_NOTHING,      // nothing is launched: gpe_knn returns rc (bad arguments, B == 0, a grid past 2^31 workgroups)
-    GPE_KNN_SORTED3,      // 1a  xyz cloud, sorted along a Morton curve, tile pruning (gpe_knn3.hip); writes order_out itself
-    GPE_KNN_ALLPAIRS,     // 1b / 2a  every distance by the defined chain
-    GPE_KNN_SCAN,         // 2b  fp16-pipe threshold scan (gpe_knn_ft.hip) + recheck
-    GPE_KNN_LISTS,        // 2c  fp16-pipe ordered-list kernel <2> / <5> / <8> + one-query recheck
-    GPE_KNN_F32FILTER     // 2d  fp32 matrix-pipe filter + one-query recheck
+#define GPE_KNN_PLAN_FIELDS 24             // numbers gpe_knn_path writes to plan_out (include/gpe_hip.h fixes their order)
+enum GpeKnnPath {         // the values are gpe_knn_path's return codes (include/gpe_hip.h): they do not change
+    GPE_KNN_NOTHING = 0,  // nothing is launched: gpe_knn returns rc (bad arguments, B == 0, a grid past 2^31 workgroups)
+    GPE_KNN_SORTED3 = 1,  // 1a  xyz cloud, sorted along a Morton curve, tile pruning (gpe_knn3.hip); writes order_out itself
+    GPE_KNN_ALLPAIRS = 2, // 1b / 2a  every distance by the defined chain
+    GPE_KNN_SCAN = 3,     // 2b  fp16-pipe threshold scan (gpe_knn_ft.hip) + recheck
+    GPE_KNN_LISTS = 4,    // 2c  fp16-pipe ordered-list kernel <2> / <5> / <8> + one-query recheck
+    GPE_KNN_F32FILTER = 5 // 2d  fp32 matrix-pipe filter + one-query recheck
 };
 struct GpeKnnPlan {
     GpeKnnPath path; int rc;

@@ -111,6 +111,23 @@ int gpe_knn(const float* x, int B, int N, int C, int ldx, int k, int32_t* idx, i
  * scanned tile by tile with an exact box bound that prunes tiles (gpe_knn3.hip; GPE_KNN_SORTED=0 disables); C >= 16 and
  * k <= 48 — a matrix-pipe filter + exact recheck (C <= 256: on the fp16 pipe, as a threshold scan for C <= 160 and k <= 32, else
  * with ordered lists; C > 256: on the fp32 pipe); otherwise the all-pairs VALU kernel.  The whole ladder: csrc/gpe_knn_plan.h. */
+/* Which kernels a gpe_knn call runs, and the numbers of its plan.  Added without a version bump (gpe_abi_version() stays 7): one
+ * host-only query, nothing else changes.  HOST ONLY: x and ws are looked at for NULL and for their alignment and never followed, no
+ * HIP call is made beyond the CU count (256 without a GPU, less gpe_reserve_cus_set) and nothing is allocated; gpe_knn takes its
+ * plan from the same function.  idx counts as given; has_idx_glob / has_order_in / has_order_out: that pointer is not NULL.
+ * switches: NULL = this process's GPE_KNN_* measurement switches (read under GPE_DEBUG=1), else ten ints in the order
+ *   PROBE, PIN, VEC, SPLIT, EXACT, F32FILTER, SORTED, NOORDER, FT, RR2      (defaults 0, -1, 0, 0, 0, 0, 1, 0, 1, 1)
+ * Returns -22 where gpe_knn refuses the call, 0 for B == 0 (nothing is launched), else the path:
+ *   1 sorted cloud (xyz)   2 all-pairs   3 threshold scan + recheck   4 ordered lists + recheck   5 fp32 filter + recheck
+ * plan_out (may be NULL; written only with a path) receives 24 numbers:
+ *   [0] identity (order_out gets the identity)  [1] pin (clouds pinned to XCDs)  [2] tiles  [3] nsplit (candidate pieces)
+ *   [4] vec (staging vector floats: all-pairs, fp32 filter)  [5] nblocks (workgroups of the main kernel)  [6] probe
+ *   [7] smallc (all-pairs C <= 4 instance)  [8] K2  [9] CP  [10] NB  [11] the bit pattern of ce (filters' error-bound factor)
+ *   [12] wide (scan: 128-query workgroups)  [13] qtiles  [14] rerank2  [15] unsorted  [16] an order hint is in use
+ *   [17 - 23] byte offsets from ws of part, norms, cmax, planes, iscale, xs, tb; -1 = region unused
+ * A field a path does not use is 0.  The thresholds are the library's to change; the codes and the positions in plan_out are not. */
+int gpe_knn_path(const float* x, int B, int N, int C, int ldx, int k, int has_idx_glob, int has_order_in, int has_order_out,
+                 const void* ws, long ws_bytes, const int* switches, long* plan_out);
 
 /* reverse adjacency of the kNN graph (needed by the gather's backward = scatter-add into x_j rows):
  * rev_off [B][N+1] int32 (local offsets: the exclusive scan of the in-degrees, rev_off[N] = N*k), rev_edge [B][N*k] int32 =

@@ -25,7 +25,7 @@ def test_header_declares_expected_surface():
                     'gpe_attn_pool_ws', 'gpe_packed_ngates_size', 'gpe_rnn_seq_bwd_ws', 'gpe_rnn_seq_fwd_ws', 'gpe_debug_get', 'gpe_reserve_cus_set', 'gpe_f16x3_min_rows',
                     'gpe_f16x3_min_rows_set', 'gpe_edge_ws_bytes', 'gpe_knn_ws_bytes', 'gpe_packed_planes_size', 'gpe_edge_lazy_dz3_ok',
                     'gpe_pack_job_blocks', 'gpe_adam_hyper', 'gpe_linear_path', 'gpe_redgemm_path',
-                    'gpe_rnn_seq_fwd_path', 'gpe_rnn_seq_bwd_path'):
+                    'gpe_rnn_seq_fwd_path', 'gpe_rnn_seq_bwd_path', 'gpe_knn_path'):
             continue
         assert res == 'i' and args[-1] == 'p', name
 
@@ -36,7 +36,7 @@ def test_parser_binds_every_declaration_of_the_header():
     src = re.sub(r'/\*.*?\*/', ' ', src, flags=re.S)
     src = re.sub(r'//[^\n]*', ' ', src)
     declared = re.findall(r'\b(gpe_\w+)\s*\(', src)
-    assert len(declared) == len(set(declared)) == 122
+    assert len(declared) == len(set(declared)) == 123
     sigs = _lib.parse_header()
     assert len(sigs) == len(declared) and set(sigs) == set(declared)
 

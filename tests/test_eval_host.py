@@ -28,7 +28,7 @@ def test_the_eval_header_is_bound_and_exported():
     main, ext = _lib.parse_header(), _lib.parse_header(_lib.EXT_HEADER_PATH)
     fit, ev = _lib.parse_header(_lib.FIT_HEADER_PATH), _lib.parse_header(_lib.EVAL_HEADER_PATH)
     assert set(ev) == set(EVAL) and not set(ev) & (set(main) | set(ext) | set(fit))
-    assert len(main) == 122 and set(fit) == {'gpe_fit_leaves', 'gpe_fit_part', 'gpe_fit_finish'}
+    assert len(main) == 123 and set(fit) == {'gpe_fit_leaves', 'gpe_fit_part', 'gpe_fit_finish'}
     assert set(ext) == {'gpe_grad_norm_slots', 'gpe_grad_norm_part', 'gpe_grad_norm_finish', 'gpe_adam_step_guarded',
                         'gpe_adam_step_guarded_dev'}
     assert _lib.HEADERS == (_lib.HEADER_PATH, _lib.EXT_HEADER_PATH) and _lib.FEATURE_HEADERS == (_lib.FIT_HEADER_PATH,)

@@ -115,6 +115,7 @@ def test_knn_xyz_sorted_cloud_bit_exact(gpe, B, N, k, data):
 
 
 # Which path a case reaches (csrc/gpe_knn_plan.h; NB = ceil(C / 32) blocks of 32 channels):
+# (asserted, case by case through gpe_knn_path, in tests/test_gpu_knn.py; these are the full-size cases)
 #   threshold scan (C <= 160, k <= 32): C = 32, 33, 64, 100, 150 with k = 5 .. 20; k = 32 is its last k
 #   ordered-list kernel <2> / <5> (C <= 160, 32 < k <= 48): C = 32 (one block of queries, a ragged tile), 33 (two blocks);
 #     C = 150 with k = 48 (the largest filtered k, K2 = 56), C = 160 (NB = 5)
