@@ -12,7 +12,7 @@ ops_eval on top of _opbase and are re-exported by ops.  `ops` is imported before
 
 The directory name contains '-', so import it with importlib or through the `gpe_amd` alias module at the
 repository root:  `import gpe_amd; from gpe_amd import nets`."""
-from . import _lib, streams, _opbase, ops, ops_stitch, ops_losses, ops_data, ops_eval, net_blocks, nets, metrics, optim, parallel, staging, configs, patterns, evaluation  # noqa: F401
+from . import _lib, streams, _opbase, ops, ops_stitch, ops_losses, ops_data, ops_scan, ops_eval, net_blocks, nets, metrics, optim, parallel, staging, configs, patterns, evaluation  # noqa: F401
 from ._lib import set_math, get_math, set_f16x3_min_rows, set_reserved_cus, get_reserved_cus  # noqa: F401
 
-__all__ = ['_lib', 'streams', '_opbase', 'ops', 'ops_stitch', 'ops_losses', 'ops_data', 'ops_eval', 'net_blocks', 'nets', 'metrics', 'optim', 'parallel', 'staging', 'configs', 'patterns', 'evaluation', 'set_math', 'get_math', 'set_f16x3_min_rows', 'set_reserved_cus', 'get_reserved_cus']
+__all__ = ['_lib', 'streams', '_opbase', 'ops', 'ops_stitch', 'ops_losses', 'ops_data', 'ops_scan', 'ops_eval', 'net_blocks', 'nets', 'metrics', 'optim', 'parallel', 'staging', 'configs', 'patterns', 'evaluation', 'set_math', 'get_math', 'set_f16x3_min_rows', 'set_reserved_cus', 'get_reserved_cus']

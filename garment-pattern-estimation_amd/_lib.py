@@ -1,6 +1,6 @@
 """ctypes binding of libgpe_hip.so (C ABI: include/gpe_hip.h, plus the additions since ABI version 7 in
 include/gpe_hip_ext.h, the feature headers of FEATURE_HEADERS: include/gpe_hip_fit.h, of EVAL_HEADERS: include/gpe_hip_eval.h, of
-PLACE_HEADERS: include/gpe_hip_place.h, of FRAMEWORK_HEADERS: include/gpe_hip_framework.h, and of FEED_HEADERS: include/gpe_hip_feed.h).  The headers are the one description
+PLACE_HEADERS: include/gpe_hip_place.h, of FRAMEWORK_HEADERS: include/gpe_hip_framework.h, of FEED_HEADERS: include/gpe_hip_feed.h, and of SCAN_HEADERS: include/gpe_hip_scan.h).  The headers are the one description
 of the ABI and both sides are checked against them: the signatures here are parsed from it (parse_header; a declaration it cannot bind raises,
 and lib() fails on a declared symbol the library does not export), and every definition in csrc/ is compiled with it
 included (csrc/gpe_common.h), so a definition that differs from its declaration does not compile.  There is NO fallback:
@@ -34,6 +34,10 @@ FRAMEWORK_HEADERS = (FRAMEWORK_HEADER_PATH,)
 # the epoch feed (include/gpe_hip_feed.h: the balanced batch schedule and the per-step gather), in a tuple of its own and walked as strictly
 FEED_HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'gpe_hip_feed.h')
 FEED_HEADERS = (FEED_HEADER_PATH,)
+# prediction from raw scans (include/gpe_hip_scan.h: model clouds drawn from resident point sets, labels handed back), in a tuple of its
+# own and walked as strictly
+SCAN_HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'gpe_hip_scan.h')
+SCAN_HEADERS = (SCAN_HEADER_PATH,)
 
 _CT = {'p': ctypes.c_void_p, 'i': ctypes.c_int, 'l': ctypes.c_long, 'f': ctypes.c_float, 'd': ctypes.c_double}
 
@@ -81,7 +85,7 @@ def lib():
                 'libgpe_hip.so not built: run `python -c "import __graft_entry__ as g; g.build()"` '
                 '(hipcc --offload-arch=gfx950).  There is no CPU fallback for the product path.')
         l = ctypes.CDLL(LIB_PATH)
-        for header in HEADERS + FEATURE_HEADERS + EVAL_HEADERS + PLACE_HEADERS + FRAMEWORK_HEADERS + FEED_HEADERS:
+        for header in HEADERS + FEATURE_HEADERS + EVAL_HEADERS + PLACE_HEADERS + FRAMEWORK_HEADERS + FEED_HEADERS + SCAN_HEADERS:
             for name, (res, args) in parse_header(header).items():
                 fn = getattr(l, name)      # AttributeError here = header/library mismatch: fail loudly
                 fn.restype = _CT[res]

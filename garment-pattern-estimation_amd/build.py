@@ -39,12 +39,12 @@ def _stale(obj, src):
         return True
     t = os.path.getmtime(obj)
     # this file is a dependency too: the compile flags (FLAGS / EXTRA_FLAGS) live here; so are the public headers (gpe_hip.h, the
-    # additions since ABI version 7, gpe_hip_ext.h, and the feature headers gpe_hip_fit.h, gpe_hip_eval.h, gpe_hip_place.h, gpe_hip_framework.h and gpe_hip_feed.h), which
+    # additions since ABI version 7, gpe_hip_ext.h, and the feature headers gpe_hip_fit.h, gpe_hip_eval.h, gpe_hip_place.h, gpe_hip_framework.h, gpe_hip_feed.h and gpe_hip_scan.h), which
     # csrc/gpe_common.h includes so that every definition is checked against its declaration
     inc = os.path.join(os.path.dirname(HERE), 'include')
     deps = [os.path.join(CSRC, src), os.path.abspath(__file__)]
     deps += [os.path.join(inc, h) for h in ('gpe_hip.h', 'gpe_hip_ext.h', 'gpe_hip_fit.h', 'gpe_hip_eval.h', 'gpe_hip_place.h',
-                                              'gpe_hip_framework.h', 'gpe_hip_feed.h')]
+                                              'gpe_hip_framework.h', 'gpe_hip_feed.h', 'gpe_hip_scan.h')]
     deps += [os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith('.h')]
     return any(os.path.getmtime(d) > t for d in deps)
 

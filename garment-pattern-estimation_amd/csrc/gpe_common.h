@@ -18,6 +18,8 @@
 #include "../../include/gpe_hip_framework.h"
 // ... and the epoch feed (the balanced batch schedule and the per-step gather), bound through _lib.FEED_HEADERS
 #include "../../include/gpe_hip_feed.h"
+// ... and the prediction from raw scans (model clouds drawn from resident point sets, labels handed back), bound through _lib.SCAN_HEADERS
+#include "../../include/gpe_hip_scan.h"
 
 #define GPE_OK 0
 #define GPE_EINVAL (-22)

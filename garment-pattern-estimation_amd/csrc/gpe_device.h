@@ -64,7 +64,7 @@ __device__ __forceinline__ gpe_u32x4 gpe_philox4x32(unsigned c0, unsigned c1, un
 }
 // the samplers' block of one decision: key = the seed, counter = (item | kind << 28, attempt | b << 8, draw lo, draw hi), b the batch
 // slot (b8 = b << 8).  The kinds in use: 0 .. 4 gpe_stitch_sample.hip, 8 and 9 gpe_mesh_sample.hip, 10 .. 12 gpe_epoch_feed.hip
-// (there the state's second word is the epoch, and b is a slot of a batch: include/gpe_hip_feed.h)
+// (there the state's second word is the epoch, and b is a slot of a batch: include/gpe_hip_feed.h), 13 gpe_scan_sample.hip
 struct gpe_rng {
     unsigned k0, k1, d0, d1, b8;
     __device__ __forceinline__ gpe_u32x4 operator()(int kind, unsigned item, unsigned attempt = 0) const

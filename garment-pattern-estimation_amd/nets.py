@@ -76,7 +76,10 @@ class BaseModule(nn.Module):
         if not self._predicts_patterns:
             raise NotImplementedError('%s.predict_pattern: the model predicts no panels (its stitches come from predict_stitches)'
                                       % self.__class__.__name__)
-        preds = self.predict(positions_batch, route=route)
+        return self._decode(self.predict(positions_batch, route=route), data_config, stitches)
+
+    @staticmethod
+    def _decode(preds, data_config, stitches=None):
         return DecodedPatterns(ops.pattern_decode(preds, data_config['standardize'],
                                                   bool(data_config.get('explicit_stitch_tags', False)), stitches=stitches))
 
@@ -92,6 +95,27 @@ class BaseModule(nn.Module):
                                'pattern_converter.py:415)')
         d = self.predict_pattern(positions_batch, data_config, route=route).place()
         return d.attach_pair_stitches(stitch_model.predict_stitches(d.edges3d, d.num_edges, stitch_data_stats, **kw))
+
+    def predict_scans(self, sampler, index, data_config, stitch_model=None, stitch_data_stats=None, route='auto', **kw):
+        """Prediction from raw scans (the reference's evaluation_scripts/predict_per_example.py): sampler.sample(index) draws the
+        model's clouds from the resident scans (`sampler` a staging.ScanSampler, `index` the scan of every batch slot), then
+        predict_garment on them, or predict_pattern(...).place() without a stitch model.  -> the DecodedPatterns, with `scan_labels`
+        (int32, resident-sized: the predicted panel of every point of the batch's scans, -1 elsewhere; sampler.labels) and
+        `scan_picked` (int32 [B, N]: the drawn points) attached when the prediction carries `att_weights` (the attention model with
+        the segmentation loss), both None otherwise.  No host read."""
+        if not self._predicts_patterns:
+            raise NotImplementedError('%s.predict_scans: the model predicts no panels' % self.__class__.__name__)
+        if stitch_model is not None and stitch_model.training:
+            raise RuntimeError('predict_scans runs the eval-mode stitch classifier: call .eval() on it first')
+        features, picked = sampler.sample(index)
+        preds = self.predict(features, route=route)
+        d = self._decode(preds, data_config).place()
+        if stitch_model is not None:
+            d.attach_pair_stitches(stitch_model.predict_stitches(d.edges3d, d.num_edges, stitch_data_stats, **kw))
+        att = preds.get('att_weights')
+        d.scan_labels = sampler.labels(att) if att is not None else None
+        d.scan_picked = picked if att is not None else None
+        return d
 
     _predicts_patterns = False
 

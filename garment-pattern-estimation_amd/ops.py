@@ -1837,4 +1837,5 @@ class RaggedMaxFn(torch.autograd.Function):
 from .ops_stitch import *  # noqa: E402,F401,F403
 from .ops_losses import *  # noqa: E402,F401,F403
 from .ops_data import *  # noqa: E402,F401,F403
+from .ops_scan import *  # noqa: E402,F401,F403
 from .ops_eval import *  # noqa: E402,F401,F403

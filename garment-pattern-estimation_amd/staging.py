@@ -15,7 +15,11 @@ BalancedBatchSchedule and EpochFeeder make an epoch self-feeding (DatasetWrapper
 nn/data/wrapper.py:78-89, nn/data/utils.py:16-92): which garments form every batch is drawn on the device once per epoch, the
 garments' ground truth stays in HBM, and each step takes its index and ground-truth rows from there without a tensor from the host.
 
-The statistics both samplers standardise with are fitted on the device as well (fit_feature_stats of either sampler,
+ScanSampler is the input side of prediction from raw scans (nn/evaluation_scripts/predict_per_example.py): point clouds of
+arbitrary size stay in HBM and every call draws the model's clouds from them; its labels() hand the attention model's per-point panel
+labels back to every point of a scan.
+
+The statistics both training samplers standardise with are fitted on the device as well (fit_feature_stats of either sampler,
 fit_pattern_standardization for the ground truth: the reference's standardize(training), nn/data/datasets.py:596-645, 1018-1041)."""
 import numpy as np
 import torch
@@ -273,6 +277,78 @@ class MeshPointSampler:
         if install:
             self.f_shift, self.f_scale = [float(v) for v in stats['f_shift']], [float(v) for v in stats['f_scale']]
         return stats
+
+
+def load_scan_points(path):
+    """a scan from a .txt file: the first three numbers of every line are a point (load_points of the reference's
+    nn/evaluation_scripts/predict_per_example.py; blank lines are skipped, a line with fewer than three numbers is a ValueError)
+    -> float64 [n, 3]"""
+    points = []
+    with open(path, 'r') as f:
+        for no, line in enumerate(f, 1):
+            coords = [float(x) for x in line.split()]
+            if not coords:
+                continue
+            if len(coords) < 3:
+                raise ValueError('%s:%d: a point needs three numbers (got %d)' % (path, no, len(coords)))
+            points.append(coords[:3])
+    return np.asarray(points, dtype=np.float64).reshape(-1, 3)
+
+
+class ScanSampler:
+    """The pattern model's input clouds drawn on the device from raw scans that stay in HBM: what the reference's
+    nn/evaluation_scripts/predict_per_example.py does per scan on the host (np.random.permutation(n)[:mesh_samples], :137-141,
+    FeatureStandartization, :143-144, stack), for a whole batch in one call (ops.cloud_points_sample) and as often as the caller
+    likes: several draws per scan show how stable a prediction is.  It mirrors MeshPointSampler.
+
+    clouds: a list of [n, 3] arrays (load_scan_points reads the reference's .txt files), or an ops.cloud_resident(...) built from
+    one; data_stats: {'f_shift', 'f_scale'} of the points, or None.
+
+        sampler = ScanSampler([load_scan_points(p) for p in paths], stats, mesh_samples=2000)
+        patterns = model.predict_scans(sampler, index, data_config, stitch_model, stitch_stats)
+
+    The sampler owns the resident set, the generator state {seed, draw} (`.state`, int64 [2] on the device: every call of sample()
+    advances draw by one on the device, so a captured call draws new clouds on every replay), the kernel's ticket word and its
+    workspace.  `.status` is the int32 [B] status of the last call (N - n repeated rows of a scan of n < N points, 0 otherwise; -1 an
+    empty scan, -2 an index outside the set).  reseed(seed, draw) restarts the sequence: the draws are a function of (seed, draw,
+    batch slot, data).  labels(att_weights) hands the attention model's per-point panel labels of the last sample back to every
+    point of its scans."""
+
+    def __init__(self, clouds, data_stats=None, mesh_samples=2000, seed=0):
+        self.resident = ops.cloud_resident(clouds)
+        self.f_shift = [float(v) for v in data_stats['f_shift']] if data_stats else None
+        self.f_scale = [float(v) for v in data_stats['f_scale']] if data_stats else None
+        self.mesh_samples = int(mesh_samples)
+        self.device = self.resident.device
+        if not self.resident.points4.is_cuda:
+            raise RuntimeError('gpe ops need tensors on the MI355X (got a %s resident set); there is no CPU path' % self.device)
+        self.state = ops.stitch_sample_state(seed, 0, self.device)
+        self.ticket = torch.zeros(1, device=self.device, dtype=torch.int32)
+        self.status = self.index = self.picked = None
+
+    @classmethod
+    def from_config(cls, clouds, dataset_config, seed=0):
+        """dataset_config: the 'dataset' dict of a pattern-model experiment ('mesh_samples', 'standardize')"""
+        keys = ('mesh_samples',)
+        return cls(clouds, dataset_config.get('standardize'), seed=seed, **{k: dataset_config[k] for k in keys if k in dataset_config})
+
+    def reseed(self, seed, draw=0):
+        """the next call draws with (seed, draw); a copy queued on the current stream, no device read"""
+        self.state.copy_(ops.stitch_sample_state(seed, draw, 'cpu'), non_blocking=False)
+
+    def sample(self, index):
+        """index: integer [B] tensor on the device -> (features fp32 [B, mesh_samples, 3], picked int32 [B, mesh_samples])"""
+        features, self.picked, self.status = ops.cloud_points_sample(
+            self.resident, index, self.mesh_samples, self.state, self.ticket, self.f_shift, self.f_scale)
+        self.index = index
+        return features, self.picked
+
+    def labels(self, att_weights, out=None):
+        """att_weights fp32 [B, mesh_samples, P] of a prediction on the last sample -> int32 [T], resident-sized: the panel of every
+        point of the scans of that batch (ops.cloud_labels), -1 on the scans outside it"""
+        if self.picked is None:
+            raise RuntimeError('ScanSampler.labels hands back the labels of the last sample: call sample(index) first')
+        return ops.cloud_labels(self.resident, self.index, self.picked, att_weights, out=out)
 
 
 def balanced_quotas(sizes, batch_size):
